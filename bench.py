@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the self-play hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G] [--round R] [--sims S]
-    python bench.py --round 16384 --no-extras      # the round size `value` was measured on until round 2
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G] [--round R] [--sims S] [--dump-outputs DIR] [--full]
+    python bench.py --round 16384                  # the round size `value` was measured on until round 2
 
 A "step" is one self-play round on one GPU: R Tic-Tac-Toe games played to the
 end on G concurrent game trees (slots that finish a game take the next one, as
@@ -14,8 +14,12 @@ finished games to rank 0's replay buffer (and preceded, once, by the broadcast o
 the weights from rank 0).  Weights are synthetic (random-init RecurrentNet(2,1,64,2),
 seed 0); games need no dataset.  Prints ONE JSON line on rank 0.
 
-Extra keys (N = 1)
-  expansions_per_s, simulations_per_s   the metric's second half
+A plain run sets up, warms up, times the K steps and prints the line (with `expansions_per_s`, `simulations_per_s`,
+the metric's second half).  --dump-outputs DIR also writes what the last timed step computed -- SelfPlayEngine.export()
+of a fixed, seeded sample of the round's games and the round's counters, float32 / float64 .npy files -- so that two
+builds can be compared output for output (the same arguments give the same inputs).
+
+Extra keys (only with --full; N = 1)
   roofline          the dominant kernel, selfplay_kernel, against the dense BF16 MFMA peak: achieved = the bf16 MFMA
                     FLOPs it executes (six split terms per float32 product) over its HIP-event time; the
                     algorithmic float32 figure (in-bounds taps only) is the sub-key `algorithmic_f32`;
@@ -165,6 +169,26 @@ def git_commit():
                                        text=True).strip()
     except Exception:
         return os.environ.get("NZ_COMMIT")      # a snapshot without .git (the GPU box): the caller may say
+
+
+DUMP_GAMES = 16384     # games of the round in --dump-outputs: about 27 MB of .npy files
+
+
+def dump_outputs(eng, out_dir, suffix=""):
+    """What the last play() computed, as its caller receives it: SelfPlayEngine.export() for a fixed, seeded sample of
+    the round's games (`games` = their indices in the round) and the round's counters.  Integer arrays are written as
+    float64 (exact)."""
+    r = eng.export()
+    n = len(r["lengths"])
+    games = np.sort(np.random.RandomState(0).choice(n, min(n, DUMP_GAMES), replace=False))
+    c = eng.counters()
+    arrays = {k: v[games] for k, v in r.items()}
+    arrays["games"] = games
+    arrays["counters"] = np.array([c[k] for k in ("simulations", "expansions", "select_nodes", "select_children",
+                                                  "new_nodes")])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v.astype(np.float32 if v.dtype == np.float32 else np.float64))
 
 
 def scs_config4(device, games_per_tree=1):
@@ -394,17 +418,24 @@ def main():
                          "pay four times as often")
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--iters", type=int, default=2, help="recurrent iterations")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-kernel measurements after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, roofline.traffic's "
+                         "counter passes and the per-kernel / other-configuration keys after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a seeded sample of the round's games) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-kernel measurements after the timed steps")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc); the "
                          "stored measurement of profiles/ is quoted instead")
     ap.add_argument("--rounds-in-flight", type=int, default=0,
-                    help="also measure the rounds with this many engines in flight (key rounds_in_flight_N); not part of "
-                         "the default run: overlapped launches would spoil the kernel's average duration in a "
+                    help="with --full: also measure the rounds with this many engines in flight (key rounds_in_flight_N); "
+                         "not part of the default run: overlapped launches would spoil the kernel's average duration in a "
                          "rocprofv3 trace of the same command")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     n_round = args.round if args.round > 0 else 16 * args.games
     n_small = 4 * args.games                  # the round size of `round_4x`, `gamer_surface` and `rounds_in_flight_N`
 
@@ -420,11 +451,11 @@ def main():
 
     # the CPU baseline runs first, in worker processes, before this process touches the GPU
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.sims, args.cpu_seconds)
     # ... and so do the two counter passes for roofline.traffic (child processes under rocprofv3)
     traffic_live = None
-    if world == 1 and rank == 0 and not args.no_extras and not args.no_live_traffic:
+    if args.full and world == 1 and rank == 0 and not args.no_extras and not args.no_live_traffic:
         traffic_live = live_traffic(args, n_round)
 
     import torch
@@ -512,7 +543,10 @@ def main():
         out["replay_gather"] = {"ranks_seen": gather.ranks_seen, "games_saved": gather.games_saved,
                                 "buffer_positions": shared.len(), "buffer_games": shared.played_games()}
 
-    if not args.no_extras and world == 1:
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, "" if world == 1 else "_rank%d" % rank)
+
+    if args.full and not args.no_extras and world == 1:
         flops_pos = eng.net_flops_per_position()
         bf16_pos, f32_pos = eng.net_matrix_flops_per_position()
 
