@@ -120,6 +120,8 @@ constexpr int NET_KG_DWORDS = 9 * 3 * 64 * 4;
 constexpr int NET_ACT_BUFFERS = 2;                 // activation buffers in LDS (ping-pong)
 constexpr int NET_DST_POLICY = NET_ACT_BUFFERS;    // NetJob::dst: policy logits out
 constexpr int NET_DST_VALUE = NET_ACT_BUFFERS + 1; // NetJob::dst: value out
+constexpr int NET_DST_STRIP = NET_ACT_BUFFERS + 2; // NetJob::dst: the 16-channel strip (policy head's second tile, net_dev.hpp)
+constexpr int NET_SSLOT_SPLIT = -1;                // NetJob::sslot: K group read from src slots 6-7 (quads 0-1) + the strip (2-3)
 
 // The network is compiled on the host into one job list per wave (net_dev.hpp).
 // A job is one (conv layer, 16-channel output tile, output-cell group) unit; the
@@ -128,15 +130,16 @@ struct NetJob {
   int32_t w_off;       // dword offset of this (layer, n-tile)'s packed main weights [kgroup][tap][piece][lane][8 bf16]
   int32_t wx_off;      // float offset of its packed input-plane weights [tap][lane]
   int32_t next_w_off;  // w_off of the next job of this wave that reads weights, or -1 (prefetch target)
-  int16_t kgroups;     // 32-channel K groups read from the source activation buffer
-  int16_t nt;          // output tile: channels 16 nt .. 16 nt + 15
+  int8_t kgroups;      // 32-channel K groups read from the source activation buffer
+  int8_t sslot;        // first 16-byte slot of the K groups in the source rows (0 or 2, 4, 6), or NET_SSLOT_SPLIT
+  int16_t nt;          // output tile: channels 16 nt .. 16 nt + 15 (weights, network outputs)
   int8_t extra;        // 1: also read the (<= 4) input planes as one extra K step
   int8_t og;           // output-cell group (net_dev.hpp OG_MASK); OG_NONE = no work, barrier only
   int8_t src, dst;     // activation buffers 0..1; dst NET_DST_POLICY / NET_DST_VALUE = network outputs
   int8_t res;          // residual buffer or -1
   int8_t act;          // 0 none, 1 relu, 2 tanh, 3 elu
   int8_t stage_end;    // 1: workgroup barrier after this job
-  int8_t pad;
+  int8_t dtile;        // 16-channel tile of the destination rows the epilogue writes (dst a buffer or the strip)
 };
 constexpr int NET_WAVES_HOST = 8;
 constexpr int NET_MAX_JOBS = 192;

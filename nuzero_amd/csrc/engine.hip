@@ -197,42 +197,88 @@ PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vecto
 // stage carries the barrier.
 struct StageConv {
   int tensor, src, dst, res, act;
-  bool split;   // each output tile may be cut into output-cell groups (halves or quarters) to give every wave a unit
+  bool split;      // each output tile may be cut into output-cell groups (halves or quarters) to give every wave a unit
+  int sslot = 0;   // first 16-byte slot of the K groups in the source rows, or NET_SSLOT_SPLIT (net_dev.hpp)
+  int dtile = 0;   // destination tile of output tile 0 (dst a buffer): tiles past the fourth go to the strip
 };
 const int og_taps[7] = {49, 13, 12, 12, 12, 26, 23};   // (input cell, tap) pairs per output-cell group (net_dev.hpp og_mask)
+const int JOB_OVERHEAD = 12;   // a job's epilogue and start-up beyond its MFMAs, in the cost units of add_stage (32 cycles)
 bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::vector<StageConv>& stage) {
   struct Unit { NetJob job; int cost; };
-  std::vector<Unit> units;
+  struct Tile { const StageConv* sc; int nt; };
+  std::vector<Tile> tiles;
   for (const StageConv& sc : stage) {
     const PackedConv& pc = convs[sc.tensor];
-    for (int nt = 0; nt < pc.ntiles; ++nt) {
-      if (!sc.split || pc.ntiles >= NET_WAVES_HOST) return false;   // whole-tile jobs (group 0) are not compiled in
-      const int pieces = 2 * pc.ntiles >= NET_WAVES_HOST ? 2 : 4;
-      const int og_first = pieces == 1 ? 0 : pieces == 2 ? 5 : 1, og_last = pieces == 1 ? 0 : pieces == 2 ? 6 : 4;
-      for (int og = og_first; og <= og_last; ++og) {
+    if (!sc.split || pc.ntiles >= NET_WAVES_HOST) return false;   // whole-tile jobs (group 0) are not compiled in
+    for (int nt = 0; nt < pc.ntiles; ++nt) tiles.push_back({&sc, nt});
+  }
+  // the units of the stage when the tiles in `quarters` (a bit mask) are cut in four and the others in two
+  auto make_units = [&](unsigned quarters, std::vector<Unit>& units) {
+    units.clear();
+    for (size_t t = 0; t < tiles.size(); ++t) {
+      const StageConv& sc = *tiles[t].sc;
+      const PackedConv& pc = convs[sc.tensor];
+      const int nt = tiles[t].nt;
+      const bool q = (quarters >> t) & 1;
+      for (int og = q ? 1 : 5; og <= (q ? 4 : 6); ++og) {
         NetJob j{};
         j.w_off = pc.w_off + nt * pc.kgroups * NET_KG_DWORDS;
         j.wx_off = pc.wx_off + nt * 9 * 64;
-        j.kgroups = (int16_t)pc.kgroups;
+        j.kgroups = (int8_t)pc.kgroups;
+        j.sslot = (int8_t)sc.sslot;
         j.nt = (int16_t)nt;
         j.extra = (int8_t)pc.extra;
         j.og = (int8_t)og;
         j.src = (int8_t)sc.src; j.dst = (int8_t)sc.dst; j.res = (int8_t)sc.res; j.act = (int8_t)sc.act;
-        units.push_back({j, og_taps[og] * (3 * pc.kgroups + pc.extra)});   // ~MFMA time in units of 32 cycles
+        j.dtile = (int8_t)(sc.dtile + nt);
+        if (sc.dst < NET_ACT_BUFFERS && j.dtile >= 4) { j.dst = NET_DST_STRIP; j.dtile = (int8_t)(j.dtile - 4); }
+        units.push_back({j, og_taps[og] * (3 * pc.kgroups + pc.extra) + JOB_OVERHEAD});   // ~time in units of 32 cycles
       }
     }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.cost > b.cost; });
+  };
+  auto deal = [](const std::vector<Unit>& units, int (&load)[NET_WAVES_HOST], int* who) {
+    for (int w = 0; w < NET_WAVES_HOST; ++w) load[w] = 0;
+    for (size_t u = 0; u < units.size(); ++u) {
+      int w = 0;
+      for (int i = 1; i < NET_WAVES_HOST; ++i)
+        if (load[i] < load[w]) w = i;
+      load[w] += units[u].cost;
+      if (who) who[u] = w;
+    }
+  };
+  // A one-conv stage cuts its tiles in two when that gives every wave a unit, else in four.  A stage of several convs
+  // (the two heads side by side) tries every cut of its tiles in halves or quarters and keeps the one whose most loaded
+  // matrix pipe (waves w and w + 4 share one SIMD), then whose most loaded wave, has the least work.
+  unsigned best = 2 * tiles.size() >= (size_t)NET_WAVES_HOST ? 0u : (1u << tiles.size()) - 1u;
+  std::vector<Unit> units;
+  if (stage.size() > 1) {
+    long best_key = -1;
+    for (unsigned m = 0; m < (1u << tiles.size()); ++m) {
+      int load[NET_WAVES_HOST];
+      make_units(m, units);
+      deal(units, load, nullptr);
+      int simd = 0, wave = 0;
+      for (int w = 0; w < NET_WAVES_HOST; ++w) wave = std::max(wave, load[w]);
+      for (int w = 0; w < NET_WAVES_HOST / 2; ++w) simd = std::max(simd, load[w] + load[w + NET_WAVES_HOST / 2]);
+      const long key = (long)simd * 65536 + wave;
+      if (best_key < 0 || key < best_key) { best_key = key; best = m; }
+    }
   }
-  std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.cost > b.cost; });
-  int load[NET_WAVES_HOST] = {};
+  make_units(best, units);
+  for (const Unit& u : units) {
+    if (u.job.dst == NET_DST_STRIP && (u.job.dtile != 0 || u.job.act != 1 || u.job.res >= 0)) return false;
+    if (u.job.sslot == NET_SSLOT_SPLIT && u.job.kgroups != 1) return false;
+  }
+  int load[NET_WAVES_HOST];
+  std::vector<int> who(units.size());
+  deal(units, load, who.data());
   int first[NET_WAVES_HOST];
   for (int w = 0; w < NET_WAVES_HOST; ++w) first[w] = pg.n_jobs[w];
-  for (const Unit& u : units) {
-    int w = 0;
-    for (int i = 1; i < NET_WAVES_HOST; ++i)
-      if (load[i] < load[w]) w = i;
+  for (size_t u = 0; u < units.size(); ++u) {
+    const int w = who[u];
     if (pg.n_jobs[w] >= NET_MAX_JOBS) return false;
-    pg.jobs[w][pg.n_jobs[w]++] = u.job;
-    load[w] += u.cost;
+    pg.jobs[w][pg.n_jobs[w]++] = units[u].job;
   }
   for (int w = 0; w < NET_WAVES_HOST; ++w) {
     if (pg.n_jobs[w] == first[w]) {            // nothing to do in this stage: barrier only
@@ -523,12 +569,16 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
   const int ph = trunk_tensors, vh = ph + 2;
   const int vact = net->value_activation == NZ_ACT_RELU ? 1 : 2;
   const int side = cur ^ 1;
-  // two buffers: the policy head runs first (trunk -> side -> logits), then the value head
-  // ping-pongs between the two (the trunk output is dead after its first layer)
-  stage({{ph, cur, side, -1, 1, true}});
-  stage({{ph + 1, side, NET_DST_POLICY, -1, 0, true}});
-  stage({{vh, cur, side, -1, vact, true}});
-  stage({{vh + 1, side, cur, -1, vact, true}});
+  // The two heads side by side, four stages: both first convs read the trunk output, the value head's into `side`'s
+  // first tiles, the policy head's into the tiles after them and past the fourth into the strip (64 channels: 48 + 32
+  // = 3 + 2 tiles); then both second convs (the trunk output is dead: the value head's goes there), then the value
+  // head's last two.  The policy head's second conv reads its K group from where the first wrote it: slots 2 tv0.. of
+  // `side`, or slots 6-7 and the strip.
+  const int tv0 = convs[vh].ntiles, tp0 = convs[ph].ntiles;
+  if (tv0 + tp0 > 5 || (tv0 + tp0 == 5 && tv0 != 3)) return fail(e, NZ_ERR_ARG, "head layout: %d + %d tiles", tv0, tp0);
+  const int p1_sslot = tv0 + tp0 <= 4 ? 2 * tv0 : NET_SSLOT_SPLIT;
+  stage({{vh, cur, side, -1, vact, true, 0, 0}, {ph, cur, side, -1, 1, true, 0, tv0}});
+  stage({{vh + 1, side, cur, -1, vact, true}, {ph + 1, side, NET_DST_POLICY, -1, 0, true, p1_sslot, 0}});
   stage({{vh + 2, cur, side, -1, vact, true}});
   stage({{vh + 3, side, NET_DST_VALUE, -1, 0, true}});                      // per-cell outputs; net_tile takes the mean
   if (!ok) return fail(e, NZ_ERR_ARG, "network too deep for one fused launch (%d iterations)", recurrent_iterations);

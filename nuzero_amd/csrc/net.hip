@@ -28,6 +28,7 @@ __global__ __launch_bounds__(NET_THREADS) void net_kernel(const NetProgram* __re
 
   // K groups may reach past a narrow layer's channels (their weights are zero): no NaN bit patterns in LDS
   for (int idx = threadIdx.x; idx < NET_BUFFERS * ACT_FLOATS; idx += NET_THREADS) lds[idx] = 0.0f;
+  for (int idx = threadIdx.x; idx < STRIP_FLOATS; idx += NET_THREADS) lds[NET_LDS_FLOATS - STRIP_FLOATS + idx] = 0.0f;
   // input planes -> inp[cell][pos][4]
   for (int idx = threadIdx.x; idx < CELLS * POS * 4; idx += NET_THREADS) {
     const int c = idx & 3, pp = (idx >> 2) & 15, cell = idx >> 6;

@@ -47,7 +47,9 @@
 //
 // LDS layout: act[buffer][piece][cell][pos][64 ch] bf16, the 16-byte slot index XOR-ed with
 // (pos >> 1) & 7 so that ds_read_b128 (operands) and ds_write_b64 (epilogue) are
-// bank-conflict free.  Two buffers (ping-pong; residual blocks update in place).
+// bank-conflict free.  Two buffers (ping-pong; residual blocks update in place), and a 16-channel strip
+// strip[piece][cell][pos][16 ch] (16-byte slot index XOR-ed with (pos >> 2) & 1) for the one head tile that finds no
+// room in them: the two heads' first convs run as one stage, and their 48 + 32 output channels exceed one buffer's 64.
 #pragma once
 #include "engine.h"
 
@@ -69,7 +71,9 @@ constexpr int ACT_BYTES = 3 * PIECE_BYTES;
 constexpr int ACT_FLOATS = ACT_BYTES / 4;                   // LDS is declared as float[] by the kernels
 constexpr int INP_FLOATS = CELLS * POS * 4;
 constexpr int VAL_FLOATS = CELLS * POS;                      // the value head's last layer, per cell, before the mean
-constexpr int NET_LDS_FLOATS = NET_BUFFERS * ACT_FLOATS + INP_FLOATS + VAL_FLOATS;
+constexpr int STRIP_PIECE_BYTES = CELLS * POS * 16 * 2;     // one bf16 piece of the strip: a quarter of a buffer's piece
+constexpr int STRIP_FLOATS = 3 * STRIP_PIECE_BYTES / 4;
+constexpr int NET_LDS_FLOATS = NET_BUFFERS * ACT_FLOATS + INP_FLOATS + VAL_FLOATS + STRIP_FLOATS;
 constexpr int TAP_DWORDS = 3 * 64 * 4;                      // one tap of one K group: [piece][lane][8 bf16]
 constexpr int W_RING = 3;                                   // taps in flight: the weight stream runs three taps ahead of the MFMAs
 static_assert(NET_WAVES == NET_WAVES_HOST, "job lists are per wave");
@@ -87,6 +91,10 @@ __host__ __device__ constexpr int og_mask(int og) {
 // byte offset of the 16-byte slot holding channels 8 s .. 8 s + 7 of (cell, pos) inside one piece
 __device__ __forceinline__ int slot_addr(int cell, int pos, int s) {
   return ((cell * POS + pos) << 7) + (((s ^ (pos >> 1)) & 7) << 4);
+}
+// the same inside one piece of the strip (s = 0, 1): every stride is a quarter of the buffer's
+__device__ __forceinline__ int strip_addr(int cell, int pos, int s) {
+  return ((cell * POS + pos) << 5) + (((s ^ (pos >> 2)) & 1) << 4);
 }
 
 template <int I, int TAP>
@@ -196,14 +204,33 @@ __device__ __forceinline__ void load_cell(Pieces (&x)[CELLS], const unsigned cha
   }
 #endif
 }
-// this lane's activation operands of K group kg: channels 32 kg + 8 quad .. + 7 of every used input cell
+// this lane's activation operands of one K group (slot address a0) for every used input cell
 template <int OMASK>
-__device__ __forceinline__ void load_cells(Pieces (&x)[CELLS], const unsigned char* __restrict__ src, int pos, int quad,
-                                           int kg) {
-  const int a0 = slot_addr(0, pos, kg * 4 + quad);
+__device__ __forceinline__ void load_cells(Pieces (&x)[CELLS], const unsigned char* __restrict__ src, int a0) {
   load_cell<OMASK, 0>(x, src, a0); load_cell<OMASK, 1>(x, src, a0); load_cell<OMASK, 2>(x, src, a0);
   load_cell<OMASK, 3>(x, src, a0); load_cell<OMASK, 4>(x, src, a0); load_cell<OMASK, 5>(x, src, a0);
   load_cell<OMASK, 6>(x, src, a0); load_cell<OMASK, 7>(x, src, a0); load_cell<OMASK, 8>(x, src, a0);
+}
+// A K group split over two areas (NET_SSLOT_SPLIT): quads 0-1 read slots 6-7 of `src`, quads 2-3 slots 0-1 of the strip.
+// The strip's strides are the buffer's shifted right by two, so one per-lane base and shift address both: the lanes
+// supply the same channels as from one buffer, and the MFMAs see the same operands.
+template <int OMASK, int I>
+__device__ __forceinline__ void load_cell_split(Pieces (&x)[CELLS], const unsigned char* base, unsigned sh) {
+  if constexpr (input_used<OMASK, I>()) {
+#pragma unroll
+    for (int piece = 0; piece < 3; ++piece)
+      x[I].p[piece] = *reinterpret_cast<const u32x4*>(base + ((unsigned)(piece * STRIP_PIECE_BYTES + I * (POS * 32)) << sh));
+  }
+}
+template <int OMASK>
+__device__ __forceinline__ void load_cells_split(Pieces (&x)[CELLS], const unsigned char* __restrict__ src,
+                                                 const unsigned char* __restrict__ strip, int pos, int quad) {
+  const bool in_src = quad < 2;
+  const unsigned char* base = in_src ? src + slot_addr(0, pos, 6 + quad) : strip + strip_addr(0, pos, quad - 2);
+  const unsigned sh = in_src ? 2u : 0u;
+  load_cell_split<OMASK, 0>(x, base, sh); load_cell_split<OMASK, 1>(x, base, sh); load_cell_split<OMASK, 2>(x, base, sh);
+  load_cell_split<OMASK, 3>(x, base, sh); load_cell_split<OMASK, 4>(x, base, sh); load_cell_split<OMASK, 5>(x, base, sh);
+  load_cell_split<OMASK, 6>(x, base, sh); load_cell_split<OMASK, 7>(x, base, sh); load_cell_split<OMASK, 8>(x, base, sh);
 }
 __device__ __forceinline__ void load_tap(Pieces& t, const float* __restrict__ w, int lane) {
 #ifdef NZ_ABLATE_B   // timing-only build: no global loads of the weight operands (outputs are wrong)
@@ -289,15 +316,18 @@ __device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Pieces (&x)[CELLS], 
 // All K groups of one job as straight-line code (KG = 1 or 2: layers are at most 64 channels wide;
 // a loop would carry the operand registers around its back edge through copies).  On entry the
 // ring holds the first three taps of the job's first K group; on exit those of the next job that reads
-// weights (`w_after`; the stream's start when there is none).
+// weights (`w_after`; the stream's start when there is none).  The K groups start at slot `sslot` of the source rows
+// (NET_SSLOT_SPLIT: one K group from two areas, load_cells_split).
 template <int OMASK, int KG>
 __device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragS& f, const unsigned char* __restrict__ src,
+                                          const unsigned char* __restrict__ strip, int sslot,
                                           const float* __restrict__ w, const float* __restrict__ w_after, int lane) {
   const int pos = lane & 15, quad = lane >> 4;
   Pieces x[CELLS];
-  load_cells<OMASK>(x, src, pos, quad, 0);
+  if (KG == 1 && sslot == NET_SSLOT_SPLIT) load_cells_split<OMASK>(x, src, strip, pos, quad);
+  else load_cells<OMASK>(x, src, slot_addr(0, pos, sslot + quad));
   if constexpr (KG == 2) {
-    const int a1 = slot_addr(0, pos, 4 + quad);
+    const int a1 = slot_addr(0, pos, sslot + 4 + quad);
     kgroup<OMASK, 1>(acc, x, f, src, a1, w, w + NET_KG_DWORDS, lane);
     kgroup<OMASK, 2>(acc, x, f, src, a1, w + NET_KG_DWORDS, w_after, lane);
   } else {
@@ -346,11 +376,13 @@ __device__ __forceinline__ void extra_planes(f32x4 (&acc)[CELLS], const float* _
 // ACT: 0 none, 1 relu, 2 tanh, 3 elu.  The four channels of a lane are half a 16-byte slot: one
 // ds_write_b64 per piece (and one ds_read_b64 per piece for the residual, which the three pieces
 // reproduce exactly).  Output cell o lives o * 2048 bytes after cell 0.
-template <int OMASK, int ACT, bool RES>
+// STRIP: dst is the strip (its only tile; nt is ignored).
+template <int OMASK, int ACT, bool RES, bool STRIP = false>
 __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[CELLS], unsigned char* __restrict__ dst,
                                              const unsigned char* res, int lane, int nt) {
   const int pos = lane & 15, quad = lane >> 4;
-  const int off = slot_addr(0, pos, nt * 2 + (quad >> 1)) + (quad & 1) * 8;
+  constexpr int PB = STRIP ? STRIP_PIECE_BYTES : PIECE_BYTES, CB = STRIP ? POS * 32 : POS * 128;
+  const int off = (STRIP ? strip_addr(0, pos, quad >> 1) : slot_addr(0, pos, nt * 2 + (quad >> 1))) + (quad & 1) * 8;
 #ifdef NZ_ABLATE_EPI   // timing-only build: one store per job instead of the epilogue (outputs are wrong)
   {
     float t = 0.f;
@@ -389,26 +421,29 @@ __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[CELLS], unsigned
     uint32_t a0, a1, a2, b0, b1, b2;
     split_pair(v[0], v[1], a0, a1, a2);
     split_pair(v[2], v[3], b0, b1, b2);
-    *reinterpret_cast<u32x2*>(dst + 0 * PIECE_BYTES + o * (POS * 128) + off) = u32x2{a0, b0};
-    *reinterpret_cast<u32x2*>(dst + 1 * PIECE_BYTES + o * (POS * 128) + off) = u32x2{a1, b1};
-    *reinterpret_cast<u32x2*>(dst + 2 * PIECE_BYTES + o * (POS * 128) + off) = u32x2{a2, b2};
+    *reinterpret_cast<u32x2*>(dst + 0 * PB + o * CB + off) = u32x2{a0, b0};
+    *reinterpret_cast<u32x2*>(dst + 1 * PB + o * CB + off) = u32x2{a1, b1};
+    *reinterpret_cast<u32x2*>(dst + 2 * PB + o * CB + off) = u32x2{a2, b2};
   }
 }
 template <int OMASK>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob& job, unsigned char* __restrict__ lds,
-                                         int lane, int policy_channels, int n_valid, float* logits, float* vcells) {
-  if (job.dst < NET_BUFFERS) {
+                                         unsigned char* __restrict__ strip, int lane, int policy_channels, int n_valid,
+                                         float* logits, float* vcells) {
+  if (job.dst == NET_DST_STRIP) {             // ReLU only: the host compiles nothing else into the strip
+    epilogue_lds<OMASK, 1, false, true>(acc, strip, nullptr, lane, 0);
+  } else if (job.dst < NET_BUFFERS) {
     unsigned char* dst = lds + job.dst * ACT_BYTES;
     if (job.res >= 0) {
-      epilogue_lds<OMASK, 1, true>(acc, dst, lds + job.res * ACT_BYTES, lane, job.nt);
+      epilogue_lds<OMASK, 1, true>(acc, dst, lds + job.res * ACT_BYTES, lane, job.dtile);
     } else if (job.act == 1) {
-      epilogue_lds<OMASK, 1, false>(acc, dst, nullptr, lane, job.nt);
+      epilogue_lds<OMASK, 1, false>(acc, dst, nullptr, lane, job.dtile);
     } else if (job.act == 2) {
-      epilogue_lds<OMASK, 2, false>(acc, dst, nullptr, lane, job.nt);
+      epilogue_lds<OMASK, 2, false>(acc, dst, nullptr, lane, job.dtile);
     } else if (job.act == 3) {
-      epilogue_lds<OMASK, 3, false>(acc, dst, nullptr, lane, job.nt);
+      epilogue_lds<OMASK, 3, false>(acc, dst, nullptr, lane, job.dtile);
     } else {
-      epilogue_lds<OMASK, 0, false>(acc, dst, nullptr, lane, job.nt);
+      epilogue_lds<OMASK, 0, false>(acc, dst, nullptr, lane, job.dtile);
     }
   } else if (job.dst == NET_DST_POLICY) {     // policy logits [pos][P][9]
     // (addresses re-derived from an opaque copy of the lane id: hoisted out of the job loop they would sit in
@@ -443,6 +478,7 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob
 template <int OMASK, typename Stamp, typename Fetch>
 __device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float* __restrict__ W,
                                         const float* w_after, unsigned char* __restrict__ lds,
+                                        unsigned char* __restrict__ strip,
                                         const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
                                         float* logits, float* value, Stamp&& stamp, Fetch&& fetch_next) {
   // per-lane LDS addresses are derived inside the job from an opaque copy of the lane id: hoisted out of the job loop
@@ -451,19 +487,20 @@ __device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float
   f32x4 acc[CELLS];
 #pragma unroll
   for (int o = 0; o < CELLS; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (job.kgroups == 2) job_kloop<OMASK, 2>(acc, f, lds + job.src * ACT_BYTES, W + job.w_off, w_after, lane);
-  else if (job.kgroups == 1) job_kloop<OMASK, 1>(acc, f, lds + job.src * ACT_BYTES, W + job.w_off, w_after, lane);
+  if (job.kgroups == 2) job_kloop<OMASK, 2>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane);
+  else if (job.kgroups == 1) job_kloop<OMASK, 1>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane);
   stamp(0);
   if (job.extra) extra_planes<OMASK>(acc, W + job.wx_off, inp, lane);
   stamp(1);
   fetch_next();          // the next job's descriptor: in flight under the epilogue, in no register during the K loop
-  epilogue<OMASK>(acc, job, lds, lane, policy_channels, n_valid, logits, value);   // `value`: the per-cell staging area
+  epilogue<OMASK>(acc, job, lds, strip, lane, policy_channels, n_valid, logits, value);   // `value`: the per-cell staging area
   stamp(2);
 }
 
 // Run the compiled network on the 16 positions whose input planes are in `inp`
 // ([cell][pos][4 planes]); `lds_f` holds the activation buffers (NET_BUFFERS * ACT_FLOATS floats,
-// no NaN bit patterns: the callers zero it once), then `inp`'s INP_FLOATS, then VAL_FLOATS of staging.  Every thread of the 256-thread workgroup must
+// no NaN bit patterns: the callers zero it once), then `inp`'s INP_FLOATS, then VAL_FLOATS of staging, then the
+// strip's STRIP_FLOATS (zeroed once as well).  Every thread of the 256-thread workgroup must
 // call it; it ends with a workgroup barrier.
 // Outputs: logits [pos][policy_channels][9] and value [pos] for pos < n_valid
 // (any address space).
@@ -476,6 +513,7 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
                                          unsigned long long* stamps = nullptr) {
   unsigned char* __restrict__ lds = reinterpret_cast<unsigned char*>(lds_f);
   float* const vcells = lds_f + NET_BUFFERS * ACT_FLOATS + INP_FLOATS;
+  unsigned char* const strip = reinterpret_cast<unsigned char*>(vcells + VAL_FLOATS);
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));                     // per-lane addresses are derived here, not hoisted out of the caller's loop
   const int lane = tid & 63;
@@ -538,12 +576,12 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       switch (job.og) {
         // (group 0, all nine cells in one job, is never scheduled: layers are at most four tiles wide and eight waves
         // want a unit each -- engine.hip add_stage)
-        case 1: run_job<og_mask(1)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
-        case 2: run_job<og_mask(2)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
-        case 3: run_job<og_mask(3)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
-        case 4: run_job<og_mask(4)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
-        case 5: run_job<og_mask(5)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
-        default: run_job<og_mask(6)>(job, f, W, w_after, lds, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        case 1: run_job<og_mask(1)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        case 2: run_job<og_mask(2)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        case 3: run_job<og_mask(3)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        case 4: run_job<og_mask(4)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        case 5: run_job<og_mask(5)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
+        default: run_job<og_mask(6)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
       }
     }
     stamp(2);

@@ -154,11 +154,12 @@ template <bool STAMPS>
 __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
   __shared__ __attribute__((aligned(16))) float lds[NET_LDS_FLOATS + POS * TTT_ACTIONS + POS];
   float* const inp = lds + NET_BUFFERS * ACT_FLOATS;
-  float* const out_logits = inp + INP_FLOATS + VAL_FLOATS;   // [16][9], after net_tile's own areas
+  float* const out_logits = lds + NET_LDS_FLOATS;             // [16][9], after net_tile's own areas
   float* const out_value = out_logits + POS * TTT_ACTIONS;
 
   // K groups may reach past a narrow layer's channels (their weights are zero): no NaN bit patterns in LDS
   for (int idx = threadIdx.x; idx < NET_BUFFERS * ACT_FLOATS; idx += NET_THREADS) lds[idx] = 0.0f;
+  for (int idx = threadIdx.x; idx < STRIP_FLOATS; idx += NET_THREADS) lds[NET_LDS_FLOATS - STRIP_FLOATS + idx] = 0.0f;
 
   // The network phase needs the whole register file (256 + 256 per lane); the tree phase's state waits in LDS
   // meanwhile -- one word per game for what the 16 lanes of a row share, one per lane for the rest -- and lives in
