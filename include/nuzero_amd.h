@@ -427,7 +427,9 @@ nz_status nz_scs_search_last_actions(nz_scs_search* h, int32_t* actions_dev, voi
 /* The reference's optional inference cache (Explorer.py:146-155; Utils/Caches/KeylessCache.py:24-160, DictCache.py:4-85;
  * handed to Gamer.play_game by AlphaZero.py:560-577) for nz_scs_search_play: one keyless hash table in HBM shared by the
  * games of the engine -- a leaf whose state was evaluated before takes (probs, value) from the table instead of the
- * network.  Results-neutral: a position's evaluation does not depend on the batch it was computed in.
+ * network.  Results-neutral: a position's evaluation does not depend on the batch it was computed in.  The key is the
+ * state and, with per-game maps (nz_scs_search_set_games), a digest of the game's map: games on different maps never
+ * share an entry, games on equal maps do (the reference hashes the state tensor, which holds the map's planes).
  *   max_entries > 0: (re)allocate an empty table of the largest power of two <= max_entries (KeylessCache.py:27-38);
  *   0: no cache; < 0: empty the table (a new self-play round: the reference builds new Gamers, hence new caches).
  * stats out4: hits, misses, entries in use, table size. */
@@ -443,7 +445,7 @@ nz_status nz_scs_search_waves(const nz_scs_search* h, int64_t* waves);
  * search of a move -- descent, rules, the network for its own leaf, expansion, backup (Explorer.run_mcts,
  * Search/Explorer.py:40-67, with one simulation in flight per tree, :49-61) -- in ONE launch per move, no game waiting
  * for another.  Available for ConvNet / ResNet board nets on boards of up to 32 cells whose layers are at most 64
- * channels wide, with the inference cache off; other configurations keep the wave-by-wave route.
+ * channels wide, with or without the inference cache; other configurations keep the wave-by-wave route.
  * enable: 1 require it (a play fails where it is not available), 0 never, -1 the default (use it where available).
  * *used (may be NULL): whether the last play ran on it. */
 nz_status nz_scs_search_persistent(nz_scs_search* h, int32_t enable, int32_t* used);

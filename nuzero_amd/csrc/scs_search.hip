@@ -63,6 +63,7 @@ struct SearchParams {
   const double* sqrt_tab;
   const ScsRules* rules;   // the game description; with per-game maps (nz_scs_search_set_games) one row per game of the round
   const int32_t* rules_row;  // [G] the row of `rules` each slot's game reads, or nullptr: all read row 0
+  const uint64_t* rules_key; // [rows][2] digest of each row's map, mixed into the cache key (nullptr: one map, not mixed in)
   ScsState* real;          // [G]
   ScsState* scratch;       // [G]
   SNode* nodes;            // [G][2][half_cap]: two halves per game, the live tree is in half `half[g]`
@@ -395,12 +396,14 @@ __global__ void begin_move_kernel(SearchParams p, const double* __restrict__ noi
 // ---- inference cache ------------------------------------------------------------------------------------------
 // The reference's optional cache (Explorer.py:146-155; Utils/Caches/KeylessCache.py:24-160: hash of the state tensor,
 // index bits select the slot, the remaining bits are stored as the entry's id; no keys kept) as one device table
-// shared by all games of the engine.  Key: a 128-bit hash of the game STATE the tensor is generated from (equal states
-// give equal tensors, so a hit returns what the network would compute; the reference's metrohash is a third-party
-// package that is not available here, and which hash is used only matters for which entries collide).  The table
+// shared by all games of the engine.  Key: a 128-bit hash of what the tensor is generated from -- the game STATE and,
+// with per-game maps, the digest of the game's map (terrain and victory points are image planes that ScsState does not
+// hold; equal states on equal maps give equal tensors, so a hit returns what the network would compute, also across
+// games whose maps are equal; the reference's metrohash is a third-party package that is not available here, and which
+// hash is used only matters for which entries collide).  With one map for all games the key is the state's hash.  The table
 // is only READ inside wave_kernel and only WRITTEN by cache_put_kernel between two wave kernels, so no entry is
 // ever seen half-written.
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {          // murmur3 finaliser
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // murmur3 finaliser
   x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
   return x;
 }
@@ -420,6 +423,15 @@ __device__ __forceinline__ void state_hash_wave(const ScsState& st, int lane, ui
   hi = mix64(a ^ (b >> 7));
   lo = mix64(b ^ (a << 9));
   if (hi == 0 && lo == 0) lo = 1;                                 // (0, 0) marks an empty entry
+}
+// the key of game slot g's leaf with state hash (hi, lo): per-game maps mix in the digest of the slot's map row
+__device__ __forceinline__ void cache_key_of(const SearchParams& p, int g, uint64_t& hi, uint64_t& lo) {
+  if (!p.rules_key) return;                                       // one map: the state's hash as it is
+  const uint64_t* const m = p.rules_key + 2 * (size_t)p.rules_row[g];
+  const uint64_t a = hi ^ m[0], b = lo ^ m[1];
+  hi = mix64(a ^ (b >> 7));
+  lo = mix64(b ^ (a << 9));
+  if (hi == 0 && lo == 0) lo = 1;
 }
 __global__ void cache_count_kernel(const uint64_t* __restrict__ c_id, int64_t entries, int64_t* __restrict__ out) {
   long long n = 0;
@@ -693,6 +705,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
     size_t entry = 0;
     if (p.c_bits > 0) {
       state_hash_wave(sc, lane, key_hi, key_lo);
+      cache_key_of(p, g, key_hi, key_lo);
       entry = (size_t)(key_lo & ((1ull << p.c_bits) - 1));
       hit = p.c_id[2 * entry] == key_hi && p.c_id[2 * entry + 1] == key_lo;      // uniform: every lane reads the same words
     }
@@ -1532,6 +1545,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
       if (p.c_bits > 0) {
         state_hash_wave(sc, lane, key_hi, key_lo);
         key_hi = uniform64(key_hi); key_lo = uniform64(key_lo);         // (the same on every lane: scalar registers)
+        cache_key_of(p, g, key_hi, key_lo);
         entry = (size_t)(key_lo & ((1ull << p.c_bits) - 1));
         unsigned long long* const id = reinterpret_cast<unsigned long long*>(p.c_id + 2 * entry);
         const unsigned long long id0 = __hip_atomic_load(id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2112,6 +2126,7 @@ struct nz_scs_search {
   ScsRules* base_rules_dev = nullptr;         // the description of nz_scs_search_create (one row)
   ScsRules* game_rules_dev = nullptr;         // [n_game_rows]
   int32_t* rules_row_dev = nullptr;           // [n_games]
+  uint64_t* rules_key_dev = nullptr;          // [n_game_rows][2] map digests (the inference cache's key)
   int64_t n_game_rows = 0;
   std::vector<nz_rng*> game_streams;          // [n_game_rows] or empty: streams from the seeds
 };
@@ -2280,6 +2295,7 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   h->counters_base = p.leaf_count;
   p.rules = rules;
   p.rules_row = nullptr;
+  p.rules_key = nullptr;
   h->base_rules_dev = rules;
   p.bias_tab = bias;
   p.sqrt_tab = sq;
@@ -2310,6 +2326,7 @@ void nz_scs_search_destroy(nz_scs_search* h) {
     (void)hipFree(h->pq.rec_probs); (void)hipFree(h->pq.rec_value);
   }
   if (h->game_rules_dev) (void)hipFree(h->game_rules_dev);
+  if (h->rules_key_dev) (void)hipFree(h->rules_key_dev);
   if (h->rules_row_dev) (void)hipFree(h->rules_row_dev);
   for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
   delete h;
@@ -2838,7 +2855,8 @@ nz_status nz_scs_search_export_round(nz_scs_search* h, int32_t* actions, int32_t
 
 // The reference's inference cache for the library's move loop (cache_choice "keyless" / "dict" of Gamer,
 // Training/Gamer.py:20,53-55; KeylessCache.py:27-38: the table size is the largest power of two <= max_size).
-// max_entries > 0: (re)allocate an empty table; 0: switch the cache off; < 0: empty the table, keep it.
+// max_entries > 0: (re)allocate an empty table; 0: switch the cache off; < 0: empty the table, keep it.  Per-game maps
+// (nz_scs_search_set_games) are part of the key: a leaf's key mixes its state's hash with its map row's digest.
 nz_status nz_scs_search_cache(nz_scs_search* h, int64_t max_entries) {
   if (!h) return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
@@ -2907,6 +2925,32 @@ nz_status nz_scs_search_persistent(nz_scs_search* h, int32_t enable, int32_t* us
   return NZ_OK;
 }
 
+// The 128-bit digest of a map row, the part of the inference cache's key that ScsState does not hold: the per-game
+// fields one word at a time (terrain as the image's float32 triples and the rules' float64 / integer copies, victory
+// points), never the struct's bytes -- padding and entries past `tiles` / n_vp are not the map's.  Equal maps give
+// equal digests, so games on equal maps still share entries (as the reference's cache, which hashes the tensor).
+static void map_digest(const ScsRules& r, uint64_t out[2]) {
+  uint64_t a = 0, b = 0;
+  auto put = [&](uint64_t w) {          // chained: the order of the words is part of the digest
+    a = mix64(a ^ mix64(w ^ 0x9e3779b97f4a7c15ull));
+    b = mix64(b + mix64(w * 0xd6e8feb86659fd93ull + 0x2545f4914f6cdd1dull));
+  };
+  auto bits32 = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); return (uint64_t)u; };
+  auto bits64 = [](double x) { uint64_t u; std::memcpy(&u, &x, 8); return u; };
+  for (int t = 0; t < r.tiles; ++t) {
+    for (int k = 0; k < 3; ++k) put(bits32(r.terrain_f[t][k]));
+    put(bits64(r.attack_mod[t]));
+    put(bits64(r.defense_mod[t]));
+    put((uint64_t)(uint32_t)r.cost[t]);
+  }
+  for (int q = 0; q < 2; ++q) {
+    put((uint64_t)(uint32_t)r.n_vp[q]);
+    for (int i = 0; i < r.n_vp[q]; ++i) put((uint64_t)(uint8_t)r.vp[q][i]);
+  }
+  out[0] = mix64(a ^ (b >> 7));
+  out[1] = mix64(b ^ (a << 9));
+}
+
 // Every game of the next plays on its OWN map, as the reference builds a new game object -- and with a "Randomized"
 // config a new map -- per game (Training/Gamer.py:52, SCS_Game.py:1678-1738).  Host arrays for n games (n >= the games of
 // a round): terrain float32 [n][tiles][3] (attack modifier, defense modifier, cost), vp int32 [n][n_vp0 + n_vp1][2] (row,
@@ -2922,9 +2966,11 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
   for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
   h->game_streams.clear();
   if (h->game_rules_dev) { (void)hipFree(h->game_rules_dev); h->game_rules_dev = nullptr; }
+  if (h->rules_key_dev) { (void)hipFree(h->rules_key_dev); h->rules_key_dev = nullptr; }
   h->n_game_rows = 0;
   h->p.rules = h->base_rules_dev;
   h->p.rules_row = nullptr;
+  h->p.rules_key = nullptr;
   if (n == 0) return nz_scs_search_reset(h, nullptr);
   if (n < h->n_games) return sfail(h, NZ_ERR_ARG, "%lld games set, the engine plays %d at a time", (long long)n, h->n_games);
   const ScsRules& b = h->host_rules;
@@ -2935,9 +2981,13 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
     for (int t = 0; t < T; ++t)
       if (rows[(size_t)i].cost[t] < 1) return sfail(h, NZ_ERR_ARG, "game %lld: a terrain with movement cost < 1", (long long)i);
   }
-  if (hipMalloc((void**)&h->game_rules_dev, rows.size() * sizeof(ScsRules)) != hipSuccess)
+  std::vector<uint64_t> keys((size_t)n * 2);
+  for (int64_t i = 0; i < n; ++i) map_digest(rows[(size_t)i], &keys[(size_t)i * 2]);
+  if (hipMalloc((void**)&h->game_rules_dev, rows.size() * sizeof(ScsRules)) != hipSuccess ||
+      hipMalloc((void**)&h->rules_key_dev, keys.size() * sizeof(uint64_t)) != hipSuccess)
     return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
   S_HIP(h, hipMemcpy(h->game_rules_dev, rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice));
+  S_HIP(h, hipMemcpy(h->rules_key_dev, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (!h->rules_row_dev && hipMalloc((void**)&h->rules_row_dev, (size_t)h->n_games * sizeof(int32_t)) != hipSuccess)
     return sfail(h, NZ_ERR_HIP, "device allocation failed");
   std::vector<int32_t> ident(h->n_games);
@@ -2952,6 +3002,7 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
   h->n_game_rows = n;
   h->p.rules = h->game_rules_dev;
   h->p.rules_row = h->rules_row_dev;
+  h->p.rules_key = h->rules_key_dev;
   return nz_scs_search_reset(h, nullptr);      // the slots' games start on their own maps (row g for slot g)
 }
 

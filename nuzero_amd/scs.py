@@ -412,8 +412,8 @@ class ScsSelfPlay:
 
     def persistent(self, enable=-1):
         """The library's move loop on the persistent kernel (one wavefront per game, a move's whole search in one
-        launch): 1 require it, 0 never, -1 the default (where the network has a per-wavefront form and the inference
-        cache is off).  Returns whether the LAST play ran on it."""
+        launch): 1 require it, 0 never, -1 the default (where the network has a per-wavefront form; the inference cache
+        may be on).  Returns whether the LAST play ran on it."""
         used = ctypes.c_int32(0)
         self._check(lib.nz_scs_search_persistent(self._h, int(enable), byref(used)))
         return bool(used.value)
@@ -498,8 +498,9 @@ class ScsSelfPlay:
 
     def cache(self, max_entries):
         """The reference's inference cache for play_native (KeylessCache(max_size), Utils/Caches/KeylessCache.py:24-160):
-        a device hash table of the largest power of two <= max_entries, shared by the engine's games; 0 switches it
-        off.  Results do not change (tests/test_gpu_scs.py)."""
+        a device hash table of the largest power of two <= max_entries, shared by the engine's games (keyed on the
+        state and, with per-game maps, the game's map); 0 switches it off.  Results do not change (tests/test_gpu_scs.py,
+        tests/test_gpu_scs_cache_maps.py)."""
         self._check(lib.nz_scs_search_cache(self._h, int(max_entries)))
 
     def cache_clear(self):

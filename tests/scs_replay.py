@@ -6,6 +6,11 @@ game g come in exactly that order).  `replay_game` plays the game again with ora
 evaluate() the recorded (probs, value) after checking that the oracle's leaf image is the recorded one, and returns the
 per-move trace: every root statistic must then equal the device's bit for bit -- the SCS twin of
 tests/test_gpu_parity.py::test_fused_search_equals_oracle_on_same_evaluations.
+
+A job may end with an options dict: {"per_game": True} replays a game on its own "Randomized" map (seeded as the
+engine's set_games: RandomState(seed) draws the map, the search goes on with the same stream), and
+{"oracle_net": (weights, arch, depth)} also holds every consumed evaluation -- cache hits included -- to the oracle
+network on the game's own leaf image (1e-5), so that what a cache handed back is checked, not only how the search used it.
 """
 import hashlib
 import os
@@ -70,14 +75,28 @@ class LeafRecorder:
                 np.stack([r[1] for r in rec]), np.array([r[2] for r in rec], np.float32))
 
 
+ORACLE_NET_TOL = 1e-5
+
+
 def replay_game(args):
-    """(config path, search config, seed, training, digests [n,8], probs [n,A], values [n], max_moves) -> trace dict.
-    Top-level so it can run in a worker process (CPU only: nothing here touches the GPU)."""
-    config_path, search, seed, training, digests, probs, values, max_moves = args
+    """(config path, search config, seed, training, digests [n,8], probs [n,A], values [n], max_moves[, options]) ->
+    trace dict.  options (optional): "per_game" (bool), "oracle_net" ((weights, arch, depth) of a feed-forward board
+    net: FeedForwardRef).  Top-level so it can run in a worker process (CPU only: nothing here touches the GPU)."""
+    config_path, search, seed, training, digests, probs, values, max_moves = args[:8]
+    options = args[8] if len(args) > 8 and args[8] else {}
     from oracle import search as osearch
     from oracle.scs import ScsConfig, ScsGame
-    cfg = ScsConfig(config_path)
+    rs = np.random.RandomState(int(seed))
+    # per-game maps: ONE stream, the game's map drawn first and its search going on with it
+    cfg = ScsConfig(config_path, map_seed=rs) if options.get("per_game") else ScsConfig(config_path)
     game = ScsGame(cfg)
+    ref = None
+    if options.get("oracle_net") is not None:
+        from scipy.special import softmax
+        from oracle.net import FeedForwardRef
+        weights, arch, depth = options["oracle_net"]
+        ref = FeedForwardRef(weights, arch, depth)
+    worst = [0.0, 0.0]
     cursor = [0]
 
     def ev(g):
@@ -90,10 +109,18 @@ def replay_game(args):
             same = image_digest(g.state_image()[0]) == digests[i].tobytes()
         if not same:
             raise AssertionError(f"leaf {i}: the oracle's leaf image is not the one the device evaluated")
+        if ref is not None:
+            logits, v = ref.inference(g.state_image(), None)
+            dp = float(np.max(np.abs(softmax(logits.reshape(-1)) - probs[i])))
+            dv = abs(float(v.reshape(-1)[0]) - float(values[i]))
+            worst[0], worst[1] = max(worst[0], dp), max(worst[1], dv)
+            if not (dp < ORACLE_NET_TOL and dv < ORACLE_NET_TOL):
+                raise AssertionError(f"leaf {i}: the evaluation the device consumed is not the oracle network's on this "
+                                     f"game's image (probabilities off by {dp:.3g}, value by {dv:.3g})")
         cursor[0] = i + 1
         return probs[i], values[i]
 
-    explorer = osearch.Explorer(search, training, np.random.RandomState(int(seed)))
+    explorer = osearch.Explorer(search, training, rs)
     root = osearch.Node(0)
     trace = []
     while not game.is_terminal() and (not max_moves or len(trace) < max_moves):
@@ -108,7 +135,8 @@ def replay_game(args):
         root = chosen
     return {"trace": trace, "length": game.length, "terminal": bool(game.is_terminal()),
             "terminal_value": game.terminal_value if game.is_terminal() else None,
-            "evaluations_used": cursor[0], "evaluations_recorded": len(values)}
+            "evaluations_used": cursor[0], "evaluations_recorded": len(values),
+            "oracle_net_worst": tuple(worst) if ref is not None else None}
 
 
 def replay_games(jobs, workers=None):

@@ -190,4 +190,16 @@ def test_gamer_gives_every_game_its_own_map_and_fills_the_buffers():
     for x, y in zip(a, b):
         assert torch.equal(x[0], y[0]) and x[1][0] == y[1][0] and x[2] == y[2]
         assert x[1][1] == np.asarray(y[1][1], np.float32).tolist()       # (the device buffer keeps policies as float32)
-    dev.close(); g.engine.close(); g2.engine.close()
+    # the same round with the cache off: the same records and statistics (the table is shared by games on different
+    # maps, whose states can be equal -- a cache hit must never hand a game another map's evaluation)
+    g3 = Gamer(ReplayBuffer(100, 16), nm, SCS_Game, [PATH], 3, a1_search(16), 1, "disabled", size_estimate=4096,
+               num_games=N, concurrent_games=4, base_seed=base)
+    records3, stats3 = g3.play_games()
+    assert g3.engine.persistent() and stats3 == stats and len(records3) == N
+    for i, (rec, rec3) in enumerate(zip(records, records3)):
+        assert rec3.length == rec.length and rec3.terminal_value == rec.terminal_value, i
+        assert rec3.action_history == rec.action_history, i
+        for m in range(rec.length):
+            assert torch.equal(rec3.get_state_from_history(m), rec.get_state_from_history(m)), (i, m)
+            assert rec3.make_target(m) == rec.make_target(m), (i, m)
+    dev.close(); g.engine.close(); g2.engine.close(); g3.engine.close()

@@ -190,3 +190,106 @@ def test_search_on_per_game_maps_against_reference():
                 for key in ("action", "root_visits", "root_value_sum", "child_actions", "child_visits", "child_priors",
                             "child_value_sums"):
                     assert mine[key] == theirs[key], (name, key)
+
+
+def _recorded_play(path, seed, config, training, evaluate):
+    """Oracle self-play of the game with `seed` on its own map, recording every evaluation as the persistent kernel's
+    test hook does: (128-bit digest of the leaf image, probabilities, value), in the order the search consumes them."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from scs_replay import image_mix_digest
+    from oracle import search as osearch
+    rs = np.random.RandomState(seed)
+    cfg = ScsConfig(path, map_seed=rs)
+    rec = []
+
+    def ev(game):
+        img = game.state_image()[0]
+        p, v = evaluate(game, cfg)
+        rec.append((image_mix_digest(img), np.asarray(p, np.float32), np.float32(v)))
+        return rec[-1][1], rec[-1][2]
+
+    game = ScsGame(cfg)
+    osearch.play_game(game, ev, config, rs, training=training)
+    return (np.stack([r[0] for r in rec]), np.stack([r[1] for r in rec]), np.array([r[2] for r in rec], np.float32)), game
+
+
+def test_recorded_leaf_replay_on_per_game_maps():
+    """tests/scs_replay.py in per-game mode (how the GPU tests replay the device's games on per-game maps): the
+    evaluations of the scs_search_pergame_kat.json.gz games, recorded from the oracle's own play, replay to the genuine
+    reference's traces move for move -- and only on the game's own map (the map of another seed fails at the first
+    leaf image)."""
+    import gzip
+    import json
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from scs_eval import evaluate_image
+    from scs_replay import replay_game
+    with gzip.open(os.path.join(GOLDEN, "scs_search_pergame_kat.json.gz"), "rt") as f:
+        kat = json.load(f)
+    path = os.path.join(GOLDEN, "scs_configs", "randomized_5x5.yml")
+    replayed = 0
+    for name, case in kat.items():
+        for ref in case["games"]:
+            rec, _ = _recorded_play(path, ref["seed"], case["config"], case["training"],
+                                    lambda game, cfg: evaluate_image(game.state_image()[0], cfg.num_actions))
+            assert len(rec[2]) == ref["evaluations"], name
+            job = (path, case["config"], ref["seed"], case["training"]) + rec + (None,)
+            out = replay_game(job + ({"per_game": True},))
+            assert out["evaluations_used"] == out["evaluations_recorded"] == ref["evaluations"], name
+            assert out["length"] == ref["length"] and out["terminal"] and out["terminal_value"] == ref["terminal_value"]
+            assert len(out["trace"]) == len(ref["moves"])
+            for m, (mine, theirs) in enumerate(zip(out["trace"], ref["moves"])):
+                for key in theirs:
+                    assert mine[key] == theirs[key], (name, ref["seed"], m, key)
+            replayed += 1
+            with pytest.raises(AssertionError, match="leaf 0: the oracle's leaf image"):
+                replay_game((path, case["config"], ref["seed"] + 1000) + job[3:] + ({"per_game": True},))
+    assert replayed == sum(len(c["games"]) for c in kat.values())
+
+
+def test_recorded_leaf_replay_holds_every_evaluation_to_the_oracle_network():
+    """scs_replay's oracle-network option: evaluations the oracle network made on each leaf's own image replay (the
+    largest difference is reported), and a game that consumed one evaluation of another position -- what a cache hit
+    under a wrong key hands back -- fails at exactly that leaf although every image digest is right."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import torch
+    from scs_replay import replay_game
+    from nuzero_amd.weights import synthetic_weights, convnet_param_shapes
+    from oracle.net import FeedForwardRef
+    path = os.path.join(GOLDEN, "scs_configs", "randomized_5x5.yml")
+    probe = ScsConfig(path, map_seed=0)
+    w = synthetic_weights(3, convnet_param_shapes(probe.channels, probe.planes, 3, 8, 1), 2.0)
+    ref = FeedForwardRef(w, "convnet", 1)
+
+    def net(game, cfg):
+        p, v = ref.inference(game.state_image(), None)
+        return torch.softmax(torch.from_numpy(p.reshape(-1)), 0).numpy(), v.reshape(-1)[0]
+
+    search = {"Simulation": {"mcts_simulations": 8, "keep_subtree": True}, "UCT": {"pb_c_base": 10000, "pb_c_init": 1.15},
+              "Exploration": {"number_of_softmax_moves": 0, "epsilon_softmax_exploration": 0.04,
+                              "epsilon_random_exploration": 0.001, "value_factor": 1,
+                              "root_exploration_distribution": "gamma", "root_exploration_fraction": 0.2,
+                              "root_dist_alpha": 0.15, "root_dist_beta": 1}}
+    seed = 61
+    (dig, probs, values), game = _recorded_play(path, seed, search, True, net)
+    opts = {"per_game": True, "oracle_net": (w, "convnet", 1)}
+    out = replay_game((path, search, seed, True, dig, probs, values, None, opts))
+    assert out["evaluations_used"] == len(values) > 100 and out["length"] == game.length
+    assert max(out["oracle_net_worst"]) < 1e-5
+    # the same game played with ONE wrong evaluation, leaf k getting leaf k - 1's (a cache hit under a key that missed
+    # what tells the two apart): its records are self-consistent, so the digest check alone replays them to the end
+    k = next(i for i in range(40, len(values)) if np.max(np.abs(probs[i] - probs[i - 1])) > 1e-3)
+    calls = [0]
+
+    def wrong_once(game, cfg):
+        calls[0] += 1
+        return (probs[k - 1], values[k - 1]) if calls[0] == k + 1 else net(game, cfg)
+
+    bad, _ = _recorded_play(path, seed, search, True, wrong_once)
+    assert np.array_equal(bad[0][:k + 1], dig[:k + 1])
+    out = replay_game((path, search, seed, True) + bad + (None, {"per_game": True}))
+    assert out["evaluations_used"] == len(bad[2])
+    with pytest.raises(AssertionError, match=f"leaf {k}: the evaluation the device consumed"):
+        replay_game((path, search, seed, True) + bad + (None, opts))
