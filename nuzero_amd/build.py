@@ -7,6 +7,7 @@ so this also runs in the CPU-only build container.  tree.hip and the host
 random streams are compiled with -ffp-contract=off: their double-precision
 arithmetic must round exactly like the reference's (one operation at a time).
 """
+import glob
 import os
 import subprocess
 import sys
@@ -28,7 +29,6 @@ UNITS = [
     ("loss.hip", []),
     ("rng_host.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["engine.h", "tree_dev.hpp", "net_dev.hpp", "scs_dev.hpp", os.path.join("..", "..", "include", "nuzero_amd.h")]
 
 
 def _stale(target, sources):
@@ -39,7 +39,9 @@ def _stale(target, sources):
 
 
 def build(force=False, verbose=True):
-    headers = [os.path.join(CSRC, h) for h in HEADERS]
+    # every header a unit may include: editing any of them rebuilds every unit
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp"))
+    headers.append(os.path.join(CSRC, "..", "..", "include", "nuzero_amd.h"))
     objs = []
     for src, extra in UNITS:
         s = os.path.join(CSRC, src)

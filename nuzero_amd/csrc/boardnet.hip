@@ -127,21 +127,6 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs p) {
 
   f32x4 a[DEPTH][MT], b[DEPTH][NT];
   auto issue = [&](int d) {
-#ifdef NZ_ABLATE_CONV_NOLOAD       // timing experiment: no memory operands at all
-    {
-      const float f = (float)(kg + tap);
-#pragma unroll
-      for (int m = 0; m < MT; ++m) a[d][m] = f32x4{f, f, f, f};
-#pragma unroll
-      for (int n = 0; n < NT; ++n) b[d][n] = f32x4{f, f, f, f};
-      if (++kg == kgt) {
-        kg = 0;
-        if (taps_left) { tap = __ffs(taps_left) - 1; taps_left &= taps_left - 1; }
-        else tap = ntaps;
-      }
-      return;
-    }
-#endif
     const int shift = (tap_dy(tap) * p.wd + tap_dx(tap)) * 16;
     const bool second = kg >= kg0;
     const float* src = second ? p.src1 : p.src0;
@@ -149,18 +134,10 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs p) {
     const int ch = (second ? kg - kg0 : kg) * 16 + q4;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-#ifdef NZ_ABLATE_CONV_A            // timing experiment: every activation load hits the same rows
-      if (live[m] && tap < ntaps) a[d][m] = *reinterpret_cast<const f32x4*>(src + (size_t)row[m] * cs + q4);
-#else
       if (live[m] && tap < ntaps) a[d][m] = *reinterpret_cast<const f32x4*>(src + (size_t)(row[m] + shift) * cs + ch);
-#endif
       else a[d][m] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-#ifdef NZ_ABLATE_CONV_B            // timing experiment: every weight load hits the same line
-    const float* wk = wbase;
-#else
     const float* wk = wbase + ((size_t)tap * kgt + kg) * 256;
-#endif
 #pragma unroll
     for (int n = 0; n < NT; ++n) b[d][n] = *reinterpret_cast<const f32x4*>(wk + n * tile_stride);
     if (++kg == kgt) {
@@ -215,27 +192,8 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs p) {
 // split on the host, 24 KB) in LDS, double buffered, one barrier per step; each wavefront owns 128
 // positions x 64 channels = 32 accumulator tiles and issues 192 MFMAs per step from 36 LDS fragment reads.
 // Weights are the MFMA's A operand, so a lane ends up with four consecutive channels of one position:
-// the epilogue is one 16-byte store (and residual load) per accumulator tile.
-#ifndef NZ_WIDE_INTERLEAVE
-#define NZ_WIDE_INTERLEAVE 0      // 1: the four column tiles' MFMA chains term by term (measured: no difference)
-#endif
-#ifdef NZ_ABLATE_WIDE_MFMA        // timing experiment: no matrix instructions (results wrong)
-#define WIDE_MFMA(w, x, c) f32x4{(c)[0] + __builtin_bit_cast(float, (w)[0] & (x)[0]), (c)[1], (c)[2], (c)[3]}
-#else
-#define WIDE_MFMA(w, x, c) wide_mfma(w, x, c)
-#endif
-#ifndef NZ_WIDE_OVERLAP
-#define NZ_WIDE_OVERLAP 2         // 2: the next step's staging in the gaps of this step's MFMAs, operands fetched two steps ahead
-#endif
-#ifndef NZ_WIDE_XCD
-#define NZ_WIDE_XCD 1             // workgroups that share an XCD take consecutive tiles
-#endif
-#ifndef NZ_WIDE_KQ_OUTER
-#define NZ_WIDE_KQ_OUTER 1        // K loop: channel groups outside, taps inside
-#endif
-#if NZ_WIDE_OVERLAP == 2 && !NZ_WIDE_KQ_OUTER
-#error "the two-steps-ahead loop moves its cursor in channel-group order"
-#endif
+// the epilogue is one 16-byte store (and residual load) per accumulator tile.  The tile order, the K order and the
+// two-steps-ahead overlap below were each measured against their alternatives.
 constexpr int WIDE_GROUPS = 16;          // position groups (of 16) per workgroup tile
 constexpr int WIDE_NT = 8;               // 16-channel column tiles per workgroup tile
 
@@ -258,12 +216,10 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
   // block: with the K loop below running a 32-channel group's taps back to back, a cell's slice fetched for one tap is
   // in that L2 when the neighbours' workgroups want it for theirs (25 cells x 9 taps = 45 cells' slices instead of 225).
   int bid = blockIdx.x + gridDim.x * blockIdx.y;
-#if NZ_WIDE_XCD
   {
     const int nwg = gridDim.x * gridDim.y, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
-#endif
   const int ct = bid / (int)gridDim.x;                 // tile of 128 output channels
   const int bx = bid - ct * (int)gridDim.x;
   const int cell = bx % p.hw, gbase = (bx / p.hw) * WIDE_GROUPS;
@@ -293,7 +249,6 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     my_live[j] = group < n_groups;
     my_row[j] = (group * p.hw + cell) * 16 + (ppos & 15);
   }
-#if NZ_WIDE_OVERLAP == 2
   // byte offsets of this thread's eight row slices within either source (a dead row -- a position group past the batch --
   // reads the tile's first group instead of branching round its load: its outputs are never stored, and a row of the MFMA
   // only sees its own operand row)
@@ -305,7 +260,6 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     rowoff0[j] = ((uint32_t)row * (uint32_t)p.s0 + (uint32_t)my_chunk * 4u) * 4u;
     rowoff1[j] = ((uint32_t)row * (uint32_t)p.s1 + (uint32_t)my_chunk * 4u) * 4u;
   }
-#endif
   const u32x4* wtile = reinterpret_cast<const u32x4*>(p.ws) + (size_t)ct * (ntaps + 1) * kqt * (3 * WIDE_NT * 64);
   uint32_t taps_left = vmask;
   int tap = __ffs(taps_left) - 1, kq = 0, fs = 0;      // the cursor: step fs = (kq, tap); the centre tap is always on the board
@@ -325,29 +279,18 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     const int cs = second ? p.s1 : p.s0;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-#ifdef NZ_ABLATE_WIDE_FETCH        // timing experiment: no activation loads (results wrong)
-      ra[j] = f32x4{(float)j, 1.f, 2.f, (float)shift};
-#else
       // (a branch per load; reading a live row instead and zeroing at the staging measured slower: 14.9 k against 15.4 k)
       ra[j] = my_live[j] ? *reinterpret_cast<const f32x4*>(src + (size_t)(my_row[j] + shift) * cs) : f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
     const u32x4* wsrc = wtile + ((size_t)tap * kqt + kq) * (3 * WIDE_NT * 64);
 #pragma unroll
     for (int j = 0; j < 6; ++j) rb[j] = wsrc[tid + j * 256];
-#if NZ_WIDE_KQ_OUTER       // K order: 32-channel group by group, each group's taps back to back (see above)
+    // K order: 32-channel group by group, each group's taps back to back (see above)
     if (fs + 1 < total) {    // (the cursor never leaves the last step: later fetches repeat it)
       ++fs;
       if (!taps_left) { taps_left = vmask; ++kq; }
       tap = __ffs(taps_left) - 1;
       taps_left &= taps_left - 1;
     }
-#else
-    if (++kq == kqt) {
-      kq = 0;
-      if (taps_left) { tap = __ffs(taps_left) - 1; taps_left &= taps_left - 1; }
-      else tap = ntaps;
-    }
-#endif
   };
   // registers -> LDS
   auto stage_a = [&](int buf, int j) {                 // row slice j: 4 channels -> 8 bytes per piece (activations split here, once)
@@ -356,20 +299,12 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     const int ppos = (tid >> 3) + 32 * j;
     const int off = ppos * 64 + (((my_chunk >> 1) ^ ((ppos >> 2) & 3)) << 4) + (my_chunk & 1) * 8;
     const float x0 = ra[j][0], x1 = ra[j][1], x2 = ra[j][2], x3 = ra[j][3];
-#ifdef NZ_ABLATE_WIDE_SPLIT        // timing experiment: no split arithmetic (results wrong)
-    const float r0 = x1, r1 = x0, r2 = x3, r3 = x2;
-#else
     const float r0 = x0 - wide_trunc(x0), r1 = x1 - wide_trunc(x1), r2 = x2 - wide_trunc(x2), r3 = x3 - wide_trunc(x3);
-#endif
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     *reinterpret_cast<u32x2*>(ab + 0 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{wide_pack_hi16(x0, x1), wide_pack_hi16(x2, x3)};
     *reinterpret_cast<u32x2*>(ab + 1 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{wide_pack_hi16(r0, r1), wide_pack_hi16(r2, r3)};
-#ifdef NZ_ABLATE_WIDE_SPLIT
-    *reinterpret_cast<u32x2*>(ab + 2 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{wide_pack_hi16(x0, r1), wide_pack_hi16(r2, x3)};
-#else
     *reinterpret_cast<u32x2*>(ab + 2 * (WIDE_GROUPS * 16 * 64) + off) =
         u32x2{wide_pack_hi16(r0 - wide_trunc(r0), r1 - wide_trunc(r1)), wide_pack_hi16(r2 - wide_trunc(r2), r3 - wide_trunc(r3))};
-#endif
   };
   auto stage_b = [&](int buf) {
     u32x4 (&rb)[6] = rb2[0];
@@ -395,11 +330,8 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) stage_a(0, j);
   stage_b(0);
-#if NZ_WIDE_OVERLAP == 2
   if (total > 1) fetch(Set1{});
-#endif
   __syncthreads();
-#if NZ_WIDE_OVERLAP == 2
   // step s: MFMAs on LDS buffer s & 1; the registers of set (s + 1) & 1 (step s + 1's operands, fetched a step ago) are
   // staged into the other LDS buffer in the MFMAs' gaps; step s + 2's operands are fetched into set s & 1 (staged during
   // step s - 1).  Two copies of the step's code, one per register set.
@@ -420,11 +352,7 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     u32x4 (&fb)[6] = rb2[par];
     auto fetch_granule = [&](int i) {
       if (i < 8) {
-#ifdef NZ_ABLATE_WIDE_FETCH
-        fa[i] = f32x4{(float)i, 1.f, 2.f, (float)second};
-#else
         fa[i] = *reinterpret_cast<const f32x4*>(fsrc + (second ? rowoff1[i] : rowoff0[i]));
-#endif
       } else if (i < 14) fb[i - 8] = fw[tid + (i - 8) * 256];
     };
     {   // the cursor moves on (scalar selects: no branch in the step)
@@ -490,7 +418,7 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
 #define NZ_WIDE_STEP(B, X, T)                                                  \
-  acc[g][n] = WIDE_MFMA(wf[n][B], X, acc[g][n]);                               \
+  acc[g][n] = wide_mfma(wf[n][B], X, acc[g][n]);                               \
   {                                                                            \
     /* the 94 staging granules spread evenly over the 168 gaps behind MFMAs 24..191, the 14 loads over the 74 gaps they leave */ \
     constexpr int SG = 94, FG = 14, GAPS = 168, FREE = GAPS - SG;              \
@@ -518,59 +446,6 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     step2(s, Set0{});
     if (s + 1 < total) step2(s + 1, Set1{});
   }
-#else
-  for (int s = 0; s < total; ++s) {
-    const int buf = s & 1;
-    const bool more = s + 1 < total;
-    if (more) fetch(Set0{});                           // the next step's operands fly under this step's MFMAs
-    f32x4 (&ra)[8] = ra2[0];
-    u32x4 (&rb)[6] = rb2[0];
-    u32x4 wf[4][3];
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int piece = 0; piece < 3; ++piece) wf[n][piece] = sB[buf][piece][ch * 4 + n][lane];
-    u32x4 xf[2][3];
-    auto load_x = [&](int g, int slot_buf) {
-      const int prow = (ph * 8 + g) * 16 + pos;
-      const int slot = quad ^ ((prow >> 2) & 3);
-#pragma unroll
-      for (int piece = 0; piece < 3; ++piece) xf[slot_buf][piece] = sA[buf][piece][prow][slot];
-    };
-    load_x(0, 0);
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-      if (g + 1 < 8) load_x(g + 1, (g + 1) & 1);             // the next group's fragments fly under this group's MFMAs
-      const u32x4 x0 = xf[g & 1][0], x1 = xf[g & 1][1], x2 = xf[g & 1][2];
-#if NZ_WIDE_INTERLEAVE
-      // small terms first; the four column tiles' chains side by side (a term of each in turn: an MFMA that waits for the
-      // one before it issues late)
-#define NZ_WIDE_TERM(B, X)                                                          \
-  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[g][n] = wide_mfma(wf[n][B], X, acc[g][n]); \
-  __builtin_amdgcn_sched_barrier(0);
-      NZ_WIDE_TERM(1, x1) NZ_WIDE_TERM(0, x2) NZ_WIDE_TERM(2, x0) NZ_WIDE_TERM(0, x1) NZ_WIDE_TERM(1, x0) NZ_WIDE_TERM(0, x0)
-#undef NZ_WIDE_TERM
-#else
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        acc[g][n] = wide_mfma(wf[n][1], x1, acc[g][n]);       // small terms first; one dependent chain
-        acc[g][n] = wide_mfma(wf[n][0], x2, acc[g][n]);
-        acc[g][n] = wide_mfma(wf[n][2], x0, acc[g][n]);
-        acc[g][n] = wide_mfma(wf[n][0], x1, acc[g][n]);
-        acc[g][n] = wide_mfma(wf[n][1], x0, acc[g][n]);
-        acc[g][n] = wide_mfma(wf[n][0], x0, acc[g][n]);
-        __builtin_amdgcn_sched_barrier(0);                     // keep the chain together (net_dev.hpp)
-      }
-#endif
-    }
-    if (more) {                                                // staging after the MFMAs: slices between the chains were slower
-#pragma unroll
-      for (int j = 0; j < 8; ++j) stage_a(buf ^ 1, j);
-      stage_b(buf ^ 1);
-    }
-    __syncthreads();
-  }
-#endif
 
 #ifdef NZ_WIDE_STAMPS
   if (stamping && lane == 0) {
@@ -1138,9 +1013,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
     const bool next_lds = o + 1 < n_ops && next.w_lds;
     u32x4 wreg[FUSED16_WREGS];
     bool to_fetch = next_lds;                 // the wavefront's first job issues the loads (a wavefront without one: below)
-#ifdef NZ_ABL_F16_NOFETCH
-    to_fetch = false;
-#endif
     if (to_fetch && !op.w_lds) {
       fetch_weights16(next, wreg, tid);
       to_fetch = false;
@@ -1172,10 +1044,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       const unsigned long long j0 = __builtin_amdgcn_s_memtime();
 #endif
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef NZ_ABL_F16_NOK
-      if (n_ops < 0)
-#endif
-      {
       const float* wl = wbuf + (size_t)ct * op.w_chunks * 4 + lane * 4;            // LDS copy of the column tile
       const uint32_t* wg = op.w + (size_t)ct * op.w_chunks * 4 + lane * 4;         // packed stream in L2
       if (op.w_lds && kgt == 1) conv16_job<ntaps, 1, true>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
@@ -1184,7 +1052,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       else if (kgt == 2) conv16_job<ntaps, 2, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
       else if (kgt == 3) conv16_job<ntaps, 3, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
       else conv16_job<ntaps, 4, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      }
       to_fetch = false;
 #ifdef NZ_FUSED_STAMPS
       asm volatile("" :: "v"(acc));
@@ -1209,11 +1076,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
           v[2] += (lo(q0.y) + lo(q1.y)) + lo(q2.y);
           v[3] += (hi(q0.y) + hi(q1.y)) + hi(q2.y);
         }
-#ifdef NZ_ABL_F16_NOACT
-        switch (0) {
-#else
         switch (op.act) {
-#endif
           case 1:
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
@@ -1247,16 +1110,12 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
     if (o < 32) FSTAMP(tk_job[o]);
 #endif
     float* const next_wbuf = lds + (next.w_slot ? wbuf_off1 : wbuf_off0);
-#ifndef NZ_ABL_F16_NOFETCH
     if (next_lds && !next.w_after_barrier) store_weights16(next, next_wbuf, wreg, tid);
-#endif
     __syncthreads();
-#ifndef NZ_ABL_F16_NOFETCH
     if (next_lds && next.w_after_barrier) {
       store_weights16(next, next_wbuf, wreg, tid);
       __syncthreads();
     }
-#endif
 #ifdef NZ_FUSED_STAMPS
     if (o < 32) FSTAMP(tk_bar[o]);
 #endif
@@ -1549,16 +1408,14 @@ void launch_conv(const ConvArgs& a, int ntiles, hipStream_t s) {
 // (MT = 4; weight fragments shared through LDS by the four wavefronts of a workgroup; operand
 // ablations) are in profiles/r01_boardnet_tiles.txt.
 void dispatch_conv(const ConvArgs& a, int ntiles, hipStream_t s) {
-  static const int force_mt = getenv("NZ_BOARDNET_MT") ? atoi(getenv("NZ_BOARDNET_MT")) : 0;   // tuning experiments
   const int kgt = (a.c0 + a.c1) / 16;
-  static const int force_wide = getenv("NZ_BOARDNET_WIDE") ? atoi(getenv("NZ_BOARDNET_WIDE")) : -1;     // tuning experiments
   const int wide_tiles = ((a.n_host + 15) / 16 + WIDE_GROUPS - 1) / WIDE_GROUPS * a.hw * (ntiles / WIDE_NT);
   // one workgroup per tile and per CU: below ~160 tiles the chip is too empty and the per-wavefront kernel wins
   // (w256 5x5: 512 positions = 100 tiles 53 vs 59 TFLOP/s, 1024 = 200 tiles 96 vs 81; w128: 100 tiles 50 vs 58, 400 tiles 91 vs 81)
   // ... and a tile is 256 positions of one cell: with fewer than half of them live (a handful of games on a big board)
   // most of its MFMAs multiply padding, and the per-wavefront kernel wins again
   const bool tiles_filled = (a.n_host + 15) / 16 >= WIDE_GROUPS / 2;
-  if (a.ws != nullptr && (force_wide < 0 ? (wide_tiles >= 160 && tiles_filled) : force_wide != 0)) {
+  if (a.ws != nullptr && wide_tiles >= 160 && tiles_filled) {
     const int groups = (a.n_host + 15) / 16;
     dim3 grid((groups + WIDE_GROUPS - 1) / WIDE_GROUPS * a.hw, ntiles / WIDE_NT);
     if (a.hex) hipLaunchKernelGGL(conv_wide_kernel<true>, grid, dim3(256), 0, s, a);
@@ -1566,18 +1423,15 @@ void dispatch_conv(const ConvArgs& a, int ntiles, hipStream_t s) {
     return;
   }
   if (ntiles % 4 == 0) {
-    const int mt = force_mt ? force_mt : (a.n_host >= 1024 && kgt >= 8) ? 2 : 1;
-    if (mt == 2) launch_conv<2, 4, 3>(a, ntiles, s);
+    if (a.n_host >= 1024 && kgt >= 8) launch_conv<2, 4, 3>(a, ntiles, s);
     else launch_conv<1, 4, 4>(a, ntiles, s);
   } else if (ntiles % 3 == 0) {
     launch_conv<1, 3, 4>(a, ntiles, s);
   } else if (ntiles % 2 == 0) {
-    const int mt = force_mt ? force_mt : a.n_host >= 2048 ? 2 : 1;      // + 7 % at 2048 and 8192 positions; MT = 4 loses
-    if (mt >= 2) launch_conv<2, 2, 3>(a, ntiles, s);
+    if (a.n_host >= 2048) launch_conv<2, 2, 3>(a, ntiles, s);      // + 7 % at 2048 and 8192 positions; MT = 4 loses
     else launch_conv<1, 2, 4>(a, ntiles, s);
   } else {
-    const int mt = force_mt ? force_mt : a.n_host >= 2048 ? 2 : 1;
-    if (mt >= 2) launch_conv<2, 1, 3>(a, ntiles, s);
+    if (a.n_host >= 2048) launch_conv<2, 1, 3>(a, ntiles, s);
     else launch_conv<1, 1, 4>(a, ntiles, s);
   }
 }
@@ -1589,8 +1443,7 @@ namespace {
 // forward_impl with LDS buffers instead of HBM ones.  The value head's two buffers reuse the two trunk buffers that are
 // free once the trunk is done (`trunk_out` holds its output).
 void build_fused(nz_boardnet* h, int trunk_out) {
-  static const int force = getenv("NZ_BOARDNET_FUSED") ? atoi(getenv("NZ_BOARDNET_FUSED")) : -1;   // tuning experiments
-  if (force == 0 || (int)h->ops.size() > FUSED_MAX_OPS) return;
+  if ((int)h->ops.size() > FUSED_MAX_OPS) return;
   int n_cu = 0;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n_cu <= 0) return;
   const int grid = h->max_batch < n_cu ? h->max_batch : n_cu;
@@ -1699,9 +1552,8 @@ void build_fused(nz_boardnet* h, int trunk_out) {
 bool build_fused16_for(nz_boardnet* h, int p_max);
 bool build_fused16_resnet(nz_boardnet* h, int p_max);
 void build_fused16(nz_boardnet* h) {
-  static const int force = getenv("NZ_BOARDNET_FUSED16") ? atoi(getenv("NZ_BOARDNET_FUSED16")) : -1;   // tuning experiments
   const nz_net_desc& nd = h->net;
-  if (force == 0 || (nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) || (int)h->ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return;
+  if ((nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) || (int)h->ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return;
   const int n_ops = (int)h->ops.size(), n_trunk = n_ops - 6;     // first layer + num_blocks layers, then 2 + 4 head layers
   if (n_trunk < 1) return;
   for (const PackedConv& pc : h->convs)

@@ -19,7 +19,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <condition_variable>
@@ -728,9 +727,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
       nodes[node].to_play = (int8_t)to_play;
     }
     slot = __shfl(slot, 0, 64);
-#ifndef NZ_ABLATE_SCS_MASK    // timing experiment: no legal mask (results wrong)
     scs_legal_mask_wave<MASK_WORDS>(R, sc, smask, lane);
-#endif
     uint32_t* m = p.leaf_mask + (size_t)g * MASK_WORDS;
     for (int i = lane; i < MASK_WORDS; i += 64) m[i] = smask[i];
     if (hit) {                                  // the cached evaluation takes the place of the network's
@@ -740,13 +737,11 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
       NZ_STAMP(4);
       break;
     }
-#ifndef NZ_ABLATE_SCS_IMAGE   // timing experiment: no state image (results wrong)
     if (p.image_row_stride > 0)       // straight into the network's input rows: group of 16 slots, then cell, then slot
       scs_state_image_wave<true>(R, sc, images + ((size_t)(slot >> 4) * R.tiles * 16 + (slot & 15)) * p.image_row_stride,
                                  p.image_row_stride, lane);
     else
       scs_state_image_wave<false>(R, sc, images + (size_t)slot * R.channels * R.tiles, 0, lane);
-#endif
     queued = true;
     NZ_STAMP(4);                                // legal mask + state image of the queued leaf
     break;
@@ -825,19 +820,11 @@ __device__ __forceinline__ uint64_t cache_check_word(uint64_t acc, float value, 
 // One conv layer's K loop for one position and ONE column tile: both row tiles (25 cells), NTAPS x KGT steps as
 // straight-line code.  Activations (the MFMA's second operand) come from LDS, this lane's operand row per tap in srow,
 // read one step ahead of the MFMAs that use them; the weights (first operand) straight from the packed L2 stream, their
-// loads running AHEAD steps in front (an L2 round trip is several steps long).
-#ifndef NZ_PERSIST_AHEAD
-#define NZ_PERSIST_AHEAD 2
-#endif
-constexpr int WAVE_AHEAD = NZ_PERSIST_AHEAD;
+// loads running AHEAD steps in front (an L2 round trip is several steps long; three or six steps measured no faster,
+// DESIGN §5c).
+constexpr int WAVE_AHEAD = 2;
 #ifndef NZ_PERSIST_SYNC_DRAIN
 #define NZ_PERSIST_SYNC_DRAIN 0   // 1: a meeting waits for this wavefront's LDS stores before it posts its number
-#endif
-#ifndef NZ_PERSIST_KPRIO
-#define NZ_PERSIST_KPRIO 0        // > 0: the K loops run at this wavefront priority
-#endif
-#ifndef NZ_PERSIST_SPREAD
-#define NZ_PERSIST_SPREAD 1       // 1: a K step's loads placed one per MFMA gap (wave_conv)
 #endif
 // the first WAVE_AHEAD steps' weights of a column tile's stream (steps are contiguous whatever the layer's K groups)
 // (buffer loads: a wave-uniform descriptor of the column tile's stream, ONE vector register with this lane's byte offset,
@@ -855,13 +842,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_weights_rsrc(const uint32
 // the whole pass, and the layer's own scalars went to spill lanes for them
 __device__ __forceinline__ void wave_weights_step(u32x4 (&dst)[3], __amdgpu_buffer_rsrc_t rs, int& wv) {
 #pragma unroll
-  for (int piece = 0; piece < 3; ++piece) {
-#ifdef NZ_ABL_PERSIST_NOB      // timing experiment: no weight stream (results wrong)
-    dst[piece] = u32x4{(uint32_t)(wv & 0), (uint32_t)(piece & 0), 0u, 0u};       // (zeros: finite activations)
-#else
+  for (int piece = 0; piece < 3; ++piece)
     dst[piece] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, wv + piece * 1024, 0, 0));
-#endif
-  }
   wv += 3072;
   asm volatile("" : "+v"(wv));
 }
@@ -921,11 +903,7 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
   };
   auto read = [&](int st, int rt, int piece) -> u32x4 {
     const int tap = st / KGT, kg = st - tap * KGT;
-#ifdef NZ_ABL_PERSIST_NOA    // timing experiment: no LDS operand reads (results wrong)
-    return u32x4{(uint32_t)(ad[tap & 1][rt] & 0), (uint32_t)(piece & 0), (uint32_t)rt, 0u};   // (row tiles stay distinct chains)
-#else
     return *reinterpret_cast<lds_u32x4>(ad[tap & 1][rt] + (uint32_t)((kg * GROUP_FLOATS + piece * PIECE_FLOATS) * 4));
-#endif
   };
   address(0);
 #pragma unroll
@@ -941,10 +919,6 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
     *tsn = now;
   }
 #endif
-#if NZ_PERSIST_KPRIO
-  __builtin_amdgcn_s_setprio(NZ_PERSIST_KPRIO);     // (matrix work before the SIMD's other wavefront's vector work)
-#endif
-#if NZ_PERSIST_SPREAD
   if constexpr (RT == 2) {
     // A step as six SLOTS, each one pair of MFMAs (row tile 0, row tile 1; step16's term order) with loads in its shadow
     // (an MFMA's gap hides eight cycles of other vector issue, no more): slots 0..2 the next step's operand reads in the
@@ -984,29 +958,23 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
       __builtin_amdgcn_sched_barrier(0);
 #undef NZ_PAIR
     }
-#if NZ_PERSIST_KPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    return;
-  }
-#endif
+  } else {
+    // one row tile (an odd last column tile): the next step's reads and weights, then the step's six MFMAs
 #pragma unroll
-  for (int st = 0; st < STEPS; ++st) {
-    if (st + 1 < STEPS) {
+    for (int st = 0; st < STEPS; ++st) {
+      if (st + 1 < STEPS) {
 #pragma unroll
-      for (int piece = 0; piece < 3; ++piece)
+        for (int piece = 0; piece < 3; ++piece)
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) a[(st + 1) & 1][rt][piece] = read(st + 1, rt, piece);
+          for (int rt = 0; rt < RT; ++rt) a[(st + 1) & 1][rt][piece] = read(st + 1, rt, piece);
+      }
+      if (st + AHEAD < STEPS) wave_weights_step(bq[(st + AHEAD) % (AHEAD + 1)], wrs, wv);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) step16(acc[rt], a[st & 1][rt], bq[st % (AHEAD + 1)]);
+      if (st + 2 < STEPS && (st + 2) / KGT != (st + 1) / KGT) address((st + 2) / KGT);
+      __builtin_amdgcn_sched_barrier(0);          // (the scheduler would hoist every later step's loads up here: spills)
     }
-    if (st + AHEAD < STEPS) wave_weights_step(bq[(st + AHEAD) % (AHEAD + 1)], wrs, wv);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) step16(acc[rt], a[st & 1][rt], bq[st % (AHEAD + 1)]);
-    if (st + 2 < STEPS && (st + 2) / KGT != (st + 1) / KGT) address((st + 2) / KGT);
-    __builtin_amdgcn_sched_barrier(0);          // (the scheduler would hoist every later step's loads up here: spills)
   }
-#if NZ_PERSIST_KPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // float offset of (row, channel c0 = 16 ct + 4 (lane >> 4)) within a pieces buffer's row, piece 0
@@ -1019,9 +987,6 @@ __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restric
                                               int lane, int rows) {
   const int orow = rt * 16 + (lane & 15), c0 = ct * 16 + (lane >> 4) * 4;
   if (orow >= rows) return;
-#ifdef NZ_ABL_PERSIST_NOEPI   // timing experiment: no epilogue (results wrong)
-  if (acc[0] != 12345.678f) return;
-#endif
   const int chunk = pieces_chunk(ct, lane, orow);
   float v[4];
 #pragma unroll
@@ -1072,9 +1037,6 @@ __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restric
 __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __restrict__ net, const Fused16Op& op, int ct,
                                                int lane, int rows) {
   const int c0 = ct * 16 + (lane >> 4) * 4;
-#ifdef NZ_ABL_PERSIST_NOEPI   // timing experiment: no epilogue (results wrong)
-  if (acc[0][0] != 12345.678f) return;
-#endif
   int orow[2], chunk[2];
   bool ok[2];
   float v[2][4];
@@ -1174,12 +1136,7 @@ __device__ __forceinline__ void pair_sync(int* flags, int me, int& seq, int lane
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #endif
   if (lane == 0) __hip_atomic_store(&flags[me], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef NZ_PERSIST_SYNC_SLEEP
-#define NZ_PERSIST_SYNC_SLEEP 0
-#endif
-  while (__hip_atomic_load(&flags[me ^ 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) {
-    if (NZ_PERSIST_SYNC_SLEEP > 0) __builtin_amdgcn_s_sleep(NZ_PERSIST_SYNC_SLEEP);
-  }
+  while (__hip_atomic_load(&flags[me ^ 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) {}
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
@@ -1293,51 +1250,6 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
   }
 }
 
-// ---- diagnostic: FOUR wavefronts per game, one (row tile, column tile) each (netbench4_kernel; as a search kernel it
-// lost to the pair: at 128 registers the leader's tree code spills) -----------------------------------------------------
-__device__ __forceinline__ void quad_sync(int* flags, int me, int& seq, int lane) {
-  ++seq;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  if (lane == 0) __hip_atomic_store(&flags[me], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  for (int o = 0; o < 4; ++o)
-    while (__hip_atomic_load(&flags[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) __builtin_amdgcn_s_sleep(1);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-template <bool HEX>
-__device__ __forceinline__ void quad_network(const Fused16Program* __restrict__ prog, float* __restrict__ net, int n_ops, int rows,
-                                             int H, int Wd, int lane, int quad, int* flags, int& seq) {
-  constexpr int ntaps = HEX ? 7 : 9;
-  const int rt = quad & 1, half = quad >> 1;
-  TapRows<ntaps> srow[1];
-  wave_tap_rows<HEX, ntaps>(srow[0], rt * 16 + (lane & 15), rows, H, Wd, lane);
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int OP_DWORDS = (int)(sizeof(Fused16Op) / 4);
-  const gptr1u ops_words = (gptr1u)reinterpret_cast<const uint32_t*>(prog->ops);
-  uint32_t dvec = lane < OP_DWORDS ? ops_words[lane] : 0u;
-  for (int o = 0; o < n_ops; ++o) {
-    Fused16Op op;
-    {
-      uint32_t words[OP_DWORDS];
-#pragma unroll
-      for (int i = 0; i < OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(dvec, i);
-      __builtin_memcpy(&op, words, sizeof(Fused16Op));
-    }
-    if (o + 1 < n_ops && lane < OP_DWORDS) dvec = ops_words[(o + 1) * OP_DWORDS + lane];
-    const int kgt = op.kg0;
-    for (int ct = half; ct < op.ntiles; ct += 2) {
-      f32x4 acc[1];
-      u32x4 bq[WAVE_AHEAD + 1][3];
-      int wv = 0;
-      wave_weights_prologue(bq, wave_weights_rsrc(op.w + (size_t)ct * op.w_chunks * 4, op.w_chunks), wv, lane);
-      if (kgt == 1) wave_layer_kloop<ntaps, 1, 1>(acc, net, op, srow, ct, lane, bq, wv);
-      else if (kgt == 2) wave_layer_kloop<ntaps, 2, 1>(acc, net, op, srow, ct, lane, bq, wv);
-      else if (kgt == 3) wave_layer_kloop<ntaps, 3, 1>(acc, net, op, srow, ct, lane, bq, wv);
-      else wave_layer_kloop<ntaps, 4, 1>(acc, net, op, srow, ct, lane, bq, wv);
-      wave_epilogue(acc[0], net, op, rt, ct, lane, rows);
-    }
-    quad_sync(flags, quad, seq, lane);
-  }
-}
 // The ascending list of a position's legal actions (Explorer.py:163-165): the mask in LDS, then lane w enumerates mask
 // word w (and word 64 + w) behind a prefix sum of the words' bit counts.  Returns their number.
 __device__ __forceinline__ int legal_list_wave(const ScsRules& R, const ScsState& sc, uint32_t* smask, int* sidx, int lane) {
@@ -1830,10 +1742,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
   int seq = 0, pass = 0;
   for (;;) {
     int gv;
-#ifndef NZ_PERSIST_GO_SLEEP
-#define NZ_PERSIST_GO_SLEEP 2
-#endif
-    while ((gv = __hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == pass) __builtin_amdgcn_s_sleep(NZ_PERSIST_GO_SLEEP);
+    while ((gv = __hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == pass) __builtin_amdgcn_s_sleep(2);
     if (gv == PERSIST_EXIT) break;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     pass = gv;
@@ -1853,36 +1762,6 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
     wave_network<HEX>(wna, net, lane, 1, flags, seq);
     pair_sync(flags, 1, seq, lane);               // (the value plane is whole; the leader has done its softmax meanwhile)
   }
-}
-
-template <bool HEX>
-__global__ __launch_bounds__(PERSIST_GAMES * 4 * 64) void netbench4_kernel(PersistArgs q, int iters, unsigned long long* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = lane_id();
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int slot = wave >> 2, quad = wave & 3;                // a game's four wavefronts sit on the four SIMDs
-  if (threadIdx.x < PERSIST_GAMES * 8)
-    reinterpret_cast<int*>(smem + PERSIST_RULES_BYTES + (size_t)(threadIdx.x >> 3) * q.wave_bytes + PERSIST_GAME_BYTES - PERSIST_FLAG_BYTES)[threadIdx.x & 7] = 0;
-  __syncthreads();
-  unsigned char* const wb = smem + PERSIST_RULES_BYTES + (size_t)slot * q.wave_bytes;
-  int* const flags = reinterpret_cast<int*>(wb + PERSIST_GAME_BYTES - PERSIST_FLAG_BYTES);
-  float* const net = reinterpret_cast<float*>(wb + PERSIST_GAME_BYTES);
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
-  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(q.prog))[lane] : 0u;
-#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
-  const int hw = PHDR(hw), H = PHDR(h), Wd = PHDR(wd), n_ops = PHDR(n_ops);
-#undef PHDR
-  if (quad == 0)
-    for (int i = lane * 4; i < q.net_floats; i += 256) *reinterpret_cast<f32x4*>(net + i) = f32x4{0.f, 0.f, 0.f, 0.f};
-  int seq = 0;
-  quad_sync(flags, quad, seq, lane);
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  const int active = iters >> 16 ? iters >> 16 : PERSIST_GAMES, n_it = iters & 0xffff;
-  if (slot < active)
-    for (int it = 0; it < n_it; ++it) quad_network<HEX>(q.prog, net, n_ops, hw, H, Wd, lane, quad, flags, seq);
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  if (quad == 0 && lane == 0) out[blockIdx.x * PERSIST_GAMES + slot] = (t1 - t0) / (unsigned long long)n_it;
 }
 
 // Diagnostic: the network part of persist_kernel alone -- every game slot of every workgroup runs `iters` passes on an
@@ -2723,7 +2602,6 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
     h->p.eval_value = h->value;
     h->p.c_bits = h->cache_bits;
     h->p.terminal_budget = 1;                  // measured best (bench_scs.py: 1 -> 308 games/s, 16 -> 259, unbounded -> 226)
-    if (const char* e = getenv("NZ_SCS_TERMINAL_BUDGET")) h->p.terminal_budget = std::max(1, atoi(e));   // tuning experiments
     if (persist) {                               // the whole move's search of every game: one launch
       if (h->persist_profile) {
         if (!h->ev_p0) { S_HIP(h, hipEventCreate(&h->ev_p0)); S_HIP(h, hipEventCreate(&h->ev_p1)); }
@@ -2733,15 +2611,6 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
       hipLaunchKernelGGL(h->persist_fn, pgrid, dim3(PERSIST_THREADS), persist_lds, s, h->p, h->pq);
       S_HIP(h, hipGetLastError());
       ++h->waves;
-      static const bool move_times = getenv("NZ_SCS_MOVE_TIMES") != nullptr;     // experiment: the duration of every move's launch
-      if (move_times) {
-        int live = 0;
-        for (int g = 0; g < G; ++g) live += status[(size_t)g * 7 + 4] == 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        S_HIP(h, hipStreamSynchronize(s));
-        fprintf(stderr, "move %lld: %d live games, %.3f ms\n", (long long)move, live,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-      }
       if (h->persist_profile) S_HIP(h, hipEventRecord(h->ev_p1, s));
       st = nz_scs_search_end_move(h, h->uniforms, stream);     // (synchronises)
       if (st != NZ_OK) return st;
@@ -3069,18 +2938,18 @@ nz_status nz_scs_search_record_read(nz_scs_search* h, int32_t slot, int32_t* cou
 }
 
 // Diagnostic (library built with -DNZ_PERSIST_STAMPS; zeros otherwise): shader ticks of the persistent kernel summed
-// over all games and moves since the last reset -- out10: clone, descent, legal mask + list, planes + split, network,
+// over all games and moves since the last reset -- out13: clone, descent, legal mask + list, planes + split, network,
 // softmax + value, expansion, backup, whole moves (sum over games), the slowest single (game, move).
-nz_status nz_scs_search_persist_ticks(nz_scs_search* h, int64_t* out10_host) {   // (13 values)
-  if (!h || !out10_host) return NZ_ERR_ARG;
+nz_status nz_scs_search_persist_ticks(nz_scs_search* h, int64_t* out13_host) {   // (13 values)
+  if (!h || !out13_host) return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
   S_HIP(h, hipDeviceSynchronize());
   int64_t c[16];
   S_HIP(h, hipMemcpy(c, h->p.counters, sizeof(c), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 6; ++i) out10_host[i] = c[2 + i];
-  for (int i = 6; i < 9; ++i) out10_host[i] = c[5 + i];
-  out10_host[9] = c[14];
-  for (int i = 0; i < 3; ++i) out10_host[10 + i] = c[8 + i];
+  for (int i = 0; i < 6; ++i) out13_host[i] = c[2 + i];
+  for (int i = 6; i < 9; ++i) out13_host[i] = c[5 + i];
+  out13_host[9] = c[14];
+  for (int i = 0; i < 3; ++i) out13_host[10 + i] = c[8 + i];
   return NZ_OK;
 }
 
@@ -3088,7 +2957,6 @@ nz_status nz_scs_search_persist_ticks(nz_scs_search* h, int64_t* out10_host) {  
 // slots each running `iters` passes; ticks_host[blocks * 4].
 nz_status nz_scs_netbench(nz_boardnet* net, int32_t blocks, int32_t iters, uint64_t* ticks_host) {
   if (!net || blocks <= 0 || iters <= 0 || !ticks_host) return NZ_ERR_ARG;
-  const bool quad = getenv("NZ_NETBENCH_QUAD") != nullptr;        // prototype: four wavefronts per game
   nz::WaveNet wn{};
   std::string why;
   if (!nz::boardnet_wave_program(net, &wn, &why)) return sfail(nullptr, NZ_ERR_STATE, "%s", why.c_str());
@@ -3101,13 +2969,7 @@ nz_status nz_scs_netbench(nz_boardnet* net, int32_t blocks, int32_t iters, uint6
   S_HIP(nullptr, hipMalloc((void**)&out, (size_t)blocks * PERSIST_GAMES * 8));
   hipError_t e = wn.hex ? hipFuncSetAttribute((const void*)netbench_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
                         : hipFuncSetAttribute((const void*)netbench_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess && quad && !wn.hex) {
-    e = hipFuncSetAttribute((const void*)netbench4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(netbench4_kernel<false>, dim3(blocks), dim3(PERSIST_GAMES * 4 * 64), lds, nullptr, q, iters, out);
-      e = hipDeviceSynchronize();
-    }
-  } else if (e == hipSuccess) {
+  if (e == hipSuccess) {
     if (wn.hex) hipLaunchKernelGGL(netbench_kernel<true>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, out);
     else hipLaunchKernelGGL(netbench_kernel<false>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, out);
     e = hipDeviceSynchronize();
