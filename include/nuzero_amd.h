@@ -460,6 +460,41 @@ nz_status nz_scs_search_persistent(nz_scs_search* h, int32_t enable, int32_t* us
  * the `seeds` of the play calls are then ignored (may be NULL).  n = 0: back to the description's one map.  Resets. */
 nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terrain_host, const int32_t* vp_host,
                                   const uint32_t* mt_keys_host, const int32_t* mt_pos_host);
+/* The same per-game maps drawn by the library from seeds alone, on the device: what SCS_Game(config) draws for a
+ * "Randomized" map or victory points (SCS_Game.py:1678-1738) after np.random.seed(seed), as the reference's Gamer does
+ * per game (Training/Gamer.py:52).  nz_scs_search_set_map_draw sets, once per config, what a game draws:
+ *   types [n_types][3]  attack modifier, defense modifier, cost of each terrain type in the Terrain section's order
+ *                       (at most 32);
+ *   cdf [n_types]       numpy's float64 p.cumsum() / p.cumsum()[-1] of the map's distribution (uniform when the config
+ *                       gives none); a tile is types[searchsorted(cdf, random_sample(), 'right')] (legacy choice(p));
+ *   order[2]            the randomized sections in the file's order: NZ_SCS_DRAW_MAP, NZ_SCS_DRAW_VP; 0 = none;
+ *   number_vp[2]        points per side (as n_vp of the description), side_cols[4] the two sides' columns
+ *                       [p1 first, p1 end, p2 first, p2 end) -- a point is (choice(range(rows)), choice(side's columns)),
+ *                       redrawn while it repeats one of its side's.
+ * Sections the config gives in "Detailed" form are the description's.  The caller validates the distribution (numpy's
+ * ValueError); the library refuses a spec without randomized sections, counts unlike the description's, empty or bad
+ * ranges and more points than a side has cells (keeping the spec set before).  NULL: no draw set.
+ * nz_scs_search_draw_games: the effect of nz_scs_search_set_games with the maps and the streams RandomState(seeds[i])
+ * gives -- bit for bit what the host draw gives, digests of the inference cache included.  seeds_host uint32 [n]
+ * (n >= the games of a round); the per-game buffers are kept and grown across calls.  Returns when the maps are set
+ * (the streams are built on the host from one copy of the MT19937 states).  Resets.
+ * nz_scs_search_drawn_games: copies of the last draw (host or device pointers; any may be NULL): *n games, terrain
+ * float32 [n][tiles][3], vp int32 [n][n_vp0 + n_vp1][2], the streams' state after the map: mt_keys uint32 [n][624],
+ * mt_pos int32 [n] (numpy's RandomState.get_state() key and pos).  NZ_ERR_STATE when the games were not drawn here. */
+#define NZ_SCS_DRAW_MAP 1
+#define NZ_SCS_DRAW_VP 2
+typedef struct nz_scs_map_draw {
+  int32_t n_types;
+  const float* types;
+  const double* cdf;
+  int32_t order[2];
+  int32_t number_vp[2];
+  int32_t side_cols[4];
+} nz_scs_map_draw;
+nz_status nz_scs_search_set_map_draw(nz_scs_search* h, const nz_scs_map_draw* spec);
+nz_status nz_scs_search_draw_games(nz_scs_search* h, int64_t n, const uint32_t* seeds_host, void* stream);
+nz_status nz_scs_search_drawn_games(nz_scs_search* h, int64_t* n, float* terrain, int32_t* vp, uint32_t* mt_keys,
+                                    int32_t* mt_pos, void* stream);
 /* As above for the rule operators: every game of the batch on its own map (NULL terrain: the description's).  Resets. */
 nz_status nz_scs_set_maps(nz_scs* h, const float* terrain_host, const int32_t* vp_host, void* stream);
 /* HIP-event timing of the persistent kernel, on the stream it is launched on.  enable: 1 on (sums zeroed), 0 off, -1 leave.

@@ -56,6 +56,14 @@ class ScsDesc(Structure):
                 ("units", c_void_p), ("arrival", c_void_p)]
 
 
+NZ_SCS_DRAW_MAP, NZ_SCS_DRAW_VP = 1, 2
+
+
+class ScsMapDraw(Structure):
+    _fields_ = [("n_types", c_int32), ("types", c_void_p), ("cdf", c_void_p), ("order", c_int32 * 2),
+                ("number_vp", c_int32 * 2), ("side_cols", c_int32 * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/nuzero_amd.h declares
 SIGNATURES = {
     "nz_version": (c_char_p, []),
@@ -133,6 +141,9 @@ SIGNATURES = {
     "nz_scs_search_cache_stats": (c_int32, [c_void_p, POINTER(c_int64)]),
     "nz_scs_search_limits": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "nz_scs_search_set_games": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_scs_search_set_map_draw": (c_int32, [c_void_p, POINTER(ScsMapDraw)]),
+    "nz_scs_search_draw_games": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "nz_scs_search_drawn_games": (c_int32, [c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_set_maps": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_search_persistent": (c_int32, [c_void_p, c_int32, POINTER(c_int32)]),
     "nz_scs_search_persist_ticks": (c_int32, [c_void_p, POINTER(c_int64)]),

@@ -24,6 +24,7 @@ UNITS = [
     ("engine.hip", ["-ffp-contract=off"]),
     ("scs.hip", ["-ffp-contract=off"]),
     ("scs_search.hip", ["-ffp-contract=off"]),
+    ("scs_draw.hip", ["-ffp-contract=off"]),
     ("boardnet.hip", []),
     ("replay.hip", ["-ffp-contract=off"]),
     ("loss.hip", []),

@@ -135,19 +135,6 @@ bool nz::scs_fill_rules(const nz_scs_desc* d, ScsRules* out, std::string* err) {
   return true;
 }
 
-// A game's own map over a description: terrain [tiles][3] (attack modifier, defense modifier, cost) and the victory
-// points [n_vp[0] + n_vp[1]][2] (row, column), the counts as in the description.
-void nz::scs_apply_map(ScsRules* r, const float* terrain, const int32_t* vp) {
-  for (int t = 0; t < r->tiles; ++t) {
-    r->attack_mod[t] = terrain[t * 3 + 0];
-    r->defense_mod[t] = terrain[t * 3 + 1];
-    r->cost[t] = (int32_t)terrain[t * 3 + 2];
-    for (int k = 0; k < 3; ++k) r->terrain_f[t][k] = terrain[t * 3 + k];
-  }
-  for (int p = 0, k = 0; p < 2; ++p)
-    for (int i = 0; i < r->n_vp[p]; ++i, ++k) r->vp[p][i] = (int8_t)(vp[k * 2] * r->cols + vp[k * 2 + 1]);
-}
-
 extern "C" {
 
 // Every game of the batch on its own map (host arrays: terrain float32 [G][tiles][3], vp int32 [G][n_vp0 + n_vp1][2]);

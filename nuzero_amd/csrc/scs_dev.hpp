@@ -47,7 +47,72 @@ struct ScsRules {                     // immutable game description (one per eng
 };
 
 bool scs_fill_rules(const nz_scs_desc* d, ScsRules* out, std::string* err);   // scs.hip (host)
-void scs_apply_map(ScsRules* r, const float* terrain, const int32_t* vp);      // scs.hip (host): a game's own map
+
+// A game's own map over a description: terrain [tiles][3] (attack modifier, defense modifier, cost) and the victory
+// points [n_vp[0] + n_vp[1]][2] (row, column), the counts as in the description.  Host (nz_scs_set_maps,
+// nz_scs_search_set_games) and device (scs_draw_kernel) apply maps with this one function.
+__host__ __device__ inline void scs_apply_map(ScsRules* r, const float* terrain, const int32_t* vp) {
+  for (int t = 0; t < r->tiles; ++t) {
+    r->attack_mod[t] = terrain[t * 3 + 0];
+    r->defense_mod[t] = terrain[t * 3 + 1];
+    r->cost[t] = (int32_t)terrain[t * 3 + 2];
+    for (int k = 0; k < 3; ++k) r->terrain_f[t][k] = terrain[t * 3 + k];
+  }
+  for (int p = 0, k = 0; p < 2; ++p)
+    for (int i = 0; i < r->n_vp[p]; ++i, ++k) r->vp[p][i] = (int8_t)(vp[k * 2] * r->cols + vp[k * 2 + 1]);
+}
+
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // murmur3 finaliser
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+  return x;
+}
+
+// The 128-bit digest of a map row, the part of the inference cache's key that ScsState does not hold: the per-game
+// fields one word at a time (terrain as the image's float32 triples and the rules' float64 / integer copies, victory
+// points), never the struct's bytes -- padding and entries past `tiles` / n_vp are not the map's.  Equal maps give
+// equal digests, so games on equal maps still share entries (as the reference's cache, which hashes the tensor).
+// Shared by the host rows of nz_scs_search_set_games and the device rows of scs_draw_kernel.
+struct ScsMapDigest {
+  uint64_t a = 0, b = 0;
+  __host__ __device__ void put(uint64_t w) {          // chained: the order of the words is part of the digest
+    a = mix64(a ^ mix64(w ^ 0x9e3779b97f4a7c15ull));
+    b = mix64(b + mix64(w * 0xd6e8feb86659fd93ull + 0x2545f4914f6cdd1dull));
+  }
+};
+__host__ __device__ inline void scs_map_digest(const ScsRules& r, uint64_t out[2]) {
+  ScsMapDigest d;
+  for (int t = 0; t < r.tiles; ++t) {
+    for (int k = 0; k < 3; ++k) d.put(__builtin_bit_cast(uint32_t, r.terrain_f[t][k]));
+    d.put(__builtin_bit_cast(uint64_t, r.attack_mod[t]));
+    d.put(__builtin_bit_cast(uint64_t, r.defense_mod[t]));
+    d.put((uint64_t)(uint32_t)r.cost[t]);
+  }
+  for (int q = 0; q < 2; ++q) {
+    d.put((uint64_t)(uint32_t)r.n_vp[q]);
+    for (int i = 0; i < r.n_vp[q]; ++i) d.put((uint64_t)(uint8_t)r.vp[q][i]);
+  }
+  out[0] = mix64(d.a ^ (d.b >> 7));
+  out[1] = mix64(d.b ^ (d.a << 9));
+}
+
+// What a "Randomized" config draws per game (nz_scs_map_draw, checked and copied by nz_scs_search_set_map_draw); a
+// kernel argument, so it has fixed bounds.
+constexpr int SCS_DRAW_MAX_TYPES = 32;
+struct ScsDrawSpec {
+  int32_t n_types;
+  float types[SCS_DRAW_MAX_TYPES][3];          // attack modifier, defense modifier, cost in the Terrain section's order
+  double cdf[SCS_DRAW_MAX_TYPES];              // numpy's p.cumsum() / its last entry
+  int32_t order[2];                            // NZ_SCS_DRAW_MAP / NZ_SCS_DRAW_VP in file order, 0 = none
+  int32_t number_vp[2];
+  int32_t side_cols[2][2];                     // each side's victory-point columns [first, end)
+};
+// scs_draw.hip: draw the maps of games [0, n) from seeds[g] into rules rows (template `tmpl` with the map applied),
+// their digests, terrain [n][tiles][3], vp [n][n_vp0 + n_vp1][2], the MT19937 state after the draws (keys [n][624],
+// pos [n]) and err [n] (0, SCS_DRAW_ERR_COST, SCS_DRAW_ERR_CAP).  All pointers are device memory.
+enum : int32_t { SCS_DRAW_ERR_COST = 1, SCS_DRAW_ERR_CAP = 2 };
+hipError_t scs_draw_launch(const ScsDrawSpec& spec, const ScsRules* tmpl, int64_t n, const uint32_t* seeds,
+                           ScsRules* rows, uint64_t* rules_key, float* terrain, int32_t* vp, uint32_t* mt_keys,
+                           int32_t* mt_pos, int32_t* err, hipStream_t stream);
 
 struct ScsState {
   int16_t stage, turn, length;

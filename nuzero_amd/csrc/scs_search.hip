@@ -402,10 +402,6 @@ __global__ void begin_move_kernel(SearchParams p, const double* __restrict__ noi
 // hash is used only matters for which entries collide).  With one map for all games the key is the state's hash.  The table
 // is only READ inside wave_kernel and only WRITTEN by cache_put_kernel between two wave kernels, so no entry is
 // ever seen half-written.
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // murmur3 finaliser
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
 // every lane returns the same (hi, lo): position-tagged words mixed per lane, combined across the wavefront
 __device__ __forceinline__ void state_hash_wave(const ScsState& st, int lane, uint64_t& hi, uint64_t& lo) {
   const uint32_t* w = reinterpret_cast<const uint32_t*>(&st);
@@ -2007,7 +2003,16 @@ struct nz_scs_search {
   int32_t* rules_row_dev = nullptr;           // [n_games]
   uint64_t* rules_key_dev = nullptr;          // [n_game_rows][2] map digests (the inference cache's key)
   int64_t n_game_rows = 0;
+  int64_t game_rows_cap = 0;                  // rows game_rules_dev / rules_key_dev hold (grown, never shrunk)
   std::vector<nz_rng*> game_streams;          // [n_game_rows] or empty: streams from the seeds
+  // nz_scs_search_draw_games: what a game draws and the last draw's per-game buffers (grown, never shrunk)
+  bool draw_set = false;
+  ScsDrawSpec draw{};
+  int64_t draw_cap = 0;
+  int64_t n_drawn = 0;                        // games of the last draw; 0 when the games were set otherwise
+  uint32_t *draw_seeds_dev = nullptr, *draw_keys_dev = nullptr;
+  float* draw_terrain_dev = nullptr;
+  int32_t *draw_vp_dev = nullptr, *draw_pos_dev = nullptr, *draw_err_dev = nullptr;
 };
 
 namespace {
@@ -2207,6 +2212,9 @@ void nz_scs_search_destroy(nz_scs_search* h) {
   if (h->game_rules_dev) (void)hipFree(h->game_rules_dev);
   if (h->rules_key_dev) (void)hipFree(h->rules_key_dev);
   if (h->rules_row_dev) (void)hipFree(h->rules_row_dev);
+  for (void* q : {(void*)h->draw_seeds_dev, (void*)h->draw_keys_dev, (void*)h->draw_terrain_dev, (void*)h->draw_vp_dev,
+                  (void*)h->draw_pos_dev, (void*)h->draw_err_dev})
+    if (q) (void)hipFree(q);
   for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
   delete h;
 }
@@ -2794,31 +2802,46 @@ nz_status nz_scs_search_persistent(nz_scs_search* h, int32_t enable, int32_t* us
   return NZ_OK;
 }
 
-// The 128-bit digest of a map row, the part of the inference cache's key that ScsState does not hold: the per-game
-// fields one word at a time (terrain as the image's float32 triples and the rules' float64 / integer copies, victory
-// points), never the struct's bytes -- padding and entries past `tiles` / n_vp are not the map's.  Equal maps give
-// equal digests, so games on equal maps still share entries (as the reference's cache, which hashes the tensor).
-static void map_digest(const ScsRules& r, uint64_t out[2]) {
-  uint64_t a = 0, b = 0;
-  auto put = [&](uint64_t w) {          // chained: the order of the words is part of the digest
-    a = mix64(a ^ mix64(w ^ 0x9e3779b97f4a7c15ull));
-    b = mix64(b + mix64(w * 0xd6e8feb86659fd93ull + 0x2545f4914f6cdd1dull));
-  };
-  auto bits32 = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); return (uint64_t)u; };
-  auto bits64 = [](double x) { uint64_t u; std::memcpy(&u, &x, 8); return u; };
-  for (int t = 0; t < r.tiles; ++t) {
-    for (int k = 0; k < 3; ++k) put(bits32(r.terrain_f[t][k]));
-    put(bits64(r.attack_mod[t]));
-    put(bits64(r.defense_mod[t]));
-    put((uint64_t)(uint32_t)r.cost[t]);
-  }
-  for (int q = 0; q < 2; ++q) {
-    put((uint64_t)(uint32_t)r.n_vp[q]);
-    for (int i = 0; i < r.n_vp[q]; ++i) put((uint64_t)(uint8_t)r.vp[q][i]);
-  }
-  out[0] = mix64(a ^ (b >> 7));
-  out[1] = mix64(b ^ (a << 9));
+namespace {
+// Back to the description's one map; the per-game buffers stay for the next rows.
+void clear_games(nz_scs_search* h) {
+  for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
+  h->game_streams.clear();
+  h->n_game_rows = 0;
+  h->n_drawn = 0;
+  h->p.rules = h->base_rules_dev;
+  h->p.rules_row = nullptr;
+  h->p.rules_key = nullptr;
 }
+
+// Rules rows and digests for n games, and the slots' row indices.
+nz_status grow_game_rows(nz_scs_search* h, int64_t n) {
+  if (n > h->game_rows_cap) {
+    if (h->game_rules_dev) { (void)hipFree(h->game_rules_dev); h->game_rules_dev = nullptr; }
+    if (h->rules_key_dev) { (void)hipFree(h->rules_key_dev); h->rules_key_dev = nullptr; }
+    h->game_rows_cap = 0;
+    if (hipMalloc((void**)&h->game_rules_dev, (size_t)n * sizeof(ScsRules)) != hipSuccess ||
+        hipMalloc((void**)&h->rules_key_dev, (size_t)n * 2 * sizeof(uint64_t)) != hipSuccess)
+      return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
+    h->game_rows_cap = n;
+  }
+  if (!h->rules_row_dev && hipMalloc((void**)&h->rules_row_dev, (size_t)h->n_games * sizeof(int32_t)) != hipSuccess)
+    return sfail(h, NZ_ERR_HIP, "device allocation failed");
+  return NZ_OK;
+}
+
+// The rows are in place: slot g plays row g, the plays read the per-game rows and digests.
+nz_status use_game_rows(nz_scs_search* h, int64_t n, void* stream) {
+  std::vector<int32_t> ident(h->n_games);
+  for (int g = 0; g < h->n_games; ++g) ident[g] = g;
+  S_HIP(h, hipMemcpy(h->rules_row_dev, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->n_game_rows = n;
+  h->p.rules = h->game_rules_dev;
+  h->p.rules_row = h->rules_row_dev;
+  h->p.rules_key = h->rules_key_dev;
+  return nz_scs_search_reset(h, stream);       // the slots' games start on their own maps (row g for slot g)
+}
+}  // namespace
 
 // Every game of the next plays on its OWN map, as the reference builds a new game object -- and with a "Randomized"
 // config a new map -- per game (Training/Gamer.py:52, SCS_Game.py:1678-1738).  Host arrays for n games (n >= the games of
@@ -2832,14 +2855,7 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
     return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
   S_HIP(h, hipDeviceSynchronize());
-  for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
-  h->game_streams.clear();
-  if (h->game_rules_dev) { (void)hipFree(h->game_rules_dev); h->game_rules_dev = nullptr; }
-  if (h->rules_key_dev) { (void)hipFree(h->rules_key_dev); h->rules_key_dev = nullptr; }
-  h->n_game_rows = 0;
-  h->p.rules = h->base_rules_dev;
-  h->p.rules_row = nullptr;
-  h->p.rules_key = nullptr;
+  clear_games(h);
   if (n == 0) return nz_scs_search_reset(h, nullptr);
   if (n < h->n_games) return sfail(h, NZ_ERR_ARG, "%lld games set, the engine plays %d at a time", (long long)n, h->n_games);
   const ScsRules& b = h->host_rules;
@@ -2851,28 +2867,140 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
       if (rows[(size_t)i].cost[t] < 1) return sfail(h, NZ_ERR_ARG, "game %lld: a terrain with movement cost < 1", (long long)i);
   }
   std::vector<uint64_t> keys((size_t)n * 2);
-  for (int64_t i = 0; i < n; ++i) map_digest(rows[(size_t)i], &keys[(size_t)i * 2]);
-  if (hipMalloc((void**)&h->game_rules_dev, rows.size() * sizeof(ScsRules)) != hipSuccess ||
-      hipMalloc((void**)&h->rules_key_dev, keys.size() * sizeof(uint64_t)) != hipSuccess)
-    return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
+  for (int64_t i = 0; i < n; ++i) scs_map_digest(rows[(size_t)i], &keys[(size_t)i * 2]);
+  if (nz_status st = grow_game_rows(h, n)) return st;
   S_HIP(h, hipMemcpy(h->game_rules_dev, rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice));
   S_HIP(h, hipMemcpy(h->rules_key_dev, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  if (!h->rules_row_dev && hipMalloc((void**)&h->rules_row_dev, (size_t)h->n_games * sizeof(int32_t)) != hipSuccess)
-    return sfail(h, NZ_ERR_HIP, "device allocation failed");
-  std::vector<int32_t> ident(h->n_games);
-  for (int g = 0; g < h->n_games; ++g) ident[g] = g;
-  S_HIP(h, hipMemcpy(h->rules_row_dev, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   if (mt_keys_host)
     for (int64_t i = 0; i < n; ++i) {
       nz_rng* r = nz_rng_create_state(mt_keys_host + (size_t)i * 624, mt_pos_host[i], 0, 0.0);
       if (!r) return sfail(h, NZ_ERR_ARG, "game %lld: bad stream position %d", (long long)i, mt_pos_host[i]);
       h->game_streams.push_back(r);
     }
-  h->n_game_rows = n;
-  h->p.rules = h->game_rules_dev;
-  h->p.rules_row = h->rules_row_dev;
-  h->p.rules_key = h->rules_key_dev;
-  return nz_scs_search_reset(h, nullptr);      // the slots' games start on their own maps (row g for slot g)
+  return use_game_rows(h, n, nullptr);
+}
+
+// What a "Randomized" config draws per game (SCS_Game.py:1678-1738), checked against the description the engine was
+// created with; NULL forgets it.  A refused spec leaves the one set before.
+nz_status nz_scs_search_set_map_draw(nz_scs_search* h, const nz_scs_map_draw* spec) {
+  if (!h) return NZ_ERR_ARG;
+  if (!spec) {
+    h->draw_set = false;
+    return NZ_OK;
+  }
+  const ScsRules& b = h->host_rules;
+  ScsDrawSpec d{};
+  bool map = false, vps = false;
+  for (int s = 0; s < 2; ++s) {
+    const int o = spec->order[s];
+    if (o != 0 && o != NZ_SCS_DRAW_MAP && o != NZ_SCS_DRAW_VP) return sfail(h, NZ_ERR_ARG, "unknown section %d in the draw order", o);
+    if ((o == NZ_SCS_DRAW_MAP && map) || (o == NZ_SCS_DRAW_VP && vps)) return sfail(h, NZ_ERR_ARG, "a section drawn twice");
+    map |= o == NZ_SCS_DRAW_MAP;
+    vps |= o == NZ_SCS_DRAW_VP;
+    d.order[s] = o;
+  }
+  if (!map && !vps) return sfail(h, NZ_ERR_ARG, "no randomized map or victory points: there is nothing to draw");
+  if (map) {
+    if (spec->n_types < 1 || spec->n_types > SCS_DRAW_MAX_TYPES || !spec->types || !spec->cdf)
+      return sfail(h, NZ_ERR_ARG, "%d terrain types (1 to %d, with their cdf)", spec->n_types, SCS_DRAW_MAX_TYPES);
+    d.n_types = spec->n_types;
+    for (int i = 0; i < d.n_types; ++i) {
+      for (int k = 0; k < 3; ++k) d.types[i][k] = spec->types[i * 3 + k];
+      d.cdf[i] = spec->cdf[i];
+      if (!(d.cdf[i] >= 0.0) || (i > 0 && d.cdf[i] < d.cdf[i - 1]))
+        return sfail(h, NZ_ERR_ARG, "the terrain cdf is not a non-decreasing list of non-negative numbers");
+    }
+    if (d.cdf[d.n_types - 1] != 1.0) return sfail(h, NZ_ERR_ARG, "the terrain cdf does not end at 1");
+  }
+  if (vps) {
+    for (int q = 0; q < 2; ++q) {
+      const int first = spec->side_cols[2 * q], end = spec->side_cols[2 * q + 1];
+      if (spec->number_vp[q] != b.n_vp[q])
+        return sfail(h, NZ_ERR_ARG, "player %d: %d victory points drawn, the description has %d", q + 1, spec->number_vp[q], b.n_vp[q]);
+      if (first < 0 || end > b.cols || end <= first)
+        return sfail(h, NZ_ERR_ARG, "player %d: victory-point columns [%d, %d) on a board of %d", q + 1, first, end, b.cols);
+      if ((int64_t)spec->number_vp[q] > (int64_t)b.rows * (end - first))
+        return sfail(h, NZ_ERR_ARG, "player %d: %d victory points on a side of %d cells", q + 1, spec->number_vp[q], b.rows * (end - first));
+      d.number_vp[q] = spec->number_vp[q];
+      d.side_cols[q][0] = first;
+      d.side_cols[q][1] = end;
+    }
+  }
+  h->draw = d;
+  h->draw_set = true;
+  return NZ_OK;
+}
+
+// nz_scs_search_set_games with the maps and streams of RandomState(seeds[i]), drawn by scs_draw_kernel.
+nz_status nz_scs_search_draw_games(nz_scs_search* h, int64_t n, const uint32_t* seeds_host, void* stream) {
+  if (!h || n <= 0 || !seeds_host) return NZ_ERR_ARG;
+  if (!h->draw_set) return sfail(h, NZ_ERR_STATE, "no map draw set (nz_scs_search_set_map_draw)");
+  if (n < h->n_games) return sfail(h, NZ_ERR_ARG, "%lld games set, the engine plays %d at a time", (long long)n, h->n_games);
+  const hipStream_t s = (hipStream_t)stream;
+  S_HIP(h, hipSetDevice(h->device));
+  S_HIP(h, hipDeviceSynchronize());           // the last plays may still read the rows
+  clear_games(h);
+  if (nz_status st = grow_game_rows(h, n)) return st;
+  const ScsRules& b = h->host_rules;
+  const int64_t T = b.tiles, nv = b.n_vp[0] + b.n_vp[1];
+  if (n > h->draw_cap) {
+    for (void* q : {(void*)h->draw_seeds_dev, (void*)h->draw_keys_dev, (void*)h->draw_terrain_dev, (void*)h->draw_vp_dev,
+                    (void*)h->draw_pos_dev, (void*)h->draw_err_dev})
+      if (q) (void)hipFree(q);
+    h->draw_seeds_dev = h->draw_keys_dev = nullptr;
+    h->draw_terrain_dev = nullptr;
+    h->draw_vp_dev = h->draw_pos_dev = h->draw_err_dev = nullptr;
+    h->draw_cap = 0;
+    if (hipMalloc((void**)&h->draw_seeds_dev, (size_t)n * 4) != hipSuccess ||
+        hipMalloc((void**)&h->draw_keys_dev, (size_t)n * 624 * 4) != hipSuccess ||
+        hipMalloc((void**)&h->draw_terrain_dev, (size_t)n * T * 3 * 4) != hipSuccess ||
+        hipMalloc((void**)&h->draw_vp_dev, (size_t)n * nv * 2 * 4) != hipSuccess ||
+        hipMalloc((void**)&h->draw_pos_dev, (size_t)n * 4) != hipSuccess ||
+        hipMalloc((void**)&h->draw_err_dev, (size_t)n * 4) != hipSuccess)
+      return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld drawn games)", (long long)n);
+    h->draw_cap = n;
+  }
+  S_HIP(h, hipMemcpyAsync(h->draw_seeds_dev, seeds_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  S_HIP(h, scs_draw_launch(h->draw, h->base_rules_dev, n, h->draw_seeds_dev, h->game_rules_dev, h->rules_key_dev,
+                           h->draw_terrain_dev, h->draw_vp_dev, h->draw_keys_dev, h->draw_pos_dev, h->draw_err_dev, s));
+  // the streams the games go on with: one copy of the states back to the host
+  std::vector<uint32_t> keys((size_t)n * 624);
+  std::vector<int32_t> pos((size_t)n), err((size_t)n);
+  S_HIP(h, hipMemcpyAsync(keys.data(), h->draw_keys_dev, keys.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(pos.data(), h->draw_pos_dev, pos.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(err.data(), h->draw_err_dev, err.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  for (int64_t i = 0; i < n; ++i) {
+    if (err[(size_t)i] == SCS_DRAW_ERR_COST)
+      return sfail(h, NZ_ERR_ARG, "game %lld: a terrain with movement cost < 1", (long long)i);
+    if (err[(size_t)i] != 0)
+      return sfail(h, NZ_ERR_STATE, "game %lld: the map's draws did not settle within the draw kernel's bounds", (long long)i);
+  }
+  h->game_streams.reserve((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    nz_rng* r = nz_rng_create_state(keys.data() + (size_t)i * 624, pos[(size_t)i], 0, 0.0);
+    if (!r) return sfail(h, NZ_ERR_STATE, "game %lld: bad stream position %d", (long long)i, pos[(size_t)i]);
+    h->game_streams.push_back(r);
+  }
+  h->n_drawn = n;
+  return use_game_rows(h, n, stream);
+}
+
+// Copies of the last nz_scs_search_draw_games (host or device pointers; any may be NULL).
+nz_status nz_scs_search_drawn_games(nz_scs_search* h, int64_t* n, float* terrain, int32_t* vp, uint32_t* mt_keys,
+                                    int32_t* mt_pos, void* stream) {
+  if (!h) return NZ_ERR_ARG;
+  if (n) *n = h->n_drawn;
+  if (h->n_drawn == 0) return sfail(h, NZ_ERR_STATE, "the games were not drawn by nz_scs_search_draw_games");
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t N = (size_t)h->n_drawn, T = (size_t)h->host_rules.tiles, nv = (size_t)(h->host_rules.n_vp[0] + h->host_rules.n_vp[1]);
+  S_HIP(h, hipSetDevice(h->device));
+  if (terrain) S_HIP(h, hipMemcpyAsync(terrain, h->draw_terrain_dev, N * T * 3 * 4, hipMemcpyDefault, s));
+  if (vp) S_HIP(h, hipMemcpyAsync(vp, h->draw_vp_dev, N * nv * 2 * 4, hipMemcpyDefault, s));
+  if (mt_keys) S_HIP(h, hipMemcpyAsync(mt_keys, h->draw_keys_dev, N * 624 * 4, hipMemcpyDefault, s));
+  if (mt_pos) S_HIP(h, hipMemcpyAsync(mt_pos, h->draw_pos_dev, N * 4, hipMemcpyDefault, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  return NZ_OK;
 }
 
 // HIP-event timing of the persistent kernel on the stream it runs on.  enable >= 0: switch (1 also zeroes the sums).

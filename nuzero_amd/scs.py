@@ -5,7 +5,9 @@ by SCS_Game.load_game_from_config, SCS_Game.py:1570-1779) with the "Detailed" (o
 victory-point methods; `ScsBatch` runs G independent games on the device: step, legal-move
 mask (possible_actions, :395-484), state image (generate_state, :1348-1505).
 """
+import collections.abc
 import ctypes
+import operator
 from ctypes import byref, c_int32, c_void_p
 
 import numpy as np
@@ -55,6 +57,7 @@ class ScsGameConfig:
             with open(path_or_dict) as f:
                 d = yaml.safe_load(f)
         self.per_game = False
+        self._draw_spec = None
         self.rows, self.cols = int(d["Board_dimensions"]["rows"]), int(d["Board_dimensions"]["columns"])
         self.turns, self.stacking = int(d["Turns"]), int(d["Stacking_limit"])
         mid = self.cols // 2                    # the board's two sides (define_board_sides, :1140-1158)
@@ -141,6 +144,44 @@ class ScsGameConfig:
               self._terrain_by_id[int(i)]["cost"]] for row in rmap for i in row], np.float32)
         v = self.vp if rvps is None else np.array(list(rvps[0]) + list(rvps[1]), np.int32).reshape(-1, 2)
         return t, v
+
+    def map_draw_spec(self):
+        """What a game of a per-game config draws, for the device draw (nz_scs_search_set_map_draw): {"types" float32
+        [n, 3] (attack modifier, defense modifier, cost in the Terrain section's order), "cdf" float64 [n] (numpy's
+        p.cumsum() / its last entry, as legacy choice(p) computes it), "order" (the randomized sections in file order:
+        "Map", "Victory_points"), "number_vp" (p1, p2), "side_cols" ((first, end) of each side's columns)}.  Raises the
+        ValueError the reference would for a bad distribution (numpy validates it), and one where the reference would
+        hang: more victory points than a side has cells."""
+        if not self.per_game:
+            raise ValueError("the config draws no per-game 'Randomized' map or victory points (ScsGameConfig(..., "
+                             "per_game=True) of a config with such a section): there is nothing to draw")
+        if self._draw_spec is not None:
+            return self._draw_spec
+        d, p1_last, p2_first = self._random
+        ids = [int(p["id"]) for p in d["Terrain"].values()]
+        keys = ("attack_modifier", "defense_modifier", "cost")
+        types = np.array([[self._terrain_by_id[i][k] for k in keys] for i in ids], np.float32).reshape(-1, 3)
+        cdf = np.ones((len(ids),), np.float64)
+        order, number_vp, side_cols = [], (0, 0), ((0, p1_last + 1), (p2_first, self.cols))
+        for section, values in d.items():
+            if section == "Map" and values["creation_method"] == "Randomized":
+                dist = values.get("distribution") or [1 / len(ids)] * len(ids)
+                np.random.RandomState(0).choice(len(ids), p=dist)     # numpy's own checks of p (randomized_map's call)
+                cdf = np.asarray(dist, np.float64).cumsum()
+                cdf /= cdf[-1]
+                order.append("Map")
+            elif section == "Victory_points" and values["creation_method"] == "Randomized":
+                number_vp = tuple(int(values["number_vp"][k]) for k in ("p1", "p2"))
+                for side, (first, end) in enumerate(side_cols):
+                    if number_vp[side] > self.rows * max(0, end - first):
+                        raise ValueError(f"player {side + 1}: {number_vp[side]} victory points on a side of "
+                                         f"{self.rows * max(0, end - first)} cells (the reference would redraw forever)")
+                order.append("Victory_points")
+        if len(ids) > 32:
+            raise ValueError(f"{len(ids)} terrain types: the device draw takes at most 32")
+        self._draw_spec = {"types": types, "cdf": cdf, "order": tuple(order), "number_vp": number_vp,
+                           "side_cols": side_cols}
+        return self._draw_spec
 
     def draw_games(self, seeds):
         """`draw_game` for RandomState(seed) of every seed: (terrain [n, tiles, 3], vp [n, k, 2], the streams' states after
@@ -268,6 +309,9 @@ class ScsSelfPlay:
         self._images = torch.empty((G, c.channels, c.rows, c.cols), dtype=torch.float32, device=self.device)
         self._leaf_game = torch.empty((G,), dtype=torch.int32, device=self.device)
         self.evaluations = 0
+        self._game_maps = None
+        self._draw_set = False
+        self._draws = 0             # device draws so far: the lazy maps and streams belong to the last one
 
     def _check(self, st):
         if st != _lib.NZ_OK:
@@ -292,15 +336,69 @@ class ScsSelfPlay:
         self._check(lib.nz_scs_search_status(self._h, c_void_p(s.data_ptr()), self._stream()))
         return s.cpu().numpy()
 
-    def set_games(self, seeds):
+    # set_games' default for per-game configs: the maps drawn on the device (False: by numpy on the host)
+    draw_on_device = True
+
+    def set_games(self, seeds, on_device=None):
         """Per-game maps (configs made with per_game=True): game i = `np.random.seed(seeds[i]); SCS_Game(config)`, its map
-        drawn first and its play going on with the same stream (nz_scs_search_set_games).  Keeps the maps in
-        `self.game_maps` = (terrain [n, tiles, 3], vp [n, k, 2]) for whoever replays the games.  Returns the streams."""
-        terrain, vp, keys, pos, streams = self.cfg.draw_games(seeds)
-        self._check(lib.nz_scs_search_set_games(self._h, len(seeds), c_void_p(terrain.ctypes.data), c_void_p(vp.ctypes.data),
-                                                c_void_p(keys.ctypes.data), c_void_p(pos.ctypes.data)))
-        self.game_maps = (terrain, vp)
-        return streams
+        drawn first and its play going on with the same stream.  on_device (None: `self.draw_on_device`): the library
+        draws the maps from the seeds on the device (nz_scs_search_draw_games); False: numpy draws them on the host
+        (ScsGameConfig.draw_games, nz_scs_search_set_games) -- the same maps, streams and games bit for bit.  A
+        `draw_games` set on the config object itself (maps the caller supplies) always takes the host route.  The maps
+        are in `self.game_maps` = (terrain [n, tiles, 3], vp [n, k, 2]) for whoever replays the games (read back from
+        the device on first use).  Returns the games' numpy RandomStates (after a device draw: built on first use)."""
+        seeds = list(seeds)
+        if on_device is None:
+            on_device = self.draw_on_device and "draw_games" not in vars(self.cfg)
+        if not on_device or not seeds:
+            terrain, vp, keys, pos, streams = self.cfg.draw_games(seeds)
+            self._check(lib.nz_scs_search_set_games(self._h, len(seeds), c_void_p(terrain.ctypes.data),
+                                                    c_void_p(vp.ctypes.data), c_void_p(keys.ctypes.data),
+                                                    c_void_p(pos.ctypes.data)))
+            self.game_maps = (terrain, vp)
+            return streams
+        spec = self.cfg.map_draw_spec()
+        s = _seed_array(seeds)
+        if not self._draw_set:
+            order = [{"Map": _lib.NZ_SCS_DRAW_MAP, "Victory_points": _lib.NZ_SCS_DRAW_VP}[k] for k in spec["order"]]
+            self._draw_keep = (np.ascontiguousarray(spec["types"], np.float32), np.ascontiguousarray(spec["cdf"], np.float64))
+            sd = _lib.ScsMapDraw(n_types=len(spec["types"]), types=self._draw_keep[0].ctypes.data,
+                                 cdf=self._draw_keep[1].ctypes.data, order=(c_int32 * 2)(*(order + [0, 0])[:2]),
+                                 number_vp=(c_int32 * 2)(*spec["number_vp"]),
+                                 side_cols=(c_int32 * 4)(*spec["side_cols"][0], *spec["side_cols"][1]))
+            self._check(lib.nz_scs_search_set_map_draw(self._h, byref(sd)))
+            self._draw_set = True
+        self._game_maps = None
+        self._check(lib.nz_scs_search_draw_games(self._h, len(s), c_void_p(s.ctypes.data), self._stream()))
+        self._draws += 1
+        return _DrawnStreams(self, len(s))
+
+    @property
+    def game_maps(self):
+        if self._game_maps is None and self._draws:
+            self._game_maps = self._drawn(maps=True)
+        return self._game_maps
+
+    @game_maps.setter
+    def game_maps(self, maps):
+        self._game_maps = maps
+
+    def _drawn(self, maps=False, streams=False):
+        """Copies of the last device draw (nz_scs_search_drawn_games): (terrain, vp) and / or (MT19937 keys, positions)."""
+        c, n = self.cfg, ctypes.c_int64(0)
+        self._check(lib.nz_scs_search_drawn_games(self._h, byref(n), None, None, None, None, self._stream()))
+        n = int(n.value)
+        t = np.empty((n, c.rows * c.cols, 3), np.float32) if maps else None
+        v = np.empty((n, len(c.vp), 2), np.int32) if maps else None
+        k = np.empty((n, 624), np.uint32) if streams else None
+        p = np.empty((n,), np.int32) if streams else None
+        ptr = (lambda a: c_void_p(a.ctypes.data) if a is not None else None)
+        self._check(lib.nz_scs_search_drawn_games(self._h, None, ptr(t), ptr(v), ptr(k), ptr(p), self._stream()))
+        return tuple(x for x in (t, v, k, p) if x is not None)
+
+    def drawn_streams(self):
+        """The last device draw's streams as numpy's RandomState.get_state() holds them: keys uint32 [n, 624], pos int32 [n]."""
+        return self._drawn(streams=True)
 
     def play(self, evaluator, seeds, max_moves=None):
         """Reset and play every game to the end (or for `max_moves` decisions); game g draws from
@@ -543,6 +641,39 @@ class ScsSelfPlay:
 
     def export(self):
         return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in self.export_device().items()}
+
+
+def _seed_array(seeds):
+    """uint32 seeds for the device draw; numpy's RandomState(seed) refuses the same ones with the same message."""
+    a = np.asarray(seeds)
+    if a.dtype.kind not in "iu":
+        a = np.array([operator.index(x) for x in seeds], dtype=object)
+    if a.size and (a.min() < 0 or a.max() > 2 ** 32 - 1):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+class _DrawnStreams(collections.abc.Sequence):
+    """Every game's numpy RandomState after a device draw, built (RandomState.set_state) on first use: only the Python
+    evaluator loop play() needs them; the library's own plays take the streams it keeps."""
+
+    def __init__(self, selfplay, n):
+        self._sp, self._n, self._draw, self._rs = selfplay, n, selfplay._draws, None
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, i):
+        if self._rs is None:
+            if self._sp._draws != self._draw:
+                raise RuntimeError("the engine has drawn other games since these streams were handed out")
+            keys, pos = self._sp.drawn_streams()
+            self._rs = []
+            for k, p in zip(keys, pos):
+                rs = np.random.RandomState()
+                rs.set_state(("MT19937", k, int(p), 0, 0.0))
+                self._rs.append(rs)
+        return self._rs[i]
 
 
 def torch_evaluator(model, recurrent_iterations=2, pad_to=None):
