@@ -521,6 +521,36 @@ nz_status nz_scs_search_record(nz_scs_search* h, const int32_t* games_host, int3
 nz_status nz_scs_search_record_read(nz_scs_search* h, int32_t slot, int32_t* count, uint64_t* digests_host,
                                     float* probs_host, float* values_host);
 
+/* ---- evaluation matches between two MCTS agents on SCS, played inside the library -----------------------------------
+ * Tester.Test_using_agents with two MctsAgents that keep their subtrees (Testing/Tester.py:46-121,
+ * Testing/Agents/Generic/MctsAgent.py:28-39), n_games matches at once -- the trainer's "new network against the
+ * previous checkpoint".  a1 / a2: two engines of ONE game description and the same number of games, both training = 0
+ * and keep_subtree = 1, each with its own search config, its own network and its own trees; match g is game slot g of
+ * both.  Agent 1 moves when the game's player index is 1 (as oracle/agents.py play_match restates Tester.py:62-118).
+ * Per-game maps (nz_scs_search_set_games / _draw_games) must be set on BOTH handles and be the same maps: the rows' map
+ * digests are compared and a difference is refused with NZ_ERR_ARG.
+ * Per decision, for all live matches, on the device: both engines search the position (the mover's choose_action, the
+ * opponent's update_subtree) -- each on the persistent route where its network has the per-wavefront form, wave by wave
+ * otherwise, exactly as nz_scs_search_play decides (nz_scs_search_persistent, nz_scs_search_record and
+ * nz_scs_search_cache work per handle as there; nz_scs_search_persist_profile is not summed here) -- agent 2's search on
+ * a stream of its own between a fork and a join event; a hand-over kernel gives each engine's end_move its forced
+ * actions (-1 for the match's mover, the mover's max_action for the opponent) and keeps the match record.  The host
+ * waits once per decision, for the count of live matches and the engines' error flags.
+ * The inference cache stays per handle: the two networks differ, so the two tables are never shared or merged.
+ * max_moves > 0 stops every match after that many decisions (both engines at the same decision).  Synchronises.
+ * Resets both engines; afterwards nz_scs_search_status / _export read either engine as after nz_scs_search_play.
+ * nz_scs_match_result: the round's tally, counted on the device (terminal value +1: player 1 wins, -1: player 2 wins;
+ * unfinished: stopped at max_moves; length_sum / length_max over all matches), and the match record actions_dev
+ * int32 [n_games][M] (M of nz_scs_search_limits; -1 past the end; may be NULL).  Refuses (NZ_ERR_STATE) a round in which
+ * the two engines' own records and the match record disagree anywhere. */
+typedef struct nz_scs_match_tally {
+  int64_t matches, p1_wins, p2_wins, draws, unfinished, length_sum, length_max;
+} nz_scs_match_tally;
+nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
+                            int32_t max_moves, void* stream);
+nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, nz_scs_match_tally* out_host, int32_t* actions_dev,
+                              void* stream);
+
 /* ---- host random streams (numpy legacy RandomState, MT19937) --------------
  * Replaces the reference's use of the global np.random stream
  * (Explorer.py:77-78,89,199,208). */

@@ -8,3 +8,11 @@ Importing a submodule that needs the shared library raises if it has not been
 built (``python -m nuzero_amd.build``); there is no CPU fallback.
 """
 __version__ = "0.1"
+
+
+def __getattr__(name):
+    # the evaluation-match front end, imported on first use (it loads the shared library)
+    if name in ("ScsMatch", "ScsTester"):
+        from . import tester
+        return getattr(tester, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

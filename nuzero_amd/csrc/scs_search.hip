@@ -2013,6 +2013,13 @@ struct nz_scs_search {
   uint32_t *draw_seeds_dev = nullptr, *draw_keys_dev = nullptr;
   float* draw_terrain_dev = nullptr;
   int32_t *draw_vp_dev = nullptr, *draw_pos_dev = nullptr, *draw_err_dev = nullptr;
+  // nz_scs_match_play (kept on agent 1's handle): the opponent's stream and the fork / join events, the forced actions
+  // of both engines' end_move [2][G], the match record [G][max_moves], the tally, the pinned (live, flags) read-back
+  hipStream_t match_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  int32_t *match_forced = nullptr, *match_actions = nullptr, *match_state = nullptr, *match_pinned = nullptr;
+  int64_t* match_tally = nullptr;
+  const nz_scs_search* match_peer = nullptr;    // agent 2 of the last round (compared, never followed)
 };
 
 namespace {
@@ -2183,6 +2190,7 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   h->base_rules_dev = rules;
   p.bias_tab = bias;
   p.sqrt_tab = sq;
+  (void)hipMemset(p.counters, 0, 16 * sizeof(int64_t));      // (the reset leaves the cache's three alone)
   hipLaunchKernelGGL(search_reset_kernel, dim3((n_games + 127) / 128), dim3(128), 0, nullptr, p);
   if (hipDeviceSynchronize() != hipSuccess) { nz_scs_search_destroy(h); return sfail(nullptr, NZ_ERR_HIP, "reset failed"); }
   *out = h;
@@ -2197,6 +2205,9 @@ void nz_scs_search_destroy(nz_scs_search* h) {
   if (h->active_pinned) (void)hipHostFree(h->active_pinned);
   if (h->ev_poll) (void)hipEventDestroy(h->ev_poll);
   if (h->ev_p0) { (void)hipEventDestroy(h->ev_p0); (void)hipEventDestroy(h->ev_p1); }
+  if (h->match_stream) (void)hipStreamDestroy(h->match_stream);
+  if (h->ev_fork) { (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); }
+  if (h->match_pinned) (void)hipHostFree(h->match_pinned);
   {
     const RoundStore& r = h->round;
     void* store[] = {r.action, r.tree_size, r.children, r.child_action, r.child_visit, r.status, r.bias, r.root_value_sum,
@@ -2410,20 +2421,18 @@ nz_status round_store(nz_scs_search* h, int64_t n) {
   return NZ_OK;
 }
 
-// The library's move loop.  n_round == n_games: one game per slot (nz_scs_search_play_moves).  n_round > n_games: a round
-// of n_round games over the engine's slots -- a slot whose game has ended hands its records to the round's store and
-// starts the next game of the round (nz_scs_search_play_round); game i of the round is seeded with seeds_host[i]
-// wherever and whenever it runs, so the round's games do not depend on the number of slots.
-nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_host, int64_t n_round, int32_t max_moves,
-                    void* stream) {
-  if (!h || !net || (h->cfg.training && !seeds_host && h->game_streams.empty())) return sfail(h, NZ_ERR_ARG, "null argument");
-  const bool refill = n_round > h->n_games;
-  if (n_round < h->n_games) return sfail(h, NZ_ERR_ARG, "a round has at least one game per slot (%d)", h->n_games);
-  if (refill && max_moves > 0) return sfail(h, NZ_ERR_ARG, "max_moves applies to one game per slot only");
-  S_HIP(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
+// What a play call settles before its first move: the network fits the game, the move loop's buffers exist, and the
+// route -- persistent where the network has a per-wavefront form -- is chosen (nz_scs_search_play*, nz_scs_match_play).
+struct PlayRoute {
+  bool persist = false;
+  size_t persist_lds = 0;
+  float* net_rows = nullptr;                   // the leaf images go straight into the network's input rows
+  int32_t row_stride = 0;
+};
+
+nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, void* stream) {
   const int G = h->n_games;
-  const int MAX_MOVES = h->p.max_moves, MAXC = h->p.maxc;
+  const int MAXC = h->p.maxc;
   const ScsRules& R = h->host_rules;
   const int A = R.planes * R.tiles;
   int32_t nin = 0, npol = 0, nrows = 0, ncols = 0, nmax = 0;
@@ -2432,10 +2441,7 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
     return sfail(h, NZ_ERR_ARG, "network is %d planes -> %d planes on %dx%d, the game needs %d -> %d on %dx%d", nin, npol,
                  nrows, ncols, R.channels, R.planes, R.rows, R.cols);
   if (nmax < G) return sfail(h, NZ_ERR_ARG, "network max_batch %d < %d games", nmax, G);
-  int32_t* const counters = h->counters_base;
-  float* net_rows = nullptr;                   // the leaf images go straight into the network's input rows
-  int32_t row_stride = 0;
-  if (nz_boardnet_input_rows(net, &net_rows, &row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "bad network handle");
+  if (nz_boardnet_input_rows(net, &route->net_rows, &route->row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "bad network handle");
   if (!h->images) {
     // evaluations: the network's in slots [0, G), cache hits in [G, 2 G) / [2 G, 3 G) by wave parity
     const bool ok = dalloc(h, &h->images, (size_t)G * R.channels * R.tiles) && dalloc(h, &h->probs, (size_t)3 * G * A) &&
@@ -2446,8 +2452,8 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
     if (!ok) return sfail(h, NZ_ERR_HIP, "device allocation failed");
   }
   // the persistent route: the network must have a per-wavefront form
-  bool persist = false;
-  size_t persist_lds = 0;
+  bool& persist = route->persist;
+  size_t& persist_lds = route->persist_lds;
   h->persist_used = 0;
   {
     static const int env_mode = getenv("NZ_SCS_PERSIST") ? atoi(getenv("NZ_SCS_PERSIST")) : -1;       // A/B experiments
@@ -2488,6 +2494,103 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
     }
     h->cache_route = persist ? 2 : 1;
   }
+  return NZ_OK;
+}
+
+// the wave-by-wave route leaves the counter pointers on the last wave's pair
+void play_finish(nz_scs_search* h) {
+  int32_t* const counters = h->counters_base;
+  h->p.leaf_count = counters;
+  h->p.active_count = counters + 1;
+  h->p.hit_count = counters + 2;
+  h->p.clear_counters = nullptr;
+}
+
+// The search of one move for every live game of `h`, enqueued on `s`: begin_move, then the persistent kernel (one
+// launch) or the simulation waves (the host waits for the move's last ones).  end_move is the caller's.
+nz_status search_move(nz_scs_search* h, nz_boardnet* net, const PlayRoute& route, hipStream_t s) {
+  const int G = h->n_games;
+  int32_t* const counters = h->counters_base;
+  hipLaunchKernelGGL(begin_move_kernel, dim3(G), dim3(64), 0, s, h->p, h->noise);
+  h->p.image_row_stride = route.row_stride;
+  S_HIP(h, hipMemsetAsync(counters, 0, 6 * sizeof(int32_t), s));
+  h->p.eval_probs = h->probs;
+  h->p.eval_value = h->value;
+  h->p.c_bits = h->cache_bits;
+  h->p.terminal_budget = 1;                  // measured best (bench_scs.py: 1 -> 308 games/s, 16 -> 259, unbounded -> 226)
+  if (route.persist) {                       // the whole move's search of every game: one launch
+    if (h->persist_profile) {
+      if (!h->ev_p0) { S_HIP(h, hipEventCreate(&h->ev_p0)); S_HIP(h, hipEventCreate(&h->ev_p1)); }
+      S_HIP(h, hipEventRecord(h->ev_p0, s));
+    }
+    const dim3 pgrid((G + PERSIST_GAMES - 1) / PERSIST_GAMES);
+    hipLaunchKernelGGL(h->persist_fn, pgrid, dim3(PERSIST_THREADS), route.persist_lds, s, h->p, h->pq);
+    S_HIP(h, hipGetLastError());
+    ++h->waves;
+    if (h->persist_profile) S_HIP(h, hipEventRecord(h->ev_p1, s));
+    return NZ_OK;
+  }
+  const int sims = h->cfg.mcts_simulations;
+  bool poll_pending = false;
+  if (!h->active_pinned) {
+    S_HIP(h, hipHostMalloc((void**)&h->active_pinned, sizeof(int32_t), hipHostMallocDefault));
+    S_HIP(h, hipEventCreateWithFlags(&h->ev_poll, hipEventDisableTiming));
+  }
+  for (int w = 0;; ++w) {
+    // two (leaf, active) counter pairs: wave w counts into pair w & 1 and zeroes the other one for wave w + 1
+    h->p.leaf_count = counters + 3 * (w & 1);
+    h->p.active_count = h->p.leaf_count + 1;
+    h->p.hit_count = h->p.leaf_count + 2;
+    h->p.clear_counters = counters + 3 * ((w + 1) & 1);
+    h->p.c_wave = ++h->cache_wave;
+    h->p.c_hit_base = G * (1 + (w & 1));
+    hipLaunchKernelGGL(wave_kernel, dim3(G), dim3(64), 0, s, h->p, w ? 3 : 2, h->probs, h->value, route.net_rows, h->leaf_game);
+    ++h->waves;
+    if (w >= sims - 1) {                       // the move's last waves: wait for the count of games still searching
+      int32_t active = 0;
+      S_HIP(h, hipMemcpyAsync(&active, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      S_HIP(h, hipStreamSynchronize(s));
+      if (active == 0) break;
+      if (w > sims + 2) return sfail(h, NZ_ERR_STATE, "internal: a move's searches did not finish in %d waves", w);
+    } else if ((w & 7) == 7) {
+      // every game may have finished early (simulations that end in terminal leaves do not wait for a wave): the count
+      // is copied to pinned memory and looked at eight waves later -- no wait, the GPU is never left without work; the
+      // waves launched in between find nothing to do
+      if (poll_pending && hipEventQuery(h->ev_poll) == hipSuccess) {
+        poll_pending = false;
+        if (*h->active_pinned == 0) break;
+      }
+      if (!poll_pending) {
+        S_HIP(h, hipMemcpyAsync(h->active_pinned, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        S_HIP(h, hipEventRecord(h->ev_poll, s));
+        poll_pending = true;
+      }
+    }
+    if (nz_boardnet_forward_rows(net, G, h->p.leaf_count, nullptr, h->probs, h->value, (void*)s) != NZ_OK)
+      return sfail(h, NZ_ERR_HIP, "network: %s", nz_boardnet_last_error(net));
+    if (h->cache_bits > 0)                   // the leaves the network just evaluated enter the table (KeylessCache.put)
+      hipLaunchKernelGGL(cache_put_kernel, dim3(G), dim3(64), 0, s, h->p, h->p.leaf_count);
+  }
+  if (poll_pending) S_HIP(h, hipEventSynchronize(h->ev_poll));     // (long done: the move's last waves were waited for)
+  return NZ_OK;
+}
+
+// The library's move loop.  n_round == n_games: one game per slot (nz_scs_search_play_moves).  n_round > n_games: a round
+// of n_round games over the engine's slots -- a slot whose game has ended hands its records to the round's store and
+// starts the next game of the round (nz_scs_search_play_round); game i of the round is seeded with seeds_host[i]
+// wherever and whenever it runs, so the round's games do not depend on the number of slots.
+nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_host, int64_t n_round, int32_t max_moves,
+                    void* stream) {
+  if (!h || !net || (h->cfg.training && !seeds_host && h->game_streams.empty())) return sfail(h, NZ_ERR_ARG, "null argument");
+  const bool refill = n_round > h->n_games;
+  if (n_round < h->n_games) return sfail(h, NZ_ERR_ARG, "a round has at least one game per slot (%d)", h->n_games);
+  if (refill && max_moves > 0) return sfail(h, NZ_ERR_ARG, "max_moves applies to one game per slot only");
+  S_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int G = h->n_games;
+  const int MAX_MOVES = h->p.max_moves, MAXC = h->p.maxc;
+  PlayRoute route;
+  if (nz_status pst = play_prepare(h, net, &route, stream)) return pst;
   std::vector<nz_rng*> rngs;
   struct RngGuard {
     std::vector<nz_rng*>& v;
@@ -2603,82 +2706,18 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
       S_HIP(h, hipMemcpyAsync(h->noise, noise.data(), noise.size() * sizeof(double), hipMemcpyHostToDevice, s));
       S_HIP(h, hipMemcpyAsync(h->uniforms, uni.data(), uni.size() * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(begin_move_kernel, dim3(G), dim3(64), 0, s, h->p, h->noise);
-    h->p.image_row_stride = row_stride;
-    S_HIP(h, hipMemsetAsync(counters, 0, 6 * sizeof(int32_t), s));
-    h->p.eval_probs = h->probs;
-    h->p.eval_value = h->value;
-    h->p.c_bits = h->cache_bits;
-    h->p.terminal_budget = 1;                  // measured best (bench_scs.py: 1 -> 308 games/s, 16 -> 259, unbounded -> 226)
-    if (persist) {                               // the whole move's search of every game: one launch
-      if (h->persist_profile) {
-        if (!h->ev_p0) { S_HIP(h, hipEventCreate(&h->ev_p0)); S_HIP(h, hipEventCreate(&h->ev_p1)); }
-        S_HIP(h, hipEventRecord(h->ev_p0, s));
-      }
-      const dim3 pgrid((G + PERSIST_GAMES - 1) / PERSIST_GAMES);
-      hipLaunchKernelGGL(h->persist_fn, pgrid, dim3(PERSIST_THREADS), persist_lds, s, h->p, h->pq);
-      S_HIP(h, hipGetLastError());
-      ++h->waves;
-      if (h->persist_profile) S_HIP(h, hipEventRecord(h->ev_p1, s));
-      st = nz_scs_search_end_move(h, h->uniforms, stream);     // (synchronises)
-      if (st != NZ_OK) return st;
-      if (h->persist_profile) {
-        float ms = 0.f;
-        S_HIP(h, hipEventElapsedTime(&ms, h->ev_p0, h->ev_p1));
-        h->persist_ms += ms;
-        ++h->persist_launches;
-      }
-      continue;
-    }
-    const int sims = h->cfg.mcts_simulations;
-    bool poll_pending = false;
-    if (!h->active_pinned) {
-      S_HIP(h, hipHostMalloc((void**)&h->active_pinned, sizeof(int32_t), hipHostMallocDefault));
-      S_HIP(h, hipEventCreateWithFlags(&h->ev_poll, hipEventDisableTiming));
-    }
-    for (int w = 0;; ++w) {
-      // two (leaf, active) counter pairs: wave w counts into pair w & 1 and zeroes the other one for wave w + 1
-      h->p.leaf_count = counters + 3 * (w & 1);
-      h->p.active_count = h->p.leaf_count + 1;
-      h->p.hit_count = h->p.leaf_count + 2;
-      h->p.clear_counters = counters + 3 * ((w + 1) & 1);
-      h->p.c_wave = ++h->cache_wave;
-      h->p.c_hit_base = G * (1 + (w & 1));
-      hipLaunchKernelGGL(wave_kernel, dim3(G), dim3(64), 0, s, h->p, w ? 3 : 2, h->probs, h->value, net_rows, h->leaf_game);
-      ++h->waves;
-      if (w >= sims - 1) {                       // the move's last waves: wait for the count of games still searching
-        int32_t active = 0;
-        S_HIP(h, hipMemcpyAsync(&active, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        S_HIP(h, hipStreamSynchronize(s));
-        if (active == 0) break;
-        if (w > sims + 2) return sfail(h, NZ_ERR_STATE, "internal: a move's searches did not finish in %d waves", w);
-      } else if ((w & 7) == 7) {
-        // every game may have finished early (simulations that end in terminal leaves do not wait for a wave): the count
-        // is copied to pinned memory and looked at eight waves later -- no wait, the GPU is never left without work; the
-        // waves launched in between find nothing to do
-        if (poll_pending && hipEventQuery(h->ev_poll) == hipSuccess) {
-          poll_pending = false;
-          if (*h->active_pinned == 0) break;
-        }
-        if (!poll_pending) {
-          S_HIP(h, hipMemcpyAsync(h->active_pinned, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-          S_HIP(h, hipEventRecord(h->ev_poll, s));
-          poll_pending = true;
-        }
-      }
-      if (nz_boardnet_forward_rows(net, G, h->p.leaf_count, nullptr, h->probs, h->value, stream) != NZ_OK)
-        return sfail(h, NZ_ERR_HIP, "network: %s", nz_boardnet_last_error(net));
-      if (h->cache_bits > 0)                   // the leaves the network just evaluated enter the table (KeylessCache.put)
-        hipLaunchKernelGGL(cache_put_kernel, dim3(G), dim3(64), 0, s, h->p, h->p.leaf_count);
-    }
-    if (poll_pending) S_HIP(h, hipEventSynchronize(h->ev_poll));     // (long done: the move's last waves were waited for)
-    st = nz_scs_search_end_move(h, h->uniforms, stream);
+    st = search_move(h, net, route, s);
     if (st != NZ_OK) return st;
+    st = nz_scs_search_end_move(h, h->uniforms, stream);     // (synchronises)
+    if (st != NZ_OK) return st;
+    if (route.persist && h->persist_profile) {
+      float ms = 0.f;
+      S_HIP(h, hipEventElapsedTime(&ms, h->ev_p0, h->ev_p1));
+      h->persist_ms += ms;
+      ++h->persist_launches;
+    }
   }
-  h->p.leaf_count = counters;
-  h->p.active_count = counters + 1;
-  h->p.hit_count = counters + 2;
-  h->p.clear_counters = nullptr;
+  play_finish(h);
   if (refill) {
     for (int g = 0; g < G; ++g)
       if (slot_game[g] >= 0) return sfail(h, NZ_ERR_STATE, "internal: the round did not finish in %lld moves", (long long)move_limit);
@@ -2744,7 +2783,10 @@ nz_status nz_scs_search_cache(nz_scs_search* h, int64_t max_entries) {
     if (p.c_id) { (void)hipFree(p.c_id); (void)hipFree(p.c_probs); (void)hipFree(p.c_value); (void)hipFree(p.c_writer); (void)hipFree(p.c_check); }
     p.c_id = nullptr; p.c_probs = nullptr; p.c_value = nullptr; p.c_writer = nullptr; p.c_check = nullptr;
     h->cache_bits = 0; h->cache_entries = 0;
-    if (max_entries == 0) return NZ_OK;
+    if (max_entries == 0) {                    // no table: nz_scs_search_cache_stats reports none, not the last one's
+      S_HIP(h, hipMemset(p.counters + 8, 0, 3 * sizeof(int64_t)));
+      return NZ_OK;
+    }
     int bits = 0;
     while ((2ll << bits) <= max_entries && bits < 30) ++bits;          // closest power of two under max_entries
     if (bits == 0) bits = 1;
@@ -3152,5 +3194,269 @@ extern "C" nz_status nz_scs_search_status(nz_scs_search* h, int32_t* status_dev,
   S_HIP(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(search_status_kernel, dim3((h->n_games + 127) / 128), dim3(128), 0, (hipStream_t)stream, h->p, status_dev);
   S_HIP(h, hipGetLastError());
+  return NZ_OK;
+}
+
+// ---- evaluation matches between two agents (nz_scs_match_play) ---------------------------------------------------------
+// Tester.Test_using_agents with two MctsAgents that keep their subtrees (Testing/Tester.py:62-118,
+// Testing/Agents/Generic/MctsAgent.py:28-39), one match per game slot: two engines hold the same games, each with its
+// own trees, search config and network.  Per decision both search the position; the hand-over kernel tells each
+// engine's end_move_kernel what to play.
+namespace {
+struct MatchSide {                 // what the match kernels read of one engine
+  const ScsState* real;
+  const SNode* nodes;
+  const int8_t* half;
+  const int32_t* root;
+  const int32_t* rec_action;
+  const int32_t* error_flag;
+  int32_t cap, half_cap;
+};
+MatchSide match_side(const SearchParams& p) {
+  return MatchSide{p.real, p.nodes, p.half, p.root, p.rec_action, p.error_flag, p.cap, p.half_cap};
+}
+
+__device__ __forceinline__ bool match_in_step(const ScsState& x, const ScsState& y) {
+  return x.length == y.length && x.player == y.player && x.terminal == y.terminal && x.stage == y.stage &&
+         x.sub_phase == y.sub_phase && x.terminal_value == y.terminal_value;
+}
+
+// max_action (Explorer.py:183-185) of the search that just ended at game g's root: the first maximum of the children's
+// visits, as end_move_kernel picks it; -1 for a root without children (end_move_kernel reports that)
+__device__ __forceinline__ int match_root_choice(const MatchSide& s, int g) {
+  const SNode* nodes = s.nodes + (size_t)g * s.cap + (size_t)s.half[g] * s.half_cap;
+  const SNode root = nodes[s.root[g]];
+  if (root.n_children == 0) return -1;
+  int best = 0;
+  for (int j = 1; j < root.n_children; ++j)
+    if (nodes[root.child_base + j].visit > nodes[root.child_base + best].visit) best = j;
+  return nodes[root.child_base + best].action;
+}
+
+// out3 (zeroed by the host): matches still being played, and the two engines' error flags; bit 64 of the first flag:
+// the engines no longer hold the same game
+__global__ void match_live_kernel(MatchSide a, MatchSide b, int n, int32_t* __restrict__ out3) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = g < n;
+  const bool live = in && !a.real[g].terminal;
+  const bool apart = in && !match_in_step(a.real[g], b.real[g]);
+  const int n_live = __popcll(__ballot(live));
+  const bool any_apart = __ballot(apart) != 0;
+  if ((threadIdx.x & 63) == 0) {
+    if (n_live) atomicAdd(&out3[0], n_live);
+    if (any_apart) atomicOr(&out3[1], 64);
+  }
+  if (g == 0) {
+    atomicOr(&out3[1], *a.error_flag);
+    atomicOr(&out3[2], *b.error_flag);
+  }
+}
+
+// The hand-over of one decision, after both searches: the player to move differs from match to match (SCS turns have
+// phases), so per match the mover's engine gets -1 ("choose yourself": its end_move_kernel takes max_action) and the
+// opponent's engine gets the action the mover will take -- read from the mover's root exactly as end_move_kernel reads
+// it, because one end_move launch per engine serves movers and followers alike (match_tally_kernel holds the two
+// engines' records against each other).  Agent 1 moves for player index 1 (oracle/agents.py play_match).  The action
+// also enters the match record [n][max_moves].
+__global__ void match_handover_kernel(MatchSide a, MatchSide b, int n, int max_moves, int32_t* __restrict__ forced_a,
+                                      int32_t* __restrict__ forced_b, int32_t* __restrict__ actions) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  forced_a[g] = -1;
+  forced_b[g] = -1;
+  const ScsState& st = a.real[g];
+  if (st.terminal) return;
+  const int move = st.length;
+  if (move >= max_moves) return;                         // (end_move_kernel reports it)
+  const bool a_moves = st.player == 1;
+  const int action = a_moves ? match_root_choice(a, g) : match_root_choice(b, g);
+  if (action < 0) return;
+  (a_moves ? forced_b : forced_a)[g] = action;
+  actions[(size_t)g * max_moves + move] = action;
+}
+
+// tally [8] (zeroed by the host): matches, wins of player 1 (terminal value +1), wins of player 2 (-1), draws,
+// unfinished (stopped at max_moves), sum and maximum of the match lengths, and the matches in which the two engines'
+// records or the match record disagree (a result with any of those is refused)
+__global__ void match_tally_kernel(MatchSide a, MatchSide b, int n, int max_moves, const int32_t* __restrict__ actions,
+                                   unsigned long long* __restrict__ tally) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = g < n;
+  int length = 0, value = 0;
+  bool done = false, bad = false;
+  if (in) {
+    const ScsState& st = a.real[g];
+    length = st.length;
+    value = st.terminal_value;
+    done = st.terminal != 0;
+    bad = !match_in_step(st, b.real[g]) || length > max_moves;
+    for (int m = 0; m < length && !bad; ++m) {
+      const size_t at = (size_t)g * max_moves + m;
+      bad = a.rec_action[at] != actions[at] || b.rec_action[at] != actions[at] || actions[at] < 0;
+    }
+  }
+  const int n_in = __popcll(__ballot(in)), n_p1 = __popcll(__ballot(in && done && value > 0)),
+            n_p2 = __popcll(__ballot(in && done && value < 0)), n_draw = __popcll(__ballot(in && done && value == 0)),
+            n_open = __popcll(__ballot(in && !done));
+  if ((threadIdx.x & 63) == 0) {               // one vector atomic per wavefront and category
+    if (n_in) atomicAdd(&tally[0], (unsigned long long)n_in);
+    if (n_p1) atomicAdd(&tally[1], (unsigned long long)n_p1);
+    if (n_p2) atomicAdd(&tally[2], (unsigned long long)n_p2);
+    if (n_draw) atomicAdd(&tally[3], (unsigned long long)n_draw);
+    if (n_open) atomicAdd(&tally[4], (unsigned long long)n_open);
+  }
+  if (in) {
+    atomicAdd(&tally[5], (unsigned long long)length);
+    atomicMax(&tally[6], (unsigned long long)length);
+    if (bad) atomicAdd(&tally[7], 1ull);
+  }
+}
+}  // namespace
+
+extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
+                                       int32_t max_moves, void* stream) {
+  if (!a1 || !a2 || !net1 || !net2) return sfail(a1, NZ_ERR_ARG, "null argument");
+  if (a1 == a2) return sfail(a1, NZ_ERR_ARG, "a match needs two engines: each agent keeps its own trees");
+  a1->match_peer = nullptr;
+  if (a1->cfg.training || a2->cfg.training) return sfail(a1, NZ_ERR_ARG, "evaluation agents are training = 0 engines (MctsAgent.py:14-20)");
+  if (a1->n_games != a2->n_games || a1->device != a2->device)
+    return sfail(a1, NZ_ERR_ARG, "the two engines hold %d and %d games on devices %d and %d", a1->n_games, a2->n_games, a1->device, a2->device);
+  if (memcmp(&a1->host_rules, &a2->host_rules, sizeof(ScsRules)) != 0)
+    return sfail(a1, NZ_ERR_ARG, "the two engines were created with different game descriptions");
+  S_HIP(a1, hipSetDevice(a1->device));
+  hipStream_t s1 = (hipStream_t)stream;
+  const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
+  if (a1->n_game_rows != a2->n_game_rows)
+    return sfail(a1, NZ_ERR_ARG, "per-game maps: %lld set on agent 1, %lld on agent 2", (long long)a1->n_game_rows, (long long)a2->n_game_rows);
+  if (a1->n_game_rows > 0) {                   // every match on its own map: the same one in both engines
+    if (a1->n_game_rows < G) return sfail(a1, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)a1->n_game_rows);
+    std::vector<uint64_t> k1((size_t)G * 2), k2((size_t)G * 2);
+    std::vector<int32_t> ident(G);
+    for (int g = 0; g < G; ++g) ident[g] = g;
+    S_HIP(a1, hipStreamSynchronize(s1));
+    S_HIP(a1, hipMemcpy(k1.data(), a1->rules_key_dev, k1.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    S_HIP(a1, hipMemcpy(k2.data(), a2->rules_key_dev, k2.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int g = 0; g < G; ++g)
+      if (k1[(size_t)g * 2] != k2[(size_t)g * 2] || k1[(size_t)g * 2 + 1] != k2[(size_t)g * 2 + 1])
+        return sfail(a1, NZ_ERR_ARG, "match %d: the two engines hold different maps (digests %016llx%016llx and %016llx%016llx)", g,
+                     (unsigned long long)k1[(size_t)g * 2], (unsigned long long)k1[(size_t)g * 2 + 1],
+                     (unsigned long long)k2[(size_t)g * 2], (unsigned long long)k2[(size_t)g * 2 + 1]);
+    S_HIP(a1, hipMemcpy(a1->rules_row_dev, ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    S_HIP(a1, hipMemcpy(a2->rules_row_dev, ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  // agent 2's failures are reported on agent 1's handle, the one the caller asks
+  auto on2 = [&](nz_status st) {
+    if (st != NZ_OK) a1->error = "agent 2: " + a2->error;
+    return st;
+  };
+  PlayRoute r1, r2;
+  if (nz_status st = play_prepare(a1, net1, &r1, stream)) return st;
+  if (nz_status st = on2(play_prepare(a2, net2, &r2, stream))) return st;
+  if (r1.persist && r2.persist && a1->persist_fn == a2->persist_fn && r1.persist_lds != r2.persist_lds)
+    // one kernel, two networks: the attribute is the kernel's, so it must cover the larger of the two launches
+    S_HIP(a1, hipFuncSetAttribute((const void*)a1->persist_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)std::max(r1.persist_lds, r2.persist_lds)));
+  if (!a1->match_forced) {
+    const bool ok = dalloc(a1, &a1->match_forced, (size_t)2 * G) && dalloc(a1, &a1->match_actions, (size_t)G * MAX_MOVES) &&
+                    dalloc(a1, &a1->match_state, (size_t)3) && dalloc(a1, &a1->match_tally, (size_t)8);
+    if (!ok) return sfail(a1, NZ_ERR_HIP, "device allocation failed");
+    S_HIP(a1, hipHostMalloc((void**)&a1->match_pinned, 3 * sizeof(int32_t), hipHostMallocDefault));
+    S_HIP(a1, hipStreamCreateWithFlags(&a1->match_stream, hipStreamNonBlocking));
+    S_HIP(a1, hipEventCreateWithFlags(&a1->ev_fork, hipEventDisableTiming));
+    S_HIP(a1, hipEventCreateWithFlags(&a1->ev_join, hipEventDisableTiming));
+  }
+  // The two searches of a decision are independent: agent 2's runs on a stream of its own between a fork and a join
+  // event.  One stream when the agents share a network object (the wave-by-wave route evaluates in the network's own
+  // buffers) or for the A/B measurement (NZ_SCS_MATCH_STREAMS=1, scripts/time_scs_match.py).
+  const char* env_streams = getenv("NZ_SCS_MATCH_STREAMS");
+  const bool two_streams = net1 != net2 && !(env_streams && atoi(env_streams) == 1);
+  hipStream_t s2 = two_streams ? a1->match_stream : s1;
+  int32_t* const forced1 = a1->match_forced;
+  int32_t* const forced2 = a1->match_forced + G;
+  if (nz_status st = nz_scs_search_reset(a1, stream)) return st;
+  if (nz_status st = on2(nz_scs_search_reset(a2, stream))) return st;
+  S_HIP(a1, hipMemsetAsync(a1->match_actions, 0xFF, (size_t)G * MAX_MOVES * sizeof(int32_t), s1));    // -1: not played
+  a1->waves = a2->waves = 0;
+  a1->round_games = a2->round_games = 0;
+  const MatchSide m1 = match_side(a1->p), m2 = match_side(a2->p);
+  const dim3 grid1((G + 127) / 128), block1(128);
+  const int move_limit = max_moves > 0 && max_moves < MAX_MOVES ? max_moves : MAX_MOVES;
+  auto state_check = [&](int32_t* live) -> nz_status {   // the decision's one wait: live matches and both engines' flags
+    S_HIP(a1, hipMemsetAsync(a1->match_state, 0, 3 * sizeof(int32_t), s1));
+    hipLaunchKernelGGL(match_live_kernel, grid1, block1, 0, s1, m1, m2, G, a1->match_state);
+    S_HIP(a1, hipMemcpyAsync(a1->match_pinned, a1->match_state, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s1));
+    S_HIP(a1, hipStreamSynchronize(s1));
+    const int32_t f1 = a1->match_pinned[1], f2 = a1->match_pinned[2];
+    if (f1 & 64) return sfail(a1, NZ_ERR_STATE, "internal: the two engines no longer hold the same games");
+    if (f1 || f2)
+      return sfail(a1, NZ_ERR_OVERFLOW, "device check failed (agent 1 flag %d, agent 2 flag %d: 1 arena full, 2 visit table/path too "
+                   "short, 4 move ended before its search, 8 forced action is not legal, 16 more legal actions than the bound "
+                   "computed at create, 32 game longer than that bound)", f1, f2);
+    *live = a1->match_pinned[0];
+    return NZ_OK;
+  };
+  nz_status st = NZ_OK;
+  for (int move = 0; move < move_limit; ++move) {
+    int32_t live = 0;
+    if ((st = state_check(&live)) != NZ_OK) return st;
+    if (live == 0) break;
+    if (two_streams) {
+      S_HIP(a1, hipEventRecord(a1->ev_fork, s1));
+      S_HIP(a1, hipStreamWaitEvent(s2, a1->ev_fork, 0));
+    }
+    // a persistent search is one launch; a wave-by-wave one keeps the host until its last wave: enqueue the former first
+    if (!r1.persist && r2.persist) {
+      st = on2(search_move(a2, net2, r2, s2));
+      if (st == NZ_OK) st = search_move(a1, net1, r1, s1);
+    } else {
+      st = search_move(a1, net1, r1, s1);
+      if (st == NZ_OK) st = on2(search_move(a2, net2, r2, s2));
+    }
+    if (st != NZ_OK) {
+      if (two_streams) (void)hipStreamSynchronize(s2);
+      return st;
+    }
+    if (two_streams) {
+      S_HIP(a1, hipEventRecord(a1->ev_join, s2));
+      S_HIP(a1, hipStreamWaitEvent(s1, a1->ev_join, 0));
+    }
+    hipLaunchKernelGGL(match_handover_kernel, grid1, block1, 0, s1, m1, m2, G, MAX_MOVES, forced1, forced2, a1->match_actions);
+    const dim3 grid_end((G + 63) / 64), block_end(64);
+    hipLaunchKernelGGL(end_move_kernel, grid_end, block_end, 0, s1, a1->p, (const double*)nullptr, (const int32_t*)forced1);
+    hipLaunchKernelGGL(compact_kernel, dim3(G), dim3(64), 0, s1, a1->p);
+    hipLaunchKernelGGL(end_move_kernel, grid_end, block_end, 0, s1, a2->p, (const double*)nullptr, (const int32_t*)forced2);
+    hipLaunchKernelGGL(compact_kernel, dim3(G), dim3(64), 0, s1, a2->p);
+    S_HIP(a1, hipGetLastError());
+  }
+  play_finish(a1);
+  play_finish(a2);
+  int32_t live = 0;
+  if ((st = state_check(&live)) != NZ_OK) return st;     // (the last decision's flags)
+  a1->match_peer = a2;
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, nz_scs_match_tally* out_host,
+                                         int32_t* actions_dev, void* stream) {
+  if (!a1 || !a2) return sfail(a1, NZ_ERR_ARG, "null argument");
+  if (a1->match_peer != a2) return sfail(a1, NZ_ERR_STATE, "no match round was played on these two handles");
+  S_HIP(a1, hipSetDevice(a1->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
+  S_HIP(a1, hipMemsetAsync(a1->match_tally, 0, 8 * sizeof(int64_t), s));
+  hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(a1->p), match_side(a2->p), G, MAX_MOVES,
+                     (const int32_t*)a1->match_actions, (unsigned long long*)a1->match_tally);
+  S_HIP(a1, hipGetLastError());
+  int64_t t[8];
+  S_HIP(a1, hipMemcpyAsync(t, a1->match_tally, sizeof(t), hipMemcpyDeviceToHost, s));
+  if (actions_dev)
+    S_HIP(a1, hipMemcpyAsync(actions_dev, a1->match_actions, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  S_HIP(a1, hipStreamSynchronize(s));
+  if (t[7] != 0)
+    return sfail(a1, NZ_ERR_STATE, "internal: in %lld matches the two engines' records and the match record disagree", (long long)t[7]);
+  if (out_host) {
+    out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
+    out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
+  }
   return NZ_OK;
 }
