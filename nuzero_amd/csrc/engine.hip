@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "hip_own.hpp"
 
 using namespace nz;
 
@@ -19,8 +20,22 @@ namespace {
 thread_local std::string g_create_error;
 
 struct ProfileSpan {
-  hipEvent_t a, b;
-  int cls;
+  Event a, b;
+  int cls = 0;
+};
+
+// The device arrays made by nz_engine_create, one owner each: TreeParams and the launches borrow their pointers.
+struct EngineArrays {
+  DevBuf<TNode> nodes;
+  DevBuf<uint32_t> board, leaf_board, leaf_boards, hist_board;
+  DevBuf<int32_t> next_game, length, alive, outcome, root, node_count, sims_left, pending, path, path_len, sim_count, exp_count,
+      sel_nodes, sel_children, new_nodes, n_root_children, desync, leaf_count, error_flag, hist_action, hist_visits,
+      hist_tree_size, hist_children;
+  DevBuf<float> leaf_logits, leaf_value;
+  DevBuf<double> bias_tab, sqrt_tab, hist_bias, hist_prior, hist_value_sum, hist_root_value_sum;
+  DevBuf<double> noise, uniforms, game_noise, game_uniforms;   // one move's randomness [G][A], [G][3]; a whole game's [G][T]...
+  DevBuf<unsigned long long> stamps;          // [blocks][4], diagnostic build only
+  DevBuf<NetProgram> prog;
 };
 }  // namespace
 
@@ -33,43 +48,29 @@ struct nz_engine {
   int cap = 0;
   int tab_len = 0;
   TreeParams tp;
-  std::vector<void*> allocs;
+  EngineArrays dev;
   std::string error;
   // network
   bool have_net = false, have_table = false;
   nz_net_desc net;
   int iters = 0;
   NetProgram prog_host;
-  NetProgram* prog_dev = nullptr;
-  float* weights_dev = nullptr;
-  float* table_dev = nullptr;
-  float* leaf_logits = nullptr;
-  float* leaf_value = nullptr;
+  DevBuf<float> weights_dev, table_dev;
+  const float* borrowed_weights = nullptr;    // fallback engine: the parent's packed weights, used instead of weights_dev
   double executed_bf16_flops_per_position = 0.0, executed_f32_flops_per_position = 0.0;
   double algorithmic_flops_per_position = 0.0;
   // host staging for nz_engine_play
-  int32_t* h_children = nullptr;   // pinned [G]
-  int32_t* h_alive = nullptr;      // pinned [G]
-  double* h_noise = nullptr;       // pinned [G][A]
-  double* h_uniforms = nullptr;    // pinned [G][3]
-  double* d_noise = nullptr;
-  double* d_uniforms = nullptr;
+  PinnedBuf<int32_t> h_children, h_alive, h_desync;   // [G]
+  PinnedBuf<double> h_noise, h_uniforms;    // [G][A], [G][3]
   std::vector<nz_rng*> rngs;
   // persistent-kernel path: whole-game randomness, [G][T][A] and [G][T][3]
-  double* h_game_noise = nullptr;     // pinned
-  double* h_game_uniforms = nullptr;  // pinned
-  double* d_game_noise = nullptr;
-  double* d_game_uniforms = nullptr;
-  int32_t* h_desync = nullptr;        // pinned [G]
+  PinnedBuf<double> h_game_noise, h_game_uniforms;
   // randomness of the NEXT round, drawn on host threads while this round's kernel runs (nz_engine_play_next)
-  double* h_next_noise = nullptr;     // pinned [G][T][A]
-  double* h_next_uniforms = nullptr;  // pinned [G][T][3]
+  PinnedBuf<double> h_next_noise, h_next_uniforms;   // [G][T][A], [G][T][3]
   bool next_ready = false;
   uint64_t next_seed = 0;
-  bool borrowed_net = false;          // fallback engine: network buffers belong to the parent
   nz_engine* fallback = nullptr;
   int64_t desync_total = 0;
-  unsigned long long* d_stamps = nullptr;   // [blocks][4], diagnostic build only
   bool stamps = false;
   // profiling
   bool profile = false;
@@ -97,14 +98,7 @@ nz_status fail(nz_engine* e, nz_status code, const char* fmt, ...) {
       return fail((e), NZ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
   } while (0)
 
-template <typename T>
-nz_status dev_alloc(nz_engine* e, T** out, size_t count) {
-  void* p = nullptr;
-  NZ_HIP(e, hipMalloc(&p, count * sizeof(T)));
-  e->allocs.push_back(p);
-  *out = static_cast<T*>(p);
-  return NZ_OK;
-}
+const float* net_weights(const nz_engine* e) { return e->borrowed_weights ? e->borrowed_weights : e->weights_dev.get(); }
 
 struct Span {
   nz_engine* e;
@@ -114,13 +108,13 @@ struct Span {
   Span(nz_engine* e_, hipStream_t s_, int cls) : e(e_), s(s_), on(e_->profile) {
     if (!on) return;
     sp.cls = cls;
-    if (hipEventCreate(&sp.a) != hipSuccess || hipEventCreate(&sp.b) != hipSuccess) { on = false; return; }
-    (void)hipEventRecord(sp.a, s);
+    if (!sp.a.create() || !sp.b.create()) { on = false; return; }
+    (void)hipEventRecord(sp.a.get(), s);
   }
   ~Span() {
     if (!on) return;
-    (void)hipEventRecord(sp.b, s);
-    e->spans.push_back(sp);
+    (void)hipEventRecord(sp.b.get(), s);
+    e->spans.push_back(std::move(sp));
   }
 };
 
@@ -345,7 +339,6 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   // every expansion at move m adds at most 9 - m children: 1 + sims * (9 + 8 + ... + 1)
   e->cap = 1 + cfg->mcts_simulations * 45;
   e->tab_len = cfg->mcts_simulations * TTT_MAX_MOVES + 2;
-  nz_status st = NZ_OK;
   auto bail = [&](nz_status s) {
     g_create_error = e->error;
     nz_engine_destroy(e);
@@ -356,27 +349,26 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   TreeParams& p = e->tp;
   memset(&p, 0, sizeof(p));
   const size_t G = n_games, N = (size_t)n_slots * (size_t)e->cap, GT = G * TTT_MAX_MOVES, GTA = GT * TTT_ACTIONS;
-#define A(ptr, n)                                        \
-  if ((st = dev_alloc(e, &(ptr), (n))) != NZ_OK) return bail(st)
-  A(p.nodes, N);
-  A(p.board, G); A(p.length, G); A(p.alive, G); A(p.outcome, G); A(p.root, G); A(p.node_count, G);
-  A(p.sims_left, G); A(p.pending, G); A(p.leaf_board, G); A(p.path, G * MAX_PATH); A(p.path_len, G);
-  A(p.sim_count, G); A(p.exp_count, G); A(p.sel_nodes, G); A(p.sel_children, G); A(p.new_nodes, G); A(p.desync, G); A(p.n_root_children, G);
-  A(p.leaf_count, 2); A(p.leaf_boards, G); A(e->leaf_logits, G * TTT_ACTIONS); A(e->leaf_value, G);
-  A(p.error_flag, 1);
-  A(p.hist_board, GT); A(p.hist_action, GT); A(p.hist_visits, GTA); A(p.hist_tree_size, GT);
-  A(p.hist_children, GT); A(p.hist_bias, GT); A(p.hist_prior, GTA); A(p.hist_value_sum, GTA);
-  A(p.hist_root_value_sum, GT);
-  double *bias_tab = nullptr, *sqrt_tab = nullptr;
-  A(bias_tab, e->tab_len); A(sqrt_tab, e->tab_len);
-  A(e->d_noise, G * TTT_ACTIONS); A(e->d_uniforms, G * 3);
-  A(e->d_game_noise, GTA); A(e->d_game_uniforms, GT * 3);
-  A(e->d_stamps, (size_t)n_slots * 6);                 // (one workgroup per slot at most)
-  A(p.next_game, 1);
-  A(e->prog_dev, 1);
-#undef A
-  p.leaf_logits = e->leaf_logits;
-  p.leaf_value = e->leaf_value;
+#define P(f, n)                                                                           \
+  if (!e->dev.f.ensure(n)) return bail(fail(e, NZ_ERR_HIP, "device allocation failed")); \
+  p.f = e->dev.f.get()
+  P(nodes, N);
+  P(board, G); P(length, G); P(alive, G); P(outcome, G); P(root, G); P(node_count, G);
+  P(sims_left, G); P(pending, G); P(leaf_board, G); P(path, G * MAX_PATH); P(path_len, G);
+  P(sim_count, G); P(exp_count, G); P(sel_nodes, G); P(sel_children, G); P(new_nodes, G); P(desync, G); P(n_root_children, G);
+  P(leaf_count, 2); P(leaf_boards, G); P(leaf_logits, G * TTT_ACTIONS); P(leaf_value, G);
+  P(error_flag, 1);
+  P(hist_board, GT); P(hist_action, GT); P(hist_visits, GTA); P(hist_tree_size, GT);
+  P(hist_children, GT); P(hist_bias, GT); P(hist_prior, GTA); P(hist_value_sum, GTA);
+  P(hist_root_value_sum, GT);
+  P(bias_tab, e->tab_len); P(sqrt_tab, e->tab_len);
+  P(next_game, 1);
+#undef P
+  EngineArrays& d = e->dev;
+  if (!d.noise.ensure(G * TTT_ACTIONS) || !d.uniforms.ensure(G * 3) || !d.game_noise.ensure(GTA) ||
+      !d.game_uniforms.ensure(GT * 3) || !d.stamps.ensure((size_t)n_slots * 6) ||      // (one workgroup per slot at most)
+      !d.prog.ensure(1))
+    return bail(fail(e, NZ_ERR_HIP, "device allocation failed"));
   p.cap = e->cap;
   p.n_games = n_games;
   p.n_slots = n_slots;
@@ -418,28 +410,16 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
     hb[n] = std::log(((double)n + cfg->pb_c_base + 1.0) / cfg->pb_c_base) + cfg->pb_c_init;
     hs[n] = std::sqrt((double)n);
   }
-  if (hipMemcpy(bias_tab, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(sqrt_tab, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+  if (hipMemcpy(d.bias_tab.get(), hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d.sqrt_tab.get(), hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
     return bail(fail(e, NZ_ERR_HIP, "table upload failed"));
-  p.bias_tab = bias_tab;
-  p.sqrt_tab = sqrt_tab;
 
-  if (hipHostMalloc((void**)&e->h_children, G * sizeof(int32_t)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_alive, G * sizeof(int32_t)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_noise, G * TTT_ACTIONS * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_uniforms, G * 3 * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_game_noise, GTA * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_game_uniforms, GT * 3 * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_next_noise, GTA * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_next_uniforms, GT * 3 * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_desync, G * sizeof(int32_t)) != hipSuccess)
+  if (!e->h_children.ensure(G) || !e->h_alive.ensure(G) || !e->h_noise.ensure(G * TTT_ACTIONS) || !e->h_uniforms.ensure(G * 3) ||
+      !e->h_game_noise.ensure(GTA) || !e->h_game_uniforms.ensure(GT * 3) || !e->h_next_noise.ensure(GTA) ||
+      !e->h_next_uniforms.ensure(GT * 3) || !e->h_desync.ensure(G))
     return bail(fail(e, NZ_ERR_HIP, "pinned host allocation failed"));
-  memset(e->h_noise, 0, G * TTT_ACTIONS * sizeof(double));
-  memset(e->h_uniforms, 0, G * 3 * sizeof(double));
-  memset(e->h_game_noise, 0, GTA * sizeof(double));
-  memset(e->h_game_uniforms, 0, GT * 3 * sizeof(double));
-  memset(e->h_next_noise, 0, GTA * sizeof(double));
-  memset(e->h_next_uniforms, 0, GT * 3 * sizeof(double));
+  for (PinnedBuf<double>* b : {&e->h_noise, &e->h_uniforms, &e->h_game_noise, &e->h_game_uniforms, &e->h_next_noise, &e->h_next_uniforms})
+    memset(b->get(), 0, b->size() * sizeof(double));
 
   launch_reset(p, nullptr);
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, NZ_ERR_HIP, "reset kernel failed"));
@@ -451,24 +431,8 @@ void nz_engine_destroy(nz_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
-  for (void* p : e->allocs) (void)hipFree(p);
   if (e->fallback) nz_engine_destroy(e->fallback);
-  if (e->weights_dev && !e->borrowed_net) (void)hipFree(e->weights_dev);
-  if (e->table_dev && !e->borrowed_net) (void)hipFree(e->table_dev);
-  if (e->h_game_noise) (void)hipHostFree(e->h_game_noise);
-  if (e->h_game_uniforms) (void)hipHostFree(e->h_game_uniforms);
-  if (e->h_desync) (void)hipHostFree(e->h_desync);
-  if (e->h_next_noise) (void)hipHostFree(e->h_next_noise);
-  if (e->h_next_uniforms) (void)hipHostFree(e->h_next_uniforms);
-  if (e->h_children) (void)hipHostFree(e->h_children);
-  if (e->h_alive) (void)hipHostFree(e->h_alive);
-  if (e->h_noise) (void)hipHostFree(e->h_noise);
-  if (e->h_uniforms) (void)hipHostFree(e->h_uniforms);
   for (nz_rng* r : e->rngs) nz_rng_destroy(r);
-  for (auto& sp : e->spans) {
-    (void)hipEventDestroy(sp.a);
-    (void)hipEventDestroy(sp.b);
-  }
   delete e;
 }
 
@@ -605,10 +569,9 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
     e->executed_f32_flops_per_position = f32 / 16.0;
   }
 
-  if (e->weights_dev) { (void)hipFree(e->weights_dev); e->weights_dev = nullptr; }
-  NZ_HIP(e, hipMalloc((void**)&e->weights_dev, packed.size() * sizeof(float)));
-  NZ_HIP(e, hipMemcpy(e->weights_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  NZ_HIP(e, hipMemcpy(e->prog_dev, &pg, sizeof(pg), hipMemcpyHostToDevice));
+  if (!e->weights_dev.ensure(packed.size())) return fail(e, NZ_ERR_HIP, "device allocation failed (%zu packed weights)", packed.size());
+  NZ_HIP(e, hipMemcpy(e->weights_dev.get(), packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+  NZ_HIP(e, hipMemcpy(e->dev.prog.get(), &pg, sizeof(pg), hipMemcpyHostToDevice));
   e->net = *net;
   e->iters = recurrent_iterations;
   e->have_net = true;
@@ -621,9 +584,9 @@ nz_status nz_engine_set_table(nz_engine* e, const float* table, int32_t n_rows) 
   if (!e || !table) return NZ_ERR_ARG;
   if (n_rows != TTT_TABLE_ROWS) return fail(e, NZ_ERR_ARG, "table must have %d rows", TTT_TABLE_ROWS);
   NZ_HIP(e, hipSetDevice(e->device));
-  if (!e->table_dev) NZ_HIP(e, hipMalloc((void**)&e->table_dev, (size_t)TTT_TABLE_ROWS * 10 * sizeof(float)));
-  NZ_HIP(e, hipMemcpy(e->table_dev, table, (size_t)TTT_TABLE_ROWS * 10 * sizeof(float), hipMemcpyDefault));
-  e->tp.table = e->table_dev;
+  if (!e->table_dev.ensure((size_t)TTT_TABLE_ROWS * 10)) return fail(e, NZ_ERR_HIP, "device allocation failed (table)");
+  NZ_HIP(e, hipMemcpy(e->table_dev.get(), table, (size_t)TTT_TABLE_ROWS * 10 * sizeof(float), hipMemcpyDefault));
+  e->tp.table = e->table_dev.get();
   e->have_table = true;
   return NZ_OK;
 }
@@ -672,8 +635,8 @@ static nz_status search_lockstep(nz_engine* e, const double* noise_dev, hipStrea
       if (it == sims) break;
       {
         Span sp(e, s, 1);
-        launch_net(e->prog_dev, 0, e->weights_dev, p.leaf_boards, nullptr,
-                   p.leaf_count + (it & 1), e->n_games, e->leaf_logits, e->leaf_value, nullptr, nullptr, s);
+        launch_net(e->dev.prog.get(), 0, net_weights(e), p.leaf_boards, nullptr,
+                   p.leaf_count + (it & 1), e->n_games, e->dev.leaf_logits.get(), e->dev.leaf_value.get(), nullptr, nullptr, s);
       }
     }
   }
@@ -741,7 +704,7 @@ nz_status nz_engine_last_actions(nz_engine* e, int32_t* actions_dev, void* strea
 nz_status nz_engine_live_games(nz_engine* e, int32_t* n_live_host, void* stream) {
   if (!e || !n_live_host) return NZ_ERR_ARG;
   hipStream_t s = as_stream(stream);
-  NZ_HIP(e, hipMemcpyAsync(e->h_alive, e->tp.alive, e->n_games * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  NZ_HIP(e, hipMemcpyAsync(e->h_alive.get(), e->tp.alive, e->n_games * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   NZ_HIP(e, hipStreamSynchronize(s));
   int n = 0;
   for (int g = 0; g < e->n_games; ++g) n += e->h_alive[g] != 0;
@@ -791,8 +754,8 @@ static nz_status play_lockstep(nz_engine* e, const uint32_t* seeds, void* stream
   nz_status st = nz_engine_reset(e, stream);
   if (st != NZ_OK) return st;
   for (int move = 0; move < TTT_MAX_MOVES; ++move) {
-    NZ_HIP(e, hipMemcpyAsync(e->h_children, e->tp.n_root_children, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    NZ_HIP(e, hipMemcpyAsync(e->h_alive, e->tp.alive, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    NZ_HIP(e, hipMemcpyAsync(e->h_children.get(), e->tp.n_root_children, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    NZ_HIP(e, hipMemcpyAsync(e->h_alive.get(), e->tp.alive, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     NZ_HIP(e, hipStreamSynchronize(s));
     int live = 0;
     for (int g = 0; g < G; ++g) live += e->h_alive[g] != 0;
@@ -800,11 +763,11 @@ static nz_status play_lockstep(nz_engine* e, const uint32_t* seeds, void* stream
     if (c.training) {
       for (int g = 0; g < G; ++g)
         if (e->h_alive[g])
-          draw_move(e->rngs[g], c, move, e->h_children[g], e->h_noise + (size_t)g * TTT_ACTIONS, e->h_uniforms + g * 3);
-      NZ_HIP(e, hipMemcpyAsync(e->d_noise, e->h_noise, (size_t)G * TTT_ACTIONS * sizeof(double), hipMemcpyHostToDevice, s));
-      NZ_HIP(e, hipMemcpyAsync(e->d_uniforms, e->h_uniforms, (size_t)G * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+          draw_move(e->rngs[g], c, move, e->h_children[g], e->h_noise.get() + (size_t)g * TTT_ACTIONS, e->h_uniforms.get() + g * 3);
+      NZ_HIP(e, hipMemcpyAsync(e->dev.noise.get(), e->h_noise.get(), (size_t)G * TTT_ACTIONS * sizeof(double), hipMemcpyHostToDevice, s));
+      NZ_HIP(e, hipMemcpyAsync(e->dev.uniforms.get(), e->h_uniforms.get(), (size_t)G * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    st = nz_engine_move(e, e->d_noise, e->d_uniforms, stream);
+    st = nz_engine_move(e, e->dev.noise.get(), e->dev.uniforms.get(), stream);
     if (st != NZ_OK) return st;
   }
   return check_device_flag(e, s);
@@ -832,17 +795,15 @@ static nz_status replay_desynced(nz_engine* e, const std::vector<int>& games, ui
     nz_engine* f = nullptr;
     nz_status st = nz_engine_create(&f, &e->cfg, &e->game, std::max(n, 16), e->device);
     if (st != NZ_OK) return fail(e, st, "fallback engine: %s", nz_last_error(nullptr));
-    f->borrowed_net = true;
     e->fallback = f;
   }
   nz_engine* f = e->fallback;
-  f->weights_dev = e->weights_dev;
-  f->table_dev = e->table_dev;
+  f->borrowed_weights = e->weights_dev.get();
   f->tp.table = e->tp.table;
   f->have_net = e->have_net;
   f->have_table = e->have_table;
   f->prog_host = e->prog_host;
-  NZ_HIP(e, hipMemcpy(f->prog_dev, &e->prog_host, sizeof(NetProgram), hipMemcpyHostToDevice));
+  NZ_HIP(e, hipMemcpy(f->dev.prog.get(), &e->prog_host, sizeof(NetProgram), hipMemcpyHostToDevice));
   std::vector<uint32_t> seeds(f->n_games, 0u);
   for (int i = 0; i < n; ++i) seeds[i] = (uint32_t)((base_seed + (uint64_t)games[i]) & 0xffffffffu);
   nz_status st = play_lockstep(f, seeds.data(), stream);
@@ -910,28 +871,28 @@ nz_status nz_engine_play_next(nz_engine* e, uint64_t base_seed, int32_t have_nex
       std::swap(e->h_game_noise, e->h_next_noise);
       std::swap(e->h_game_uniforms, e->h_next_uniforms);
     } else {
-      draw_round(e, base_seed, e->h_game_noise, e->h_game_uniforms);
+      draw_round(e, base_seed, e->h_game_noise.get(), e->h_game_uniforms.get());
     }
     e->next_ready = false;
-    NZ_HIP(e, hipMemcpyAsync(e->d_game_noise, e->h_game_noise, GT * TTT_ACTIONS * sizeof(double), hipMemcpyHostToDevice, s));
-    NZ_HIP(e, hipMemcpyAsync(e->d_game_uniforms, e->h_game_uniforms, GT * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    NZ_HIP(e, hipMemcpyAsync(e->dev.game_noise.get(), e->h_game_noise.get(), GT * TTT_ACTIONS * sizeof(double), hipMemcpyHostToDevice, s));
+    NZ_HIP(e, hipMemcpyAsync(e->dev.game_uniforms.get(), e->h_game_uniforms.get(), GT * 3 * sizeof(double), hipMemcpyHostToDevice, s));
   }
   {
     Span sp(e, s, 0);
-    launch_selfplay(e->tp, e->prog_dev, 0, e->weights_dev,
-                    c.training ? e->d_game_noise : nullptr, c.training ? e->d_game_uniforms : nullptr,
-                    e->stamps ? e->d_stamps : nullptr, s);
+    launch_selfplay(e->tp, e->dev.prog.get(), 0, net_weights(e),
+                    c.training ? e->dev.game_noise.get() : nullptr, c.training ? e->dev.game_uniforms.get() : nullptr,
+                    e->stamps ? e->dev.stamps.get() : nullptr, s);
   }
   NZ_HIP(e, hipGetLastError());
   if (c.training && have_next) {                            // the next round's draws, while the kernel runs
-    draw_round(e, next_base_seed, e->h_next_noise, e->h_next_uniforms);
+    draw_round(e, next_base_seed, e->h_next_noise.get(), e->h_next_uniforms.get());
     e->next_ready = true;
     e->next_seed = next_base_seed;
   }
   st = check_device_flag(e, s);
   if (st != NZ_OK) return st;
   if (c.training) {
-    NZ_HIP(e, hipMemcpyAsync(e->h_desync, e->tp.desync, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    NZ_HIP(e, hipMemcpyAsync(e->h_desync.get(), e->tp.desync, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     NZ_HIP(e, hipStreamSynchronize(s));
     std::vector<int> bad;
     for (int g = 0; g < G; ++g)
@@ -952,7 +913,7 @@ nz_status nz_engine_phase_stamps(nz_engine* e, int32_t enable, double* out4_host
     std::vector<unsigned long long> h((size_t)blocks * 6);
     NZ_HIP(e, hipSetDevice(e->device));
     NZ_HIP(e, hipDeviceSynchronize());
-    NZ_HIP(e, hipMemcpy(h.data(), e->d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    NZ_HIP(e, hipMemcpy(h.data(), e->dev.stamps.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     double sum[4] = {0, 0, 0, 0};
     double max_total = 0;
     for (int b = 0; b < blocks; ++b) {
@@ -1071,7 +1032,7 @@ nz_status nz_net_forward(nz_engine* e, const float* states_dev, int32_t batch, f
   if (batch <= 0) return NZ_OK;
   NZ_HIP(e, hipSetDevice(e->device));
   Span sp(e, as_stream(stream), 1);
-  launch_net(e->prog_dev, 0, e->weights_dev, nullptr, states_dev, nullptr, batch, logits_dev,
+  launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, states_dev, nullptr, batch, logits_dev,
              value_dev, probs_dev, nullptr, as_stream(stream));
   NZ_HIP(e, hipGetLastError());
   return NZ_OK;
@@ -1083,13 +1044,12 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
   if (!e->have_net) return fail(e, NZ_ERR_STATE, "no network: call nz_engine_set_weights first");
   NZ_HIP(e, hipSetDevice(e->device));
   const int blocks = (batch + 15) / 16;
-  unsigned long long* d = nullptr;
-  NZ_HIP(e, hipMalloc((void**)&d, (size_t)blocks * 4 * sizeof(unsigned long long)));
-  launch_net(e->prog_dev, 0, e->weights_dev, nullptr, states_dev, nullptr, batch, logits_dev, value_dev, nullptr, d,
+  DevBuf<unsigned long long> stamps;
+  if (!stamps.ensure((size_t)blocks * 4)) return fail(e, NZ_ERR_HIP, "device allocation failed");
+  launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, states_dev, nullptr, batch, logits_dev, value_dev, nullptr, stamps.get(),
              nullptr);
   std::vector<unsigned long long> h((size_t)blocks * 4);
-  hipError_t err = hipMemcpy(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  hipError_t err = hipMemcpy(h.data(), stamps.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   if (err != hipSuccess) return fail(e, NZ_ERR_HIP, "stamp read-back failed: %s", hipGetErrorString(err));
   for (int i = 0; i < 4; ++i) {
     double sum = 0;
@@ -1101,10 +1061,6 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
 
 nz_status nz_engine_profile(nz_engine* e, int32_t enable) {
   if (!e) return NZ_ERR_ARG;
-  for (auto& sp : e->spans) {
-    (void)hipEventDestroy(sp.a);
-    (void)hipEventDestroy(sp.b);
-  }
   e->spans.clear();
   e->profile = enable != 0;
   return NZ_OK;
@@ -1118,7 +1074,7 @@ nz_status nz_engine_profile_read(nz_engine* e, double* ms_host, int64_t* launche
   int64_t n[3] = {0, 0, 0};
   for (auto& sp : e->spans) {
     float t = 0.f;
-    NZ_HIP(e, hipEventElapsedTime(&t, sp.a, sp.b));
+    NZ_HIP(e, hipEventElapsedTime(&t, sp.a.get(), sp.b.get()));
     ms[sp.cls] += t;
     n[sp.cls] += 1;
   }

@@ -19,15 +19,16 @@
 #include <string>
 
 #include "../../include/nuzero_amd.h"
+#include "hip_own.hpp"
 
 struct nz_replay {
   int device = 0;
   int64_t capacity = 0;
   int32_t state_floats = 0, num_actions = 0;
-  float* states = nullptr;      // [capacity][state_floats]
-  float* policies = nullptr;    // [capacity][num_actions]
-  float* values = nullptr;      // [capacity]
-  int32_t* game_index = nullptr;
+  nz::DevBuf<float> states;      // [capacity][state_floats]
+  nz::DevBuf<float> policies;    // [capacity][num_actions]
+  nz::DevBuf<float> values;      // [capacity] (+ 1)
+  nz::DevBuf<int32_t> game_index;  // [capacity] and the kernels' error flag
   std::string error;
 };
 
@@ -162,15 +163,13 @@ nz_status nz_replay_create(nz_replay** out, int64_t capacity, int32_t state_floa
   nz_replay* h = new nz_replay;
   h->device = device; h->capacity = capacity; h->state_floats = state_floats; h->num_actions = num_actions;
   const size_t n = (size_t)capacity;
-  if (hipMalloc((void**)&h->states, n * state_floats * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->policies, n * num_actions * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->values, (n + 1) * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->game_index, (n + 1) * sizeof(int32_t)) != hipSuccess) {
+  if (!h->states.ensure(n * state_floats) || !h->policies.ensure(n * num_actions) || !h->values.ensure(n + 1) ||
+      !h->game_index.ensure(n + 1)) {
     nz_replay_destroy(h);
     return rfail(nullptr, NZ_ERR_HIP, "device allocation failed (%lld positions)", (long long)capacity);
   }
   // the word after the last game index is the kernels' error flag
-  if (hipMemset(h->game_index + n, 0, sizeof(int32_t)) != hipSuccess) {
+  if (hipMemset(h->game_index.get() + n, 0, sizeof(int32_t)) != hipSuccess) {
     nz_replay_destroy(h);
     return rfail(nullptr, NZ_ERR_HIP, "memset failed");
   }
@@ -182,7 +181,6 @@ void nz_replay_destroy(nz_replay* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  (void)hipFree(h->states); (void)hipFree(h->policies); (void)hipFree(h->values); (void)hipFree(h->game_index);
   delete h;
 }
 
@@ -198,9 +196,9 @@ nz_status nz_replay_append(nz_replay* h, const float* states_dev, const int32_t*
   if (rows_per_game <= 0) return rfail(h, NZ_ERR_ARG, "rows_per_game must be positive");
   if (n_rows <= 0) return NZ_OK;
   R_HIP(h, hipSetDevice(h->device));
-  AppendArgs a{h->states, h->policies, h->values, h->game_index, states_dev, visits_dev, policies_dev, child_action_dev,
+  AppendArgs a{h->states.get(), h->policies.get(), h->values.get(), h->game_index.get(), states_dev, visits_dev, policies_dev, child_action_dev,
                child_visit_dev, n_children_dev, game_value_dev, dst_slot_dev, h->state_floats, h->num_actions, max_children,
-               rows_per_game, game_index, h->capacity, h->game_index + h->capacity};
+               rows_per_game, game_index, h->capacity, h->game_index.get() + h->capacity};
   hipLaunchKernelGGL(append_kernel, dim3((unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, a);
   R_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -211,8 +209,8 @@ nz_status nz_replay_gather(nz_replay* h, const int64_t* slots_dev, int64_t batch
   if (!h || !slots_dev) return NZ_ERR_ARG;
   if (batch <= 0) return NZ_OK;
   R_HIP(h, hipSetDevice(h->device));
-  GatherArgs a{h->states, h->policies, h->values, h->game_index, slots_dev, states_out, policies_out, values_out,
-               game_index_out, h->state_floats, h->num_actions, h->capacity, h->game_index + h->capacity};
+  GatherArgs a{h->states.get(), h->policies.get(), h->values.get(), h->game_index.get(), slots_dev, states_out, policies_out, values_out,
+               game_index_out, h->state_floats, h->num_actions, h->capacity, h->game_index.get() + h->capacity};
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
   R_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -222,7 +220,7 @@ nz_status nz_replay_check(nz_replay* h, void* stream) {
   if (!h) return NZ_ERR_ARG;
   R_HIP(h, hipSetDevice(h->device));
   int32_t f = 0;
-  R_HIP(h, hipMemcpyAsync(&f, h->game_index + h->capacity, sizeof(f), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  R_HIP(h, hipMemcpyAsync(&f, h->game_index.get() + h->capacity, sizeof(f), hipMemcpyDeviceToHost, (hipStream_t)stream));
   R_HIP(h, hipStreamSynchronize((hipStream_t)stream));
   if (f) return rfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: 1 slot beyond capacity, 2 action out of range, "
                                           "4 batch slot out of range)", f);

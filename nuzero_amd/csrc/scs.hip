@@ -9,15 +9,16 @@
 
 #include "../../include/nuzero_amd.h"
 #include "scs_dev.hpp"
+#include "hip_own.hpp"
 
 using namespace nz;
 
 struct nz_scs {
   int device = 0, n_games = 0;
   ScsRules host_rules;
-  ScsRules* rules = nullptr;                 // one description, or one per game (nz_scs_set_maps)
+  DevBuf<ScsRules> rules;                    // one description, or one per game (nz_scs_set_maps)
   int rules_stride = 0;                      // 0: every game reads rules[0]; 1: game g reads rules[g]
-  ScsState* states = nullptr;
+  DevBuf<ScsState> states;
   std::string error;
 };
 
@@ -150,14 +151,11 @@ nz_status nz_scs_set_maps(nz_scs* h, const float* terrain_host, const int32_t* v
     const int T = b.tiles, nv = b.n_vp[0] + b.n_vp[1];
     for (int g = 0; g < want; ++g) nz::scs_apply_map(&rows[g], terrain_host + (size_t)g * T * 3, vp_host + (size_t)g * nv * 2);
   }
-  ScsRules* dev = nullptr;
-  SCS_HIP(h, hipMalloc((void**)&dev, rows.size() * sizeof(ScsRules)));
-  if (hipMemcpy(dev, rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(dev);
+  DevBuf<ScsRules> dev;                      // the rows in use stay until the new ones are up
+  if (!dev.ensure(rows.size())) return scs_fail(h, NZ_ERR_HIP, "device allocation failed");
+  if (hipMemcpy(dev.get(), rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice) != hipSuccess)
     return scs_fail(h, NZ_ERR_HIP, "upload failed");
-  }
-  (void)hipFree(h->rules);
-  h->rules = dev;
+  h->rules = std::move(dev);
   h->rules_stride = terrain_host ? 1 : 0;
   return nz_scs_reset(h, stream);
 }
@@ -180,13 +178,12 @@ nz_status nz_scs_create(nz_scs** out, const nz_scs_desc* d, int32_t n_games, int
     return scs_fail(nullptr, NZ_ERR_ARG, "%s", err.c_str());
   }
   ScsRules& r = h->host_rules;
-  if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&h->rules, sizeof(ScsRules)) != hipSuccess ||
-      hipMalloc((void**)&h->states, (size_t)n_games * sizeof(ScsState)) != hipSuccess ||
-      hipMemcpy(h->rules, &r, sizeof(r), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || !h->rules.ensure(1) ||
+      !h->states.ensure((size_t)n_games) || hipMemcpy(h->rules.get(), &r, sizeof(r), hipMemcpyHostToDevice) != hipSuccess) {
     nz_scs_destroy(h);
     return scs_fail(nullptr, NZ_ERR_HIP, "device allocation failed");
   }
-  hipLaunchKernelGGL(scs_reset_kernel, dim3(blocks(n_games)), dim3(128), 0, nullptr, h->rules, 0, h->states, n_games);
+  hipLaunchKernelGGL(scs_reset_kernel, dim3(blocks(n_games)), dim3(128), 0, nullptr, h->rules.get(), 0, h->states.get(), n_games);
   if (hipDeviceSynchronize() != hipSuccess) {
     nz_scs_destroy(h);
     return scs_fail(nullptr, NZ_ERR_HIP, "reset kernel failed");
@@ -198,8 +195,6 @@ nz_status nz_scs_create(nz_scs** out, const nz_scs_desc* d, int32_t n_games, int
 void nz_scs_destroy(nz_scs* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->rules) (void)hipFree(h->rules);
-  if (h->states) (void)hipFree(h->states);
   delete h;
 }
 
@@ -215,7 +210,7 @@ nz_status nz_scs_dims(const nz_scs* h, int32_t* planes, int32_t* rows, int32_t* 
 nz_status nz_scs_reset(nz_scs* h, void* stream) {
   if (!h) return NZ_ERR_ARG;
   SCS_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(scs_reset_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules, h->rules_stride, h->states,
+  hipLaunchKernelGGL(scs_reset_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules.get(), h->rules_stride, h->states.get(),
                      h->n_games);
   SCS_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -224,7 +219,7 @@ nz_status nz_scs_reset(nz_scs* h, void* stream) {
 nz_status nz_scs_step(nz_scs* h, const int32_t* actions_dev, void* stream) {
   if (!h || !actions_dev) return NZ_ERR_ARG;
   SCS_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(scs_step_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules, h->rules_stride, h->states,
+  hipLaunchKernelGGL(scs_step_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules.get(), h->rules_stride, h->states.get(),
                      actions_dev, h->n_games);
   SCS_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -233,7 +228,7 @@ nz_status nz_scs_step(nz_scs* h, const int32_t* actions_dev, void* stream) {
 nz_status nz_scs_legal_mask(nz_scs* h, int8_t* mask_dev, void* stream) {
   if (!h || !mask_dev) return NZ_ERR_ARG;
   SCS_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(scs_mask_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules, h->rules_stride, h->states,
+  hipLaunchKernelGGL(scs_mask_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules.get(), h->rules_stride, h->states.get(),
                      mask_dev, h->n_games);
   SCS_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -242,7 +237,7 @@ nz_status nz_scs_legal_mask(nz_scs* h, int8_t* mask_dev, void* stream) {
 nz_status nz_scs_state_image(nz_scs* h, float* image_dev, void* stream) {
   if (!h || !image_dev) return NZ_ERR_ARG;
   SCS_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(scs_image_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules, h->rules_stride, h->states,
+  hipLaunchKernelGGL(scs_image_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->rules.get(), h->rules_stride, h->states.get(),
                      image_dev, h->n_games);
   SCS_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -251,7 +246,7 @@ nz_status nz_scs_state_image(nz_scs* h, float* image_dev, void* stream) {
 nz_status nz_scs_status(nz_scs* h, int32_t* status_dev, void* stream) {
   if (!h || !status_dev) return NZ_ERR_ARG;
   SCS_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(scs_status_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->states,
+  hipLaunchKernelGGL(scs_status_kernel, dim3(blocks(h->n_games)), dim3(128), 0, (hipStream_t)stream, h->states.get(),
                      status_dev, h->n_games);
   SCS_HIP(h, hipGetLastError());
   return NZ_OK;

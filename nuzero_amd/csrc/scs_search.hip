@@ -30,6 +30,7 @@
 #include "../../include/nuzero_amd.h"
 #include "scs_dev.hpp"
 #include "boardnet_internal.h"
+#include "hip_own.hpp"
 
 using namespace nz;
 
@@ -1959,6 +1960,143 @@ persist_fn_t persist_pick(bool hex, bool one_chunk) {
   return one_chunk ? persist_kernel<false, 1> : persist_kernel<false, MAXC_CHUNKS>;
 }
 
+
+// ---- who owns the handle's memory --------------------------------------------------------------------------------------
+// One struct of owners (hip_own.hpp) per lifecycle: ensure() is all or nothing -- a group that could not be made whole is
+// emptied, so the next call tries again and nothing ever runs on half of one -- and bind() is the only code that writes
+// the group's pointers into the kernels' argument structs (null after a reset).
+template <typename Group>
+bool whole(Group* g, bool ok) {
+  if (!ok) *g = Group{};
+  return ok;
+}
+
+struct CreateBufs {               // nz_scs_search_create, for the handle's life
+  DevBuf<ScsRules> rules;         // the description (one row)
+  DevBuf<ScsState> real, scratch;
+  DevBuf<SNode> nodes;
+  DevBuf<int32_t> node_count, root, sims_left, pending, path, path_len, error_flag;
+  DevBuf<int32_t> leaf_count;     // 6 ints: two (leaf, active, cache hit) triples
+  DevBuf<int8_t> half; DevBuf<uint32_t> leaf_mask; DevBuf<int64_t> counters;
+  DevBuf<double> bias_tab, sqrt_tab;
+  DevBuf<int32_t> rec_action, rec_tree_size, rec_children, rec_child_action, rec_child_visit;
+  DevBuf<double> rec_bias, rec_root_value_sum, rec_child_prior, rec_child_value_sum;
+  // makes the arrays and hands them to `p` (p.rules: GameRows::bind; the counter triple: rest_counters)
+  bool ensure(SearchParams& p) {
+    const size_t G = p.n_games, GM = G * p.max_moves, GMC = GM * p.maxc, tab = p.tab_len;
+#define MADE(f, n) (f.ensure(n) && (p.f = f.get()))
+    return whole(this, rules.ensure(1) && leaf_count.ensure(6) && MADE(real, G) && MADE(scratch, G) && MADE(nodes, G * (size_t)p.cap) &&
+                           MADE(half, G) && MADE(node_count, G) && MADE(root, G) && MADE(sims_left, G) && MADE(pending, G) &&
+                           MADE(path, G * (size_t)p.max_path) && MADE(path_len, G) && MADE(leaf_mask, G * MASK_WORDS) && MADE(error_flag, 1) &&
+                           MADE(counters, 16) && MADE(bias_tab, tab) && MADE(sqrt_tab, tab) && MADE(rec_action, GM) && MADE(rec_tree_size, GM) &&
+                           MADE(rec_children, GM) && MADE(rec_bias, GM) && MADE(rec_root_value_sum, GM) && MADE(rec_child_action, GMC) &&
+                           MADE(rec_child_visit, GMC) && MADE(rec_child_prior, GMC) && MADE(rec_child_value_sum, GMC));
+#undef MADE
+  }
+};
+
+struct PlayBufs {                 // the library's move loop: leaf batch, evaluations, one move's host-drawn randomness
+  DevBuf<float> probs, value;     // evaluations: the network's in slots [0, G), cache hits in [G, 2 G) / [2 G, 3 G) by wave parity
+  DevBuf<int32_t> leaf_game, nchild, status;
+  DevBuf<uint64_t> leaf_key;
+  DevBuf<double> noise, uniforms;
+  PinnedBuf<int32_t> active;      // pinned host word + event: the early-finish poll of the wave-by-wave route
+  Event ev_poll;
+  bool ensure(size_t G, size_t A, size_t maxc) {
+    return whole(this, probs.ensure(3 * G * A) && value.ensure(3 * G) && leaf_game.ensure(G) && leaf_key.ensure(2 * G) &&
+                           nchild.ensure(G) && status.ensure(G * 7) && noise.ensure(G * maxc) && uniforms.ensure(G * 3) &&
+                           active.ensure(1) && ev_poll.create(hipEventDisableTiming));
+  }
+  void bind(SearchParams& p) const { p.leaf_key = leaf_key.get(); p.eval_probs = probs.get(); p.eval_value = value.get(); }
+};
+
+struct RoundBufs {                // nz_scs_search_play_round: the round's store (grown, never shrunk), one move's slot bookkeeping
+  DevBuf<int32_t> action, tree_size, children, child_action, child_visit, status, to_record, restart;
+  DevBuf<double> bias, root_value_sum, child_prior, child_value_sum;
+  int64_t games = 0;              // games the store holds
+  bool ensure(int64_t n, size_t G, const SearchParams& p) {
+    if (n <= games) return true;
+    *this = RoundBufs{};          // every array grows with n: free them all before the first is made anew
+    const size_t NM = (size_t)n * p.max_moves, NMC = NM * p.maxc;
+    const bool ok = action.ensure(NM) && tree_size.ensure(NM) && children.ensure(NM) && bias.ensure(NM) && root_value_sum.ensure(NM) &&
+                    child_action.ensure(NMC) && child_visit.ensure(NMC) && child_prior.ensure(NMC) && child_value_sum.ensure(NMC) &&
+                    status.ensure((size_t)n * 2) && to_record.ensure(G) && restart.ensure(G);
+    games = ok ? n : 0;
+    return whole(this, ok);
+  }
+  void bind(RoundStore& r) const {
+    r.action = action.get(); r.tree_size = tree_size.get(); r.children = children.get(); r.child_action = child_action.get();
+    r.child_visit = child_visit.get(); r.status = status.get(); r.bias = bias.get(); r.root_value_sum = root_value_sum.get();
+    r.child_prior = child_prior.get(); r.child_value_sum = child_value_sum.get();
+  }
+};
+
+struct CacheBufs {                // nz_scs_search_cache: the inference cache's table
+  DevBuf<uint64_t> id, check;
+  DevBuf<float> probs, value;
+  DevBuf<int32_t> writer;
+  bool ensure(size_t n, size_t A) {
+    return whole(this, id.ensure(n * 2) && probs.ensure(n * A) && value.ensure(n) && writer.ensure(n) && check.ensure(n));
+  }
+  void bind(SearchParams& p) const {
+    p.c_id = id.get(); p.c_probs = probs.get(); p.c_value = value.get(); p.c_writer = writer.get(); p.c_check = check.get();
+  }
+};
+
+struct RecordBufs {               // nz_scs_search_record: leaf evaluations of chosen games
+  DevBuf<int32_t> slot, count;
+  DevBuf<uint64_t> digest;
+  DevBuf<float> probs, value;
+  bool ensure(size_t G, size_t n, size_t capacity, size_t A) {
+    const size_t N = n * capacity;
+    return whole(this, slot.ensure(G) && count.ensure(n) && digest.ensure(N * 2) && probs.ensure(N * A) && value.ensure(N));
+  }
+  void bind(PersistArgs& q) const {
+    q.rec_slot = slot.get(); q.rec_count = count.get(); q.rec_digest = digest.get(); q.rec_probs = probs.get(); q.rec_value = value.get();
+  }
+};
+
+struct GameRows {                 // per-game maps (nz_scs_search_set_games / _draw_games); grown, never shrunk
+  DevBuf<ScsRules> rules;         // [rows]
+  DevBuf<uint64_t> key;           // [rows][2] map digests (the inference cache's key)
+  DevBuf<int32_t> row;            // [n_games] the row each slot's game reads
+  bool ensure(size_t n, size_t G) {
+    if (n > rules.size()) { rules.reset(); key.reset(); }     // both grow: free both before either is made anew
+    return whole(this, rules.ensure(n) && key.ensure(n * 2) && row.ensure(G));
+  }
+  // the plays read the per-game rows and digests, or the description's one map
+  void bind(SearchParams& p, const ScsRules* base, bool per_game) const {
+    p.rules = per_game ? rules.get() : base;
+    p.rules_row = per_game ? row.get() : nullptr;
+    p.rules_key = per_game ? key.get() : nullptr;
+  }
+};
+
+struct DrawBufs {                 // nz_scs_search_draw_games: the last draw's per-game buffers (grown, never shrunk)
+  DevBuf<uint32_t> seeds, keys;
+  DevBuf<float> terrain;
+  DevBuf<int32_t> vp, pos, err;
+  bool ensure(size_t n, size_t tiles, size_t n_vp) {
+    if (n > seeds.size()) *this = DrawBufs{};                 // all grow: free them all before the first is made anew
+    return whole(this, seeds.ensure(n) && keys.ensure(n * 624) && terrain.ensure(n * tiles * 3) && vp.ensure(n * n_vp * 2) &&
+                           pos.ensure(n) && err.ensure(n));
+  }
+};
+
+struct MatchBufs {                // nz_scs_match_play, kept on agent 1's handle
+  // the forced actions of both engines' end_move [2][G], the match record [G][max_moves], live matches and both engines' flags [3]
+  DevBuf<int32_t> forced, actions, state;
+  DevBuf<int64_t> tally;          // [8]
+  PinnedBuf<int32_t> pinned;      // the (live, flags) read-back
+  Stream stream;                  // the opponent's search
+  Event ev_fork, ev_join;
+  bool ensure(size_t G, size_t max_moves) {
+    return whole(this, forced.ensure(2 * G) && actions.ensure(G * max_moves) && state.ensure(3) && tally.ensure(8) && pinned.ensure(3) &&
+                           stream.create(hipStreamNonBlocking) && ev_fork.create(hipEventDisableTiming) &&
+                           ev_join.create(hipEventDisableTiming));
+  }
+};
+
 }  // namespace
 
 struct nz_scs_search {
@@ -1966,59 +2104,41 @@ struct nz_scs_search {
   nz_search_cfg cfg;
   ScsRules host_rules;
   SearchParams p;
-  std::vector<void*> allocs;
   std::string error;
-  // nz_scs_search_play: leaf batch, evaluations and the host-drawn randomness of one move
-  float *images = nullptr, *probs = nullptr, *value = nullptr;
-  int32_t *leaf_game = nullptr, *nchild = nullptr, *status = nullptr;
-  double *noise = nullptr, *uniforms = nullptr;
+  CreateBufs made;
+  PlayBufs play;                              // (the library's move loop)
   int64_t waves = 0;
-  int32_t* active_pinned = nullptr;          // pinned host word + event: the early-finish poll of the move loop
-  hipEvent_t ev_poll = nullptr;
-  // nz_scs_search_play_round: the round's store and the slot bookkeeping of one move
+  // nz_scs_search_play_round
+  RoundBufs round_bufs;
   RoundStore round{};
-  int64_t round_capacity = 0, round_games = 0;
-  int32_t *to_record = nullptr, *restart = nullptr;
-  int32_t* counters_base = nullptr;          // 6 ints: two (leaf, active, cache hit) triples
+  int64_t round_games = 0;
   // inference cache (nz_scs_search_cache)
-  int cache_bits = 0;
+  CacheBufs cache;
+  int32_t cache_bits = 0, cache_wave = 0;
   int64_t cache_entries = 0;
-  int32_t cache_wave = 0;
   int cache_route = 0;                        // which route filled the table (1 wave by wave, 2 persistent); they do not mix
   // persistent route (persist_kernel): -1 follow the default (on where the network has a per-wavefront form), 0 off, 1 on
   int persist_mode = -1;
   int persist_used = 0;                       // the last play ran on it
   void (*persist_fn)(SearchParams, PersistArgs) = nullptr;     // the kernel variant of the last play
   bool persist_profile = false;               // HIP events around every persist_kernel launch (nz_scs_search_persist_profile)
-  hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+  Event ev_p0, ev_p1;
   double persist_ms = 0.0;
   int64_t persist_launches = 0, persist_mfmas = 0, persist_flops = 0;
   std::string persist_why;                    // why not
   PersistArgs pq{};
-  int32_t* rec_slot_dev = nullptr;
+  RecordBufs rec;
   int32_t rec_slots = 0;
   // per-game maps and streams of the next plays (nz_scs_search_set_games)
-  ScsRules* base_rules_dev = nullptr;         // the description of nz_scs_search_create (one row)
-  ScsRules* game_rules_dev = nullptr;         // [n_game_rows]
-  int32_t* rules_row_dev = nullptr;           // [n_games]
-  uint64_t* rules_key_dev = nullptr;          // [n_game_rows][2] map digests (the inference cache's key)
-  int64_t n_game_rows = 0;
-  int64_t game_rows_cap = 0;                  // rows game_rules_dev / rules_key_dev hold (grown, never shrunk)
+  GameRows rows;
+  int64_t n_game_rows = 0;                    // rows in use; 0: the description's one map
   std::vector<nz_rng*> game_streams;          // [n_game_rows] or empty: streams from the seeds
-  // nz_scs_search_draw_games: what a game draws and the last draw's per-game buffers (grown, never shrunk)
+  // nz_scs_search_draw_games: what a game draws and the last draw
   bool draw_set = false;
   ScsDrawSpec draw{};
-  int64_t draw_cap = 0;
+  DrawBufs drawn;
   int64_t n_drawn = 0;                        // games of the last draw; 0 when the games were set otherwise
-  uint32_t *draw_seeds_dev = nullptr, *draw_keys_dev = nullptr;
-  float* draw_terrain_dev = nullptr;
-  int32_t *draw_vp_dev = nullptr, *draw_pos_dev = nullptr, *draw_err_dev = nullptr;
-  // nz_scs_match_play (kept on agent 1's handle): the opponent's stream and the fork / join events, the forced actions
-  // of both engines' end_move [2][G], the match record [G][max_moves], the tally, the pinned (live, flags) read-back
-  hipStream_t match_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int32_t *match_forced = nullptr, *match_actions = nullptr, *match_state = nullptr, *match_pinned = nullptr;
-  int64_t* match_tally = nullptr;
+  MatchBufs match;
   const nz_scs_search* match_peer = nullptr;    // agent 2 of the last round (compared, never followed)
 };
 
@@ -2038,20 +2158,19 @@ nz_status sfail(nz_scs_search* h, nz_status code, const char* fmt, ...) {
     hipError_t e__ = (call);                                                                      \
     if (e__ != hipSuccess) return sfail((h), NZ_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
   } while (0)
-template <typename T>
-bool dalloc(nz_scs_search* h, T** out, size_t n) {
-  void* q = nullptr;
-  if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return false;
-  h->allocs.push_back(q);
-  *out = static_cast<T*>(q);
-  return true;
+constexpr const char* FLAG_TEXT = "1 arena full, 2 visit table/path too short, 4 move ended before its search, 8 forced action is not legal, "
+                                  "16 more legal actions than the bound computed at create, 32 game longer than that bound";
+// the (leaf, active, cache hit) counter pointers at rest: the first triple, zeroed by the host (a wave-by-wave play leaves the last wave's)
+void rest_counters(nz_scs_search* h) {
+  int32_t* const counters = h->made.leaf_count.get();
+  h->p.leaf_count = counters; h->p.active_count = counters + 1; h->p.hit_count = counters + 2;
+  h->p.clear_counters = nullptr;
 }
 nz_status check_flag(nz_scs_search* h, hipStream_t s) {
   int32_t f = 0;
   S_HIP(h, hipMemcpyAsync(&f, h->p.error_flag, sizeof(f), hipMemcpyDeviceToHost, s));
   S_HIP(h, hipStreamSynchronize(s));
-  if (f) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: 1 arena full, 2 visit table/path too short, "
-                                          "4 move ended before its search, 8 forced action is not legal, 16 more legal actions than the bound computed at create, 32 game longer than that bound)", f);
+  if (f) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s)", f, FLAG_TEXT);
   return NZ_OK;
 }
 }  // namespace
@@ -2080,7 +2199,6 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   (void)hipSetDevice(device);
   SearchParams& p = h->p;
   memset(&p, 0, sizeof(p));
-  const size_t G = n_games;
   p.n_games = n_games;
 
   p.sims = cfg->mcts_simulations;
@@ -2156,40 +2274,20 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   p.value_factor = cfg->value_factor;
   p.eps_softmax = cfg->epsilon_softmax_exploration;
   p.eps_random = cfg->epsilon_random_exploration;
-  ScsRules* rules = nullptr;
-  double *bias = nullptr, *sq = nullptr;
-  const size_t GM = G * MAX_MOVES;
-  bool ok = dalloc(h, &rules, 1) && dalloc(h, &p.real, G) && dalloc(h, &p.scratch, G) &&
-            dalloc(h, &p.nodes, G * (size_t)p.cap) && dalloc(h, &p.half, G) && dalloc(h, &p.node_count, G) && dalloc(h, &p.root, G) &&
-            dalloc(h, &p.sims_left, G) && dalloc(h, &p.pending, G) && dalloc(h, &p.path, G * (size_t)p.max_path) &&
-            dalloc(h, &p.path_len, G) && dalloc(h, &p.leaf_mask, G * MASK_WORDS) && dalloc(h, &p.leaf_count, 6) &&
-            dalloc(h, &p.error_flag, 1) && dalloc(h, &p.counters, 16) && dalloc(h, &bias, (size_t)p.tab_len) &&
-            dalloc(h, &sq, (size_t)p.tab_len) && dalloc(h, &p.rec_action, GM) && dalloc(h, &p.rec_tree_size, GM) &&
-            dalloc(h, &p.rec_children, GM) && dalloc(h, &p.rec_bias, GM) && dalloc(h, &p.rec_root_value_sum, GM) &&
-            dalloc(h, &p.rec_child_action, GM * MAXC) && dalloc(h, &p.rec_child_visit, GM * MAXC) &&
-            dalloc(h, &p.rec_child_prior, GM * MAXC) && dalloc(h, &p.rec_child_value_sum, GM * MAXC);
-  if (!ok) { nz_scs_search_destroy(h); return sfail(nullptr, NZ_ERR_HIP, "device allocation failed"); }
+  if (!h->made.ensure(p)) { nz_scs_search_destroy(h); return sfail(nullptr, NZ_ERR_HIP, "device allocation failed"); }
+  h->rows.bind(p, h->made.rules.get(), false);
   std::vector<double> hb(p.tab_len), hs(p.tab_len);
   for (int n = 0; n < p.tab_len; ++n) {      // Explorer.py:103-112 with the host libm
     hb[n] = std::log(((double)n + cfg->pb_c_base + 1.0) / cfg->pb_c_base) + cfg->pb_c_init;
     hs[n] = std::sqrt((double)n);
   }
-  if (hipMemcpy(rules, &h->host_rules, sizeof(ScsRules), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(bias, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(sq, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(h->made.rules.get(), &h->host_rules, sizeof(ScsRules), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->made.bias_tab.get(), hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->made.sqrt_tab.get(), hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
     nz_scs_search_destroy(h);
     return sfail(nullptr, NZ_ERR_HIP, "upload failed");
   }
-  p.active_count = p.leaf_count + 1;
-  p.hit_count = p.leaf_count + 2;
-  p.clear_counters = nullptr;
-  h->counters_base = p.leaf_count;
-  p.rules = rules;
-  p.rules_row = nullptr;
-  p.rules_key = nullptr;
-  h->base_rules_dev = rules;
-  p.bias_tab = bias;
-  p.sqrt_tab = sq;
+  rest_counters(h);
   (void)hipMemset(p.counters, 0, 16 * sizeof(int64_t));      // (the reset leaves the cache's three alone)
   hipLaunchKernelGGL(search_reset_kernel, dim3((n_games + 127) / 128), dim3(128), 0, nullptr, p);
   if (hipDeviceSynchronize() != hipSuccess) { nz_scs_search_destroy(h); return sfail(nullptr, NZ_ERR_HIP, "reset failed"); }
@@ -2201,31 +2299,6 @@ void nz_scs_search_destroy(nz_scs_search* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  for (void* q : h->allocs) (void)hipFree(q);
-  if (h->active_pinned) (void)hipHostFree(h->active_pinned);
-  if (h->ev_poll) (void)hipEventDestroy(h->ev_poll);
-  if (h->ev_p0) { (void)hipEventDestroy(h->ev_p0); (void)hipEventDestroy(h->ev_p1); }
-  if (h->match_stream) (void)hipStreamDestroy(h->match_stream);
-  if (h->ev_fork) { (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); }
-  if (h->match_pinned) (void)hipHostFree(h->match_pinned);
-  {
-    const RoundStore& r = h->round;
-    void* store[] = {r.action, r.tree_size, r.children, r.child_action, r.child_visit, r.status, r.bias, r.root_value_sum,
-                     r.child_prior, r.child_value_sum};
-    for (void* q : store)
-      if (q) (void)hipFree(q);
-  }
-  if (h->p.c_id) { (void)hipFree(h->p.c_id); (void)hipFree(h->p.c_probs); (void)hipFree(h->p.c_value); (void)hipFree(h->p.c_writer); (void)hipFree(h->p.c_check); }
-  if (h->rec_slot_dev) {
-    (void)hipFree(h->rec_slot_dev); (void)hipFree(h->pq.rec_count); (void)hipFree(h->pq.rec_digest);
-    (void)hipFree(h->pq.rec_probs); (void)hipFree(h->pq.rec_value);
-  }
-  if (h->game_rules_dev) (void)hipFree(h->game_rules_dev);
-  if (h->rules_key_dev) (void)hipFree(h->rules_key_dev);
-  if (h->rules_row_dev) (void)hipFree(h->rules_row_dev);
-  for (void* q : {(void*)h->draw_seeds_dev, (void*)h->draw_keys_dev, (void*)h->draw_terrain_dev, (void*)h->draw_vp_dev,
-                  (void*)h->draw_pos_dev, (void*)h->draw_err_dev})
-    if (q) (void)hipFree(q);
   for (nz_rng* r : h->game_streams) nz_rng_destroy(r);
   delete h;
 }
@@ -2242,6 +2315,14 @@ nz_status nz_scs_search_root_children(nz_scs_search* h, int32_t* out_dev, void* 
   if (!h || !out_dev) return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(root_children_kernel, dim3((h->n_games + 127) / 128), dim3(128), 0, (hipStream_t)stream, h->p, out_dev);
+  S_HIP(h, hipGetLastError());
+  return NZ_OK;
+}
+
+nz_status nz_scs_search_status(nz_scs_search* h, int32_t* status_dev, void* stream) {
+  if (!h || !status_dev) return NZ_ERR_ARG;
+  S_HIP(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(search_status_kernel, dim3((h->n_games + 127) / 128), dim3(128), 0, (hipStream_t)stream, h->p, status_dev);
   S_HIP(h, hipGetLastError());
   return NZ_OK;
 }
@@ -2285,13 +2366,7 @@ nz_status nz_scs_search_expand(nz_scs_search* h, const float* probs_dev, const f
 nz_status nz_scs_search_end_move(nz_scs_search* h, const double* uniforms_dev, void* stream) {
   if (!h) return NZ_ERR_ARG;
   if (h->cfg.training && !uniforms_dev) return sfail(h, NZ_ERR_ARG, "training search needs uniforms");
-  S_HIP(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(end_move_kernel, dim3((h->n_games + 63) / 64), dim3(64), 0, s, h->p, uniforms_dev,
-                     (const int32_t*)nullptr);
-  hipLaunchKernelGGL(compact_kernel, dim3(h->n_games), dim3(64), 0, s, h->p);
-  S_HIP(h, hipGetLastError());
-  return check_flag(h, s);
+  return nz_scs_search_apply(h, nullptr, uniforms_dev, stream);     // (no forced actions: every search chooses its own)
 }
 
 nz_status nz_scs_search_apply(nz_scs_search* h, const int32_t* actions_dev, const double* uniforms_dev, void* stream) {
@@ -2322,8 +2397,6 @@ nz_status nz_scs_search_last_actions(nz_scs_search* h, int32_t* actions_dev, voi
   return NZ_OK;
 }
 
-nz_status nz_scs_search_status(nz_scs_search* h, int32_t* status_dev, void* stream);
-
 // Gamer.play_game for all games to the end with the network on the device too: the move loop of
 // Training/Gamer.py:52-92 and Explorer.run_mcts, one simulation wave = [expand + select] kernel
 // -> nz_boardnet_forward on the wave's leaves (batch size read from device memory).  The host
@@ -2336,22 +2409,6 @@ nz_status nz_scs_search_play(nz_scs_search* h, nz_boardnet* net, const uint32_t*
 }  // extern "C"
 
 namespace {
-// page-locked host array (the move loop's read-backs and uploads: from pageable memory every copy is staged)
-template <typename T>
-struct Pinned {
-  T* p = nullptr;
-  size_t n = 0;
-  explicit Pinned(size_t count) : n(count) {
-    if (hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault) != hipSuccess) p = nullptr;
-  }
-  ~Pinned() { if (p) (void)hipHostFree(p); }
-  Pinned(const Pinned&) = delete;
-  Pinned& operator=(const Pinned&) = delete;
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-  T* data() { return p; }
-  size_t size() const { return n; }
-};
 // a few host threads that live for one play call: every move hands them the same job (the games' random draws, a slice
 // of the games each) -- starting and joining eight threads per move was a quarter of a millisecond of every move
 class WorkerPool {
@@ -2396,29 +2453,44 @@ class WorkerPool {
   bool stop_ = false;
 };
 
-// (re)allocate the round's store for `n` games
+// the round's store for `n` games
 nz_status round_store(nz_scs_search* h, int64_t n) {
-  if (n <= h->round_capacity) return NZ_OK;
-  RoundStore& r = h->round;
-  void* old[] = {r.action, r.tree_size, r.children, r.child_action, r.child_visit, r.status, r.bias, r.root_value_sum,
-                 r.child_prior, r.child_value_sum};
-  for (void* q : old)
-    if (q) (void)hipFree(q);
-  r = RoundStore{};
-  h->round_capacity = 0;
-  const size_t NM = (size_t)n * h->p.max_moves, NMC = NM * h->p.maxc;
-  const bool ok = hipMalloc((void**)&r.action, NM * 4) == hipSuccess && hipMalloc((void**)&r.tree_size, NM * 4) == hipSuccess &&
-                  hipMalloc((void**)&r.children, NM * 4) == hipSuccess && hipMalloc((void**)&r.bias, NM * 8) == hipSuccess &&
-                  hipMalloc((void**)&r.root_value_sum, NM * 8) == hipSuccess &&
-                  hipMalloc((void**)&r.child_action, NMC * 4) == hipSuccess && hipMalloc((void**)&r.child_visit, NMC * 4) == hipSuccess &&
-                  hipMalloc((void**)&r.child_prior, NMC * 8) == hipSuccess && hipMalloc((void**)&r.child_value_sum, NMC * 8) == hipSuccess &&
-                  hipMalloc((void**)&r.status, (size_t)n * 2 * 4) == hipSuccess;
+  if (n <= h->round_bufs.games) return NZ_OK;
+  const bool ok = h->round_bufs.ensure(n, (size_t)h->n_games, h->p);
+  h->round_bufs.bind(h->round);
   if (!ok) return sfail(h, NZ_ERR_HIP, "device allocation failed (round store for %lld games)", (long long)n);
   // unplayed moves' child rows are never written by archive_kernel: keep them defined
+  const RoundStore& r = h->round;
+  const size_t NMC = (size_t)n * h->p.max_moves * h->p.maxc;
   S_HIP(h, hipMemset(r.child_action, 0, NMC * 4)); S_HIP(h, hipMemset(r.child_visit, 0, NMC * 4));
   S_HIP(h, hipMemset(r.child_prior, 0, NMC * 8)); S_HIP(h, hipMemset(r.child_value_sum, 0, NMC * 8));
-  h->round_capacity = n;
   return NZ_OK;
+}
+
+// The records of `games` games in `r` to the caller's device arrays `out` (any may be null), and the simulation and
+// expansion counters to the host (nz_scs_search_export, nz_scs_search_export_round).
+nz_status export_records(nz_scs_search* h, const RoundStore& r, size_t games, const RoundStore& out, int64_t* counters_host, hipStream_t s) {
+  const size_t NM = games * h->p.max_moves, NMC = NM * h->p.maxc;
+  auto copy = [s](auto* dst, const auto* src, size_t n) {
+    return dst ? hipMemcpyAsync(dst, src, n * sizeof(*src), hipMemcpyDeviceToDevice, s) : hipSuccess;
+  };
+  S_HIP(h, copy(out.action, r.action, NM)); S_HIP(h, copy(out.tree_size, r.tree_size, NM)); S_HIP(h, copy(out.children, r.children, NM));
+  S_HIP(h, copy(out.bias, r.bias, NM)); S_HIP(h, copy(out.root_value_sum, r.root_value_sum, NM));
+  S_HIP(h, copy(out.child_action, r.child_action, NMC)); S_HIP(h, copy(out.child_visit, r.child_visit, NMC));
+  S_HIP(h, copy(out.child_prior, r.child_prior, NMC)); S_HIP(h, copy(out.child_value_sum, r.child_value_sum, NMC));
+  S_HIP(h, copy(out.status, r.status, games * 2));
+  if (counters_host) {
+    S_HIP(h, hipMemcpyAsync(counters_host, h->p.counters, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    S_HIP(h, hipStreamSynchronize(s));
+  }
+  return NZ_OK;
+}
+
+// the network's per-wavefront form as the persistent kernels read it
+void persist_net_args(PersistArgs* q, const nz::WaveNet& wn) {
+  q->prog = wn.prog; q->net_floats = wn.lds_floats; q->stage_off = wn.stage_off; q->stage_floats = wn.stage_floats;
+  q->inp = wn.inp; q->in_channels = wn.in_channels;
+  q->wave_bytes = PERSIST_GAME_BYTES + (wn.lds_floats * 4 + 15) / 16 * 16;
 }
 
 // What a play call settles before its first move: the network fits the game, the move loop's buffers exist, and the
@@ -2442,15 +2514,9 @@ nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, voi
                  nrows, ncols, R.channels, R.planes, R.rows, R.cols);
   if (nmax < G) return sfail(h, NZ_ERR_ARG, "network max_batch %d < %d games", nmax, G);
   if (nz_boardnet_input_rows(net, &route->net_rows, &route->row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "bad network handle");
-  if (!h->images) {
-    // evaluations: the network's in slots [0, G), cache hits in [G, 2 G) / [2 G, 3 G) by wave parity
-    const bool ok = dalloc(h, &h->images, (size_t)G * R.channels * R.tiles) && dalloc(h, &h->probs, (size_t)3 * G * A) &&
-                    dalloc(h, &h->value, (size_t)3 * G) && dalloc(h, &h->leaf_game, (size_t)G) &&
-                    dalloc(h, &h->p.leaf_key, (size_t)2 * G) &&
-                    dalloc(h, &h->nchild, (size_t)G) && dalloc(h, &h->status, (size_t)G * 7) &&
-                    dalloc(h, &h->noise, (size_t)G * MAXC) && dalloc(h, &h->uniforms, (size_t)G * 3);
-    if (!ok) return sfail(h, NZ_ERR_HIP, "device allocation failed");
-  }
+  const bool bufs = h->play.ensure((size_t)G, (size_t)A, (size_t)MAXC);
+  h->play.bind(h->p);
+  if (!bufs) return sfail(h, NZ_ERR_HIP, "device allocation failed");
   // the persistent route: the network must have a per-wavefront form
   bool& persist = route->persist;
   size_t& persist_lds = route->persist_lds;
@@ -2464,10 +2530,8 @@ nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, voi
     else if (!nz::boardnet_wave_program(net, &wn, &why)) h->persist_why = why;
     else {
       PersistArgs& q = h->pq;
-      q.prog = wn.prog; q.net_floats = wn.lds_floats; q.stage_off = wn.stage_off; q.stage_floats = wn.stage_floats;
-      q.inp = wn.inp; q.in_channels = wn.in_channels;
+      persist_net_args(&q, wn);
       h->persist_mfmas = wn.mfmas; h->persist_flops = wn.flops;
-      q.wave_bytes = PERSIST_GAME_BYTES + (wn.lds_floats * 4 + 15) / 16 * 16;
       q.rules_per_game = h->n_game_rows > 0 ? 1 : 0;
       persist_lds = (size_t)(q.rules_per_game ? PERSIST_GAMES : 1) * PERSIST_RULES_BYTES + (size_t)PERSIST_GAMES * q.wave_bytes;
       if (persist_lds > 160 * 1024) h->persist_why = "four games' blocks do not fit in LDS";
@@ -2480,9 +2544,8 @@ nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, voi
       if (persist) h->persist_used = wn.hex ? 2 : 1;
     }
     if (mode == 1 && !persist) return sfail(h, NZ_ERR_STATE, "persistent route requested but not available: %s", h->persist_why.c_str());
-    if (h->rec_slot_dev && !persist) return sfail(h, NZ_ERR_STATE, "leaf recording needs the persistent route: %s", h->persist_why.c_str());
+    if (h->rec_slots > 0 && !persist) return sfail(h, NZ_ERR_STATE, "leaf recording needs the persistent route: %s", h->persist_why.c_str());
   }
-  h->pq.rec_slot = h->rec_slot_dev;
   if (h->cache_bits > 0 && h->cache_route != (persist ? 2 : 1)) {
     // the two routes keep their entries differently (check words / writer serial numbers): a table filled by the other
     // one starts empty
@@ -2497,45 +2560,33 @@ nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, voi
   return NZ_OK;
 }
 
-// the wave-by-wave route leaves the counter pointers on the last wave's pair
-void play_finish(nz_scs_search* h) {
-  int32_t* const counters = h->counters_base;
-  h->p.leaf_count = counters;
-  h->p.active_count = counters + 1;
-  h->p.hit_count = counters + 2;
-  h->p.clear_counters = nullptr;
-}
-
 // The search of one move for every live game of `h`, enqueued on `s`: begin_move, then the persistent kernel (one
 // launch) or the simulation waves (the host waits for the move's last ones).  end_move is the caller's.
 nz_status search_move(nz_scs_search* h, nz_boardnet* net, const PlayRoute& route, hipStream_t s) {
   const int G = h->n_games;
-  int32_t* const counters = h->counters_base;
-  hipLaunchKernelGGL(begin_move_kernel, dim3(G), dim3(64), 0, s, h->p, h->noise);
+  int32_t* const counters = h->made.leaf_count.get();
+  float *const probs = h->play.probs.get(), *const value = h->play.value.get();
+  hipLaunchKernelGGL(begin_move_kernel, dim3(G), dim3(64), 0, s, h->p, h->play.noise.get());
   h->p.image_row_stride = route.row_stride;
   S_HIP(h, hipMemsetAsync(counters, 0, 6 * sizeof(int32_t), s));
-  h->p.eval_probs = h->probs;
-  h->p.eval_value = h->value;
   h->p.c_bits = h->cache_bits;
   h->p.terminal_budget = 1;                  // measured best (bench_scs.py: 1 -> 308 games/s, 16 -> 259, unbounded -> 226)
   if (route.persist) {                       // the whole move's search of every game: one launch
     if (h->persist_profile) {
-      if (!h->ev_p0) { S_HIP(h, hipEventCreate(&h->ev_p0)); S_HIP(h, hipEventCreate(&h->ev_p1)); }
-      S_HIP(h, hipEventRecord(h->ev_p0, s));
+      if (!h->ev_p0.create() || !h->ev_p1.create()) return sfail(h, NZ_ERR_HIP, "hipEventCreate failed");
+      S_HIP(h, hipEventRecord(h->ev_p0.get(), s));
     }
     const dim3 pgrid((G + PERSIST_GAMES - 1) / PERSIST_GAMES);
     hipLaunchKernelGGL(h->persist_fn, pgrid, dim3(PERSIST_THREADS), route.persist_lds, s, h->p, h->pq);
     S_HIP(h, hipGetLastError());
     ++h->waves;
-    if (h->persist_profile) S_HIP(h, hipEventRecord(h->ev_p1, s));
+    if (h->persist_profile) S_HIP(h, hipEventRecord(h->ev_p1.get(), s));
     return NZ_OK;
   }
   const int sims = h->cfg.mcts_simulations;
   bool poll_pending = false;
-  if (!h->active_pinned) {
-    S_HIP(h, hipHostMalloc((void**)&h->active_pinned, sizeof(int32_t), hipHostMallocDefault));
-    S_HIP(h, hipEventCreateWithFlags(&h->ev_poll, hipEventDisableTiming));
-  }
+  int32_t* const active_pinned = h->play.active.get();
+  const hipEvent_t ev_poll = h->play.ev_poll.get();
   for (int w = 0;; ++w) {
     // two (leaf, active) counter pairs: wave w counts into pair w & 1 and zeroes the other one for wave w + 1
     h->p.leaf_count = counters + 3 * (w & 1);
@@ -2544,7 +2595,7 @@ nz_status search_move(nz_scs_search* h, nz_boardnet* net, const PlayRoute& route
     h->p.clear_counters = counters + 3 * ((w + 1) & 1);
     h->p.c_wave = ++h->cache_wave;
     h->p.c_hit_base = G * (1 + (w & 1));
-    hipLaunchKernelGGL(wave_kernel, dim3(G), dim3(64), 0, s, h->p, w ? 3 : 2, h->probs, h->value, route.net_rows, h->leaf_game);
+    hipLaunchKernelGGL(wave_kernel, dim3(G), dim3(64), 0, s, h->p, w ? 3 : 2, probs, value, route.net_rows, h->play.leaf_game.get());
     ++h->waves;
     if (w >= sims - 1) {                       // the move's last waves: wait for the count of games still searching
       int32_t active = 0;
@@ -2556,22 +2607,22 @@ nz_status search_move(nz_scs_search* h, nz_boardnet* net, const PlayRoute& route
       // every game may have finished early (simulations that end in terminal leaves do not wait for a wave): the count
       // is copied to pinned memory and looked at eight waves later -- no wait, the GPU is never left without work; the
       // waves launched in between find nothing to do
-      if (poll_pending && hipEventQuery(h->ev_poll) == hipSuccess) {
+      if (poll_pending && hipEventQuery(ev_poll) == hipSuccess) {
         poll_pending = false;
-        if (*h->active_pinned == 0) break;
+        if (*active_pinned == 0) break;
       }
       if (!poll_pending) {
-        S_HIP(h, hipMemcpyAsync(h->active_pinned, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        S_HIP(h, hipEventRecord(h->ev_poll, s));
+        S_HIP(h, hipMemcpyAsync(active_pinned, h->p.active_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        S_HIP(h, hipEventRecord(ev_poll, s));
         poll_pending = true;
       }
     }
-    if (nz_boardnet_forward_rows(net, G, h->p.leaf_count, nullptr, h->probs, h->value, (void*)s) != NZ_OK)
+    if (nz_boardnet_forward_rows(net, G, h->p.leaf_count, nullptr, probs, value, (void*)s) != NZ_OK)
       return sfail(h, NZ_ERR_HIP, "network: %s", nz_boardnet_last_error(net));
     if (h->cache_bits > 0)                   // the leaves the network just evaluated enter the table (KeylessCache.put)
       hipLaunchKernelGGL(cache_put_kernel, dim3(G), dim3(64), 0, s, h->p, h->p.leaf_count);
   }
-  if (poll_pending) S_HIP(h, hipEventSynchronize(h->ev_poll));     // (long done: the move's last waves were waited for)
+  if (poll_pending) S_HIP(h, hipEventSynchronize(ev_poll));     // (long done: the move's last waves were waited for)
   return NZ_OK;
 }
 
@@ -2609,12 +2660,13 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
   std::vector<int32_t> rules_rows(G);
   if (own_games) {
     for (int g = 0; g < G; ++g) rules_rows[g] = g;
-    S_HIP(h, hipMemcpyAsync(h->rules_row_dev, rules_rows.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    S_HIP(h, hipMemcpyAsync(h->rows.row.get(), rules_rows.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
     S_HIP(h, hipStreamSynchronize((hipStream_t)stream));
   }
-  Pinned<int32_t> status((size_t)G * 7), nchild(G);
-  Pinned<double> noise((size_t)G * MAXC), uni((size_t)G * 3);
-  if (!status.p || !nchild.p || !noise.p || !uni.p) return sfail(h, NZ_ERR_HIP, "host allocation failed");
+  PinnedBuf<int32_t> status, nchild;
+  PinnedBuf<double> noise, uni;
+  if (!status.ensure((size_t)G * 7) || !nchild.ensure(G) || !noise.ensure((size_t)G * MAXC) || !uni.ensure((size_t)G * 3))
+    return sfail(h, NZ_ERR_HIP, "host allocation failed");
   const int n_thr = h->cfg.training && G >= 256 ? std::min<int>(8, std::max<unsigned>(1u, std::thread::hardware_concurrency())) : 0;
   WorkerPool pool(n_thr);
   nz_status st = nz_scs_search_reset(h, stream);
@@ -2627,18 +2679,18 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
   if (refill) {
     st = round_store(h, n_round);
     if (st != NZ_OK) return st;
-    if (!h->to_record && !(dalloc(h, &h->to_record, (size_t)G) && dalloc(h, &h->restart, (size_t)G)))
-      return sfail(h, NZ_ERR_HIP, "device allocation failed");
   }
+  int32_t *const status_dev = h->play.status.get(), *const nchild_dev = h->play.nchild.get();
+  int32_t *const to_record_dev = h->round_bufs.to_record.get(), *const restart_dev = h->round_bufs.restart.get();
   const dim3 grid1((G + 127) / 128), block1(128);
   const int64_t move_limit = refill ? (int64_t)MAX_MOVES * ((n_round + G - 1) / G + 1)
                                     : (max_moves > 0 && max_moves < MAX_MOVES ? max_moves : MAX_MOVES);
   for (int64_t move = 0; move < move_limit; ++move) {
-    hipLaunchKernelGGL(search_status_kernel, grid1, block1, 0, s, h->p, h->status);
-    if (h->cfg.training) hipLaunchKernelGGL(root_children_kernel, grid1, block1, 0, s, h->p, h->nchild);
-    S_HIP(h, hipMemcpyAsync(status.data(), h->status, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    hipLaunchKernelGGL(search_status_kernel, grid1, block1, 0, s, h->p, status_dev);
+    if (h->cfg.training) hipLaunchKernelGGL(root_children_kernel, grid1, block1, 0, s, h->p, nchild_dev);
+    S_HIP(h, hipMemcpyAsync(status.get(), status_dev, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (h->cfg.training)
-      S_HIP(h, hipMemcpyAsync(nchild.data(), h->nchild, nchild.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      S_HIP(h, hipMemcpyAsync(nchild.get(), nchild_dev, nchild.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     S_HIP(h, hipStreamSynchronize(s));
     if (refill) {
       bool archive = false, restarted = false;
@@ -2663,19 +2715,19 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
         }
       }
       if (archive) {
-        S_HIP(h, hipMemcpyAsync(h->to_record, to_record.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(archive_kernel, dim3(G), dim3(64), 0, s, h->p, h->round, h->to_record);
+        S_HIP(h, hipMemcpyAsync(to_record_dev, to_record.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(archive_kernel, dim3(G), dim3(64), 0, s, h->p, h->round, to_record_dev);
       }
       if (restarted) {
         if (own_games)
-          S_HIP(h, hipMemcpyAsync(h->rules_row_dev, rules_rows.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        S_HIP(h, hipMemcpyAsync(h->restart, restart.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(restart_kernel, grid1, block1, 0, s, h->p, h->restart);
-        hipLaunchKernelGGL(search_status_kernel, grid1, block1, 0, s, h->p, h->status);
-        if (h->cfg.training) hipLaunchKernelGGL(root_children_kernel, grid1, block1, 0, s, h->p, h->nchild);
-        S_HIP(h, hipMemcpyAsync(status.data(), h->status, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+          S_HIP(h, hipMemcpyAsync(h->rows.row.get(), rules_rows.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        S_HIP(h, hipMemcpyAsync(restart_dev, restart.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(restart_kernel, grid1, block1, 0, s, h->p, restart_dev);
+        hipLaunchKernelGGL(search_status_kernel, grid1, block1, 0, s, h->p, status_dev);
+        if (h->cfg.training) hipLaunchKernelGGL(root_children_kernel, grid1, block1, 0, s, h->p, nchild_dev);
+        S_HIP(h, hipMemcpyAsync(status.get(), status_dev, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (h->cfg.training)
-          S_HIP(h, hipMemcpyAsync(nchild.data(), h->nchild, nchild.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+          S_HIP(h, hipMemcpyAsync(nchild.get(), nchild_dev, nchild.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
       }
       if (archive) S_HIP(h, hipStreamSynchronize(s));     // the bookkeeping vectors are reused next move
     }
@@ -2683,8 +2735,8 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
     for (int g = 0; g < G; ++g) any |= status[(size_t)g * 7 + 4] == 0;
     if (!any) break;
     if (h->cfg.training) {
-      std::fill(noise.data(), noise.data() + noise.size(), 0.0);
-      std::fill(uni.data(), uni.data() + uni.size(), 0.0);
+      std::fill(noise.get(), noise.get() + noise.size(), 0.0);
+      std::fill(uni.get(), uni.get() + uni.size(), 0.0);
       // (every game has its own stream: the draws of different games run on host threads side by side)
       auto draw = [&](int g0, int g1) {
         for (int g = g0; g < g1; ++g) {
@@ -2703,21 +2755,21 @@ nz_status play_impl(nz_scs_search* h, nz_boardnet* net, const uint32_t* seeds_ho
       };
       if (n_thr <= 1) draw(0, G);
       else pool.run([&](int t) { draw((int)((int64_t)G * t / n_thr), (int)((int64_t)G * (t + 1) / n_thr)); });
-      S_HIP(h, hipMemcpyAsync(h->noise, noise.data(), noise.size() * sizeof(double), hipMemcpyHostToDevice, s));
-      S_HIP(h, hipMemcpyAsync(h->uniforms, uni.data(), uni.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      S_HIP(h, hipMemcpyAsync(h->play.noise.get(), noise.get(), noise.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      S_HIP(h, hipMemcpyAsync(h->play.uniforms.get(), uni.get(), uni.size() * sizeof(double), hipMemcpyHostToDevice, s));
     }
     st = search_move(h, net, route, s);
     if (st != NZ_OK) return st;
-    st = nz_scs_search_end_move(h, h->uniforms, stream);     // (synchronises)
+    st = nz_scs_search_end_move(h, h->play.uniforms.get(), stream);     // (synchronises)
     if (st != NZ_OK) return st;
     if (route.persist && h->persist_profile) {
       float ms = 0.f;
-      S_HIP(h, hipEventElapsedTime(&ms, h->ev_p0, h->ev_p1));
+      S_HIP(h, hipEventElapsedTime(&ms, h->ev_p0.get(), h->ev_p1.get()));
       h->persist_ms += ms;
       ++h->persist_launches;
     }
   }
-  play_finish(h);
+  rest_counters(h);
   if (refill) {
     for (int g = 0; g < G; ++g)
       if (slot_game[g] >= 0) return sfail(h, NZ_ERR_STATE, "internal: the round did not finish in %lld moves", (long long)move_limit);
@@ -2750,23 +2802,9 @@ nz_status nz_scs_search_export_round(nz_scs_search* h, int32_t* actions, int32_t
   if (!h) return NZ_ERR_ARG;
   if (h->round_games <= 0) return sfail(h, NZ_ERR_STATE, "no finished round of more games than slots");
   S_HIP(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  const RoundStore& r = h->round;
-  const size_t NM = (size_t)h->round_games * h->p.max_moves;
-  const int MAXC = h->p.maxc;
-#define CP(dst, src, n)                                                                          \
-  if (dst) S_HIP(h, hipMemcpyAsync(dst, src, (n) * sizeof(*src), hipMemcpyDeviceToDevice, s))
-  CP(actions, r.action, NM); CP(tree_size, r.tree_size, NM); CP(n_children, r.children, NM);
-  CP(bias, r.bias, NM); CP(root_value_sum, r.root_value_sum, NM);
-  CP(child_action, r.child_action, NM * MAXC); CP(child_visit, r.child_visit, NM * MAXC);
-  CP(child_prior, r.child_prior, NM * MAXC); CP(child_value_sum, r.child_value_sum, NM * MAXC);
-  CP(status2, r.status, (size_t)h->round_games * 2);
-#undef CP
-  if (counters_host) {
-    S_HIP(h, hipMemcpyAsync(counters_host, h->p.counters, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    S_HIP(h, hipStreamSynchronize(s));
-  }
-  return NZ_OK;
+  return export_records(h, h->round, (size_t)h->round_games,
+                        RoundStore{actions, tree_size, n_children, child_action, child_visit, status2, bias, root_value_sum, child_prior, child_value_sum},
+                        counters_host, (hipStream_t)stream);
 }
 
 // The reference's inference cache for the library's move loop (cache_choice "keyless" / "dict" of Gamer,
@@ -2780,8 +2818,8 @@ nz_status nz_scs_search_cache(nz_scs_search* h, int64_t max_entries) {
   SearchParams& p = h->p;
   const size_t A = (size_t)p.num_actions;
   if (max_entries >= 0) {
-    if (p.c_id) { (void)hipFree(p.c_id); (void)hipFree(p.c_probs); (void)hipFree(p.c_value); (void)hipFree(p.c_writer); (void)hipFree(p.c_check); }
-    p.c_id = nullptr; p.c_probs = nullptr; p.c_value = nullptr; p.c_writer = nullptr; p.c_check = nullptr;
+    h->cache = CacheBufs{};
+    h->cache.bind(p);
     h->cache_bits = 0; h->cache_entries = 0;
     if (max_entries == 0) {                    // no table: nz_scs_search_cache_stats reports none, not the last one's
       S_HIP(h, hipMemset(p.counters + 8, 0, 3 * sizeof(int64_t)));
@@ -2791,10 +2829,8 @@ nz_status nz_scs_search_cache(nz_scs_search* h, int64_t max_entries) {
     while ((2ll << bits) <= max_entries && bits < 30) ++bits;          // closest power of two under max_entries
     if (bits == 0) bits = 1;
     const size_t n = (size_t)1 << bits;
-    if (hipMalloc((void**)&p.c_id, n * 2 * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&p.c_probs, n * A * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&p.c_value, n * sizeof(float)) != hipSuccess || hipMalloc((void**)&p.c_writer, n * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&p.c_check, n * sizeof(uint64_t)) != hipSuccess)
-      return sfail(h, NZ_ERR_HIP, "cache allocation failed (%zu entries of %zu actions)", n, A);
+    if (!h->cache.ensure(n, A)) return sfail(h, NZ_ERR_HIP, "cache allocation failed (%zu entries of %zu actions)", n, A);
+    h->cache.bind(p);
     h->cache_bits = bits;
     h->cache_entries = (int64_t)n;
   }
@@ -2851,36 +2887,16 @@ void clear_games(nz_scs_search* h) {
   h->game_streams.clear();
   h->n_game_rows = 0;
   h->n_drawn = 0;
-  h->p.rules = h->base_rules_dev;
-  h->p.rules_row = nullptr;
-  h->p.rules_key = nullptr;
-}
-
-// Rules rows and digests for n games, and the slots' row indices.
-nz_status grow_game_rows(nz_scs_search* h, int64_t n) {
-  if (n > h->game_rows_cap) {
-    if (h->game_rules_dev) { (void)hipFree(h->game_rules_dev); h->game_rules_dev = nullptr; }
-    if (h->rules_key_dev) { (void)hipFree(h->rules_key_dev); h->rules_key_dev = nullptr; }
-    h->game_rows_cap = 0;
-    if (hipMalloc((void**)&h->game_rules_dev, (size_t)n * sizeof(ScsRules)) != hipSuccess ||
-        hipMalloc((void**)&h->rules_key_dev, (size_t)n * 2 * sizeof(uint64_t)) != hipSuccess)
-      return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
-    h->game_rows_cap = n;
-  }
-  if (!h->rules_row_dev && hipMalloc((void**)&h->rules_row_dev, (size_t)h->n_games * sizeof(int32_t)) != hipSuccess)
-    return sfail(h, NZ_ERR_HIP, "device allocation failed");
-  return NZ_OK;
+  h->rows.bind(h->p, h->made.rules.get(), false);
 }
 
 // The rows are in place: slot g plays row g, the plays read the per-game rows and digests.
 nz_status use_game_rows(nz_scs_search* h, int64_t n, void* stream) {
   std::vector<int32_t> ident(h->n_games);
   for (int g = 0; g < h->n_games; ++g) ident[g] = g;
-  S_HIP(h, hipMemcpy(h->rules_row_dev, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   h->n_game_rows = n;
-  h->p.rules = h->game_rules_dev;
-  h->p.rules_row = h->rules_row_dev;
-  h->p.rules_key = h->rules_key_dev;
+  h->rows.bind(h->p, h->made.rules.get(), true);
   return nz_scs_search_reset(h, stream);       // the slots' games start on their own maps (row g for slot g)
 }
 }  // namespace
@@ -2910,9 +2926,9 @@ nz_status nz_scs_search_set_games(nz_scs_search* h, int64_t n, const float* terr
   }
   std::vector<uint64_t> keys((size_t)n * 2);
   for (int64_t i = 0; i < n; ++i) scs_map_digest(rows[(size_t)i], &keys[(size_t)i * 2]);
-  if (nz_status st = grow_game_rows(h, n)) return st;
-  S_HIP(h, hipMemcpy(h->game_rules_dev, rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice));
-  S_HIP(h, hipMemcpy(h->rules_key_dev, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if (!h->rows.ensure((size_t)n, (size_t)h->n_games)) return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
+  S_HIP(h, hipMemcpy(h->rows.rules.get(), rows.data(), rows.size() * sizeof(ScsRules), hipMemcpyHostToDevice));
+  S_HIP(h, hipMemcpy(h->rows.key.get(), keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (mt_keys_host)
     for (int64_t i = 0; i < n; ++i) {
       nz_rng* r = nz_rng_create_state(mt_keys_host + (size_t)i * 624, mt_pos_host[i], 0, 0.0);
@@ -2982,35 +2998,20 @@ nz_status nz_scs_search_draw_games(nz_scs_search* h, int64_t n, const uint32_t* 
   S_HIP(h, hipSetDevice(h->device));
   S_HIP(h, hipDeviceSynchronize());           // the last plays may still read the rows
   clear_games(h);
-  if (nz_status st = grow_game_rows(h, n)) return st;
+  if (!h->rows.ensure((size_t)n, (size_t)h->n_games)) return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld game descriptions)", (long long)n);
   const ScsRules& b = h->host_rules;
   const int64_t T = b.tiles, nv = b.n_vp[0] + b.n_vp[1];
-  if (n > h->draw_cap) {
-    for (void* q : {(void*)h->draw_seeds_dev, (void*)h->draw_keys_dev, (void*)h->draw_terrain_dev, (void*)h->draw_vp_dev,
-                    (void*)h->draw_pos_dev, (void*)h->draw_err_dev})
-      if (q) (void)hipFree(q);
-    h->draw_seeds_dev = h->draw_keys_dev = nullptr;
-    h->draw_terrain_dev = nullptr;
-    h->draw_vp_dev = h->draw_pos_dev = h->draw_err_dev = nullptr;
-    h->draw_cap = 0;
-    if (hipMalloc((void**)&h->draw_seeds_dev, (size_t)n * 4) != hipSuccess ||
-        hipMalloc((void**)&h->draw_keys_dev, (size_t)n * 624 * 4) != hipSuccess ||
-        hipMalloc((void**)&h->draw_terrain_dev, (size_t)n * T * 3 * 4) != hipSuccess ||
-        hipMalloc((void**)&h->draw_vp_dev, (size_t)n * nv * 2 * 4) != hipSuccess ||
-        hipMalloc((void**)&h->draw_pos_dev, (size_t)n * 4) != hipSuccess ||
-        hipMalloc((void**)&h->draw_err_dev, (size_t)n * 4) != hipSuccess)
-      return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld drawn games)", (long long)n);
-    h->draw_cap = n;
-  }
-  S_HIP(h, hipMemcpyAsync(h->draw_seeds_dev, seeds_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  S_HIP(h, scs_draw_launch(h->draw, h->base_rules_dev, n, h->draw_seeds_dev, h->game_rules_dev, h->rules_key_dev,
-                           h->draw_terrain_dev, h->draw_vp_dev, h->draw_keys_dev, h->draw_pos_dev, h->draw_err_dev, s));
+  DrawBufs& d = h->drawn;
+  if (!d.ensure((size_t)n, (size_t)T, (size_t)nv)) return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld drawn games)", (long long)n);
+  S_HIP(h, hipMemcpyAsync(d.seeds.get(), seeds_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  S_HIP(h, scs_draw_launch(h->draw, h->made.rules.get(), n, d.seeds.get(), h->rows.rules.get(), h->rows.key.get(),
+                           d.terrain.get(), d.vp.get(), d.keys.get(), d.pos.get(), d.err.get(), s));
   // the streams the games go on with: one copy of the states back to the host
   std::vector<uint32_t> keys((size_t)n * 624);
   std::vector<int32_t> pos((size_t)n), err((size_t)n);
-  S_HIP(h, hipMemcpyAsync(keys.data(), h->draw_keys_dev, keys.size() * 4, hipMemcpyDeviceToHost, s));
-  S_HIP(h, hipMemcpyAsync(pos.data(), h->draw_pos_dev, pos.size() * 4, hipMemcpyDeviceToHost, s));
-  S_HIP(h, hipMemcpyAsync(err.data(), h->draw_err_dev, err.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(keys.data(), d.keys.get(), keys.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(pos.data(), d.pos.get(), pos.size() * 4, hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(err.data(), d.err.get(), err.size() * 4, hipMemcpyDeviceToHost, s));
   S_HIP(h, hipStreamSynchronize(s));
   for (int64_t i = 0; i < n; ++i) {
     if (err[(size_t)i] == SCS_DRAW_ERR_COST)
@@ -3037,10 +3038,10 @@ nz_status nz_scs_search_drawn_games(nz_scs_search* h, int64_t* n, float* terrain
   const hipStream_t s = (hipStream_t)stream;
   const size_t N = (size_t)h->n_drawn, T = (size_t)h->host_rules.tiles, nv = (size_t)(h->host_rules.n_vp[0] + h->host_rules.n_vp[1]);
   S_HIP(h, hipSetDevice(h->device));
-  if (terrain) S_HIP(h, hipMemcpyAsync(terrain, h->draw_terrain_dev, N * T * 3 * 4, hipMemcpyDefault, s));
-  if (vp) S_HIP(h, hipMemcpyAsync(vp, h->draw_vp_dev, N * nv * 2 * 4, hipMemcpyDefault, s));
-  if (mt_keys) S_HIP(h, hipMemcpyAsync(mt_keys, h->draw_keys_dev, N * 624 * 4, hipMemcpyDefault, s));
-  if (mt_pos) S_HIP(h, hipMemcpyAsync(mt_pos, h->draw_pos_dev, N * 4, hipMemcpyDefault, s));
+  if (terrain) S_HIP(h, hipMemcpyAsync(terrain, h->drawn.terrain.get(), N * T * 3 * 4, hipMemcpyDefault, s));
+  if (vp) S_HIP(h, hipMemcpyAsync(vp, h->drawn.vp.get(), N * nv * 2 * 4, hipMemcpyDefault, s));
+  if (mt_keys) S_HIP(h, hipMemcpyAsync(mt_keys, h->drawn.keys.get(), N * 624 * 4, hipMemcpyDefault, s));
+  if (mt_pos) S_HIP(h, hipMemcpyAsync(mt_pos, h->drawn.pos.get(), N * 4, hipMemcpyDefault, s));
   S_HIP(h, hipStreamSynchronize(s));
   return NZ_OK;
 }
@@ -3067,25 +3068,19 @@ nz_status nz_scs_search_record(nz_scs_search* h, const int32_t* games_host, int3
   if (!h || n < 0 || (n > 0 && (!games_host || capacity <= 0))) return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
   S_HIP(h, hipDeviceSynchronize());
-  if (h->rec_slot_dev) {
-    (void)hipFree(h->rec_slot_dev); (void)hipFree(h->pq.rec_count); (void)hipFree(h->pq.rec_digest);
-    (void)hipFree(h->pq.rec_probs); (void)hipFree(h->pq.rec_value);
-    h->rec_slot_dev = nullptr; h->pq.rec_count = nullptr; h->pq.rec_digest = nullptr; h->pq.rec_probs = nullptr; h->pq.rec_value = nullptr;
-    h->rec_slots = 0;
-  }
-  h->pq.rec_slot = nullptr;
+  h->rec = RecordBufs{};
+  h->rec.bind(h->pq);
+  h->rec_slots = 0;
   if (n == 0) return NZ_OK;
   std::vector<int32_t> slot(h->n_games, -1);
   for (int i = 0; i < n; ++i) {
     if (games_host[i] < 0 || games_host[i] >= h->n_games) return sfail(h, NZ_ERR_ARG, "no game %d", games_host[i]);
     slot[games_host[i]] = i;
   }
-  const size_t A = (size_t)h->p.num_actions, N = (size_t)n * capacity;
-  if (hipMalloc((void**)&h->rec_slot_dev, slot.size() * 4) != hipSuccess || hipMalloc((void**)&h->pq.rec_count, (size_t)n * 4) != hipSuccess ||
-      hipMalloc((void**)&h->pq.rec_digest, N * 16) != hipSuccess || hipMalloc((void**)&h->pq.rec_probs, N * A * 4) != hipSuccess ||
-      hipMalloc((void**)&h->pq.rec_value, N * 4) != hipSuccess)
+  if (!h->rec.ensure(slot.size(), (size_t)n, (size_t)capacity, (size_t)h->p.num_actions))
     return sfail(h, NZ_ERR_HIP, "device allocation failed (recording %d games x %d evaluations)", n, capacity);
-  S_HIP(h, hipMemcpy(h->rec_slot_dev, slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
+  h->rec.bind(h->pq);
+  S_HIP(h, hipMemcpy(h->rec.slot.get(), slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
   S_HIP(h, hipMemset(h->pq.rec_count, 0, (size_t)n * 4));
   h->pq.rec_cap = capacity;
   h->rec_slots = n;
@@ -3131,21 +3126,18 @@ nz_status nz_scs_netbench(nz_boardnet* net, int32_t blocks, int32_t iters, uint6
   std::string why;
   if (!nz::boardnet_wave_program(net, &wn, &why)) return sfail(nullptr, NZ_ERR_STATE, "%s", why.c_str());
   PersistArgs q{};
-  q.prog = wn.prog; q.net_floats = wn.lds_floats; q.stage_off = wn.stage_off; q.stage_floats = wn.stage_floats;
-  q.inp = wn.inp; q.in_channels = wn.in_channels;
-  q.wave_bytes = PERSIST_GAME_BYTES + (wn.lds_floats * 4 + 15) / 16 * 16;
+  persist_net_args(&q, wn);
   const size_t lds = (size_t)PERSIST_RULES_BYTES + (size_t)PERSIST_GAMES * q.wave_bytes;
-  unsigned long long* out = nullptr;
-  S_HIP(nullptr, hipMalloc((void**)&out, (size_t)blocks * PERSIST_GAMES * 8));
+  DevBuf<unsigned long long> ticks;
+  if (!ticks.ensure((size_t)blocks * PERSIST_GAMES)) return sfail(nullptr, NZ_ERR_HIP, "device allocation failed");
   hipError_t e = wn.hex ? hipFuncSetAttribute((const void*)netbench_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
                         : hipFuncSetAttribute((const void*)netbench_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e == hipSuccess) {
-    if (wn.hex) hipLaunchKernelGGL(netbench_kernel<true>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, out);
-    else hipLaunchKernelGGL(netbench_kernel<false>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, out);
+    if (wn.hex) hipLaunchKernelGGL(netbench_kernel<true>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, ticks.get());
+    else hipLaunchKernelGGL(netbench_kernel<false>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, ticks.get());
     e = hipDeviceSynchronize();
   }
-  if (e == hipSuccess) e = hipMemcpy(ticks_host, out, (size_t)blocks * PERSIST_GAMES * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(out);
+  if (e == hipSuccess) e = hipMemcpy(ticks_host, ticks.get(), (size_t)blocks * PERSIST_GAMES * 8, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return sfail(nullptr, NZ_ERR_HIP, "netbench: %s", hipGetErrorString(e));
   return NZ_OK;
 }
@@ -3168,34 +3160,14 @@ nz_status nz_scs_search_export(nz_scs_search* h, int32_t* actions, int32_t* tree
                                double* child_prior, double* child_value_sum, int64_t* counters_host, void* stream) {
   if (!h) return NZ_ERR_ARG;
   S_HIP(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
   const SearchParams& p = h->p;
-  const size_t GM = (size_t)h->n_games * p.max_moves;
-  const int MAXC = p.maxc;
-#define CP(dst, src, n)                                                                          \
-  if (dst) S_HIP(h, hipMemcpyAsync(dst, src, (n) * sizeof(*src), hipMemcpyDeviceToDevice, s))
-  CP(actions, p.rec_action, GM); CP(tree_size, p.rec_tree_size, GM); CP(n_children, p.rec_children, GM);
-  CP(bias, p.rec_bias, GM); CP(root_value_sum, p.rec_root_value_sum, GM);
-  CP(child_action, p.rec_child_action, GM * MAXC); CP(child_visit, p.rec_child_visit, GM * MAXC);
-  CP(child_prior, p.rec_child_prior, GM * MAXC); CP(child_value_sum, p.rec_child_value_sum, GM * MAXC);
-#undef CP
-  if (counters_host) {
-    S_HIP(h, hipMemcpyAsync(counters_host, p.counters, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    S_HIP(h, hipStreamSynchronize(s));
-  }
-  return NZ_OK;
+  return export_records(h, RoundStore{p.rec_action, p.rec_tree_size, p.rec_children, p.rec_child_action, p.rec_child_visit, nullptr, p.rec_bias,
+                                      p.rec_root_value_sum, p.rec_child_prior, p.rec_child_value_sum}, (size_t)h->n_games,
+                        RoundStore{actions, tree_size, n_children, child_action, child_visit, nullptr, bias, root_value_sum, child_prior, child_value_sum},
+                        counters_host, (hipStream_t)stream);
 }
 
 }  // extern "C"
-
-
-extern "C" nz_status nz_scs_search_status(nz_scs_search* h, int32_t* status_dev, void* stream) {
-  if (!h || !status_dev) return NZ_ERR_ARG;
-  S_HIP(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(search_status_kernel, dim3((h->n_games + 127) / 128), dim3(128), 0, (hipStream_t)stream, h->p, status_dev);
-  S_HIP(h, hipGetLastError());
-  return NZ_OK;
-}
 
 // ---- evaluation matches between two agents (nz_scs_match_play) ---------------------------------------------------------
 // Tester.Test_using_agents with two MctsAgents that keep their subtrees (Testing/Tester.py:62-118,
@@ -3334,15 +3306,15 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
     std::vector<int32_t> ident(G);
     for (int g = 0; g < G; ++g) ident[g] = g;
     S_HIP(a1, hipStreamSynchronize(s1));
-    S_HIP(a1, hipMemcpy(k1.data(), a1->rules_key_dev, k1.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    S_HIP(a1, hipMemcpy(k2.data(), a2->rules_key_dev, k2.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    S_HIP(a1, hipMemcpy(k1.data(), a1->rows.key.get(), k1.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    S_HIP(a1, hipMemcpy(k2.data(), a2->rows.key.get(), k2.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (int g = 0; g < G; ++g)
       if (k1[(size_t)g * 2] != k2[(size_t)g * 2] || k1[(size_t)g * 2 + 1] != k2[(size_t)g * 2 + 1])
         return sfail(a1, NZ_ERR_ARG, "match %d: the two engines hold different maps (digests %016llx%016llx and %016llx%016llx)", g,
                      (unsigned long long)k1[(size_t)g * 2], (unsigned long long)k1[(size_t)g * 2 + 1],
                      (unsigned long long)k2[(size_t)g * 2], (unsigned long long)k2[(size_t)g * 2 + 1]);
-    S_HIP(a1, hipMemcpy(a1->rules_row_dev, ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
-    S_HIP(a1, hipMemcpy(a2->rules_row_dev, ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    S_HIP(a1, hipMemcpy(a1->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    S_HIP(a1, hipMemcpy(a2->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   // agent 2's failures are reported on agent 1's handle, the one the caller asks
   auto on2 = [&](nz_status st) {
@@ -3356,43 +3328,34 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
     // one kernel, two networks: the attribute is the kernel's, so it must cover the larger of the two launches
     S_HIP(a1, hipFuncSetAttribute((const void*)a1->persist_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)std::max(r1.persist_lds, r2.persist_lds)));
-  if (!a1->match_forced) {
-    const bool ok = dalloc(a1, &a1->match_forced, (size_t)2 * G) && dalloc(a1, &a1->match_actions, (size_t)G * MAX_MOVES) &&
-                    dalloc(a1, &a1->match_state, (size_t)3) && dalloc(a1, &a1->match_tally, (size_t)8);
-    if (!ok) return sfail(a1, NZ_ERR_HIP, "device allocation failed");
-    S_HIP(a1, hipHostMalloc((void**)&a1->match_pinned, 3 * sizeof(int32_t), hipHostMallocDefault));
-    S_HIP(a1, hipStreamCreateWithFlags(&a1->match_stream, hipStreamNonBlocking));
-    S_HIP(a1, hipEventCreateWithFlags(&a1->ev_fork, hipEventDisableTiming));
-    S_HIP(a1, hipEventCreateWithFlags(&a1->ev_join, hipEventDisableTiming));
-  }
+  MatchBufs& m = a1->match;
+  if (!m.ensure((size_t)G, (size_t)MAX_MOVES)) return sfail(a1, NZ_ERR_HIP, "allocation failed (match buffers, stream, events)");
   // The two searches of a decision are independent: agent 2's runs on a stream of its own between a fork and a join
   // event.  One stream when the agents share a network object (the wave-by-wave route evaluates in the network's own
   // buffers) or for the A/B measurement (NZ_SCS_MATCH_STREAMS=1, scripts/time_scs_match.py).
   const char* env_streams = getenv("NZ_SCS_MATCH_STREAMS");
   const bool two_streams = net1 != net2 && !(env_streams && atoi(env_streams) == 1);
-  hipStream_t s2 = two_streams ? a1->match_stream : s1;
-  int32_t* const forced1 = a1->match_forced;
-  int32_t* const forced2 = a1->match_forced + G;
+  hipStream_t s2 = two_streams ? m.stream.get() : s1;
+  int32_t* const forced1 = m.forced.get();
+  int32_t* const forced2 = m.forced.get() + G;
   if (nz_status st = nz_scs_search_reset(a1, stream)) return st;
   if (nz_status st = on2(nz_scs_search_reset(a2, stream))) return st;
-  S_HIP(a1, hipMemsetAsync(a1->match_actions, 0xFF, (size_t)G * MAX_MOVES * sizeof(int32_t), s1));    // -1: not played
+  S_HIP(a1, hipMemsetAsync(m.actions.get(), 0xFF, (size_t)G * MAX_MOVES * sizeof(int32_t), s1));    // -1: not played
   a1->waves = a2->waves = 0;
   a1->round_games = a2->round_games = 0;
   const MatchSide m1 = match_side(a1->p), m2 = match_side(a2->p);
   const dim3 grid1((G + 127) / 128), block1(128);
   const int move_limit = max_moves > 0 && max_moves < MAX_MOVES ? max_moves : MAX_MOVES;
   auto state_check = [&](int32_t* live) -> nz_status {   // the decision's one wait: live matches and both engines' flags
-    S_HIP(a1, hipMemsetAsync(a1->match_state, 0, 3 * sizeof(int32_t), s1));
-    hipLaunchKernelGGL(match_live_kernel, grid1, block1, 0, s1, m1, m2, G, a1->match_state);
-    S_HIP(a1, hipMemcpyAsync(a1->match_pinned, a1->match_state, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s1));
+    S_HIP(a1, hipMemsetAsync(m.state.get(), 0, 3 * sizeof(int32_t), s1));
+    hipLaunchKernelGGL(match_live_kernel, grid1, block1, 0, s1, m1, m2, G, m.state.get());
+    S_HIP(a1, hipMemcpyAsync(m.pinned.get(), m.state.get(), 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s1));
     S_HIP(a1, hipStreamSynchronize(s1));
-    const int32_t f1 = a1->match_pinned[1], f2 = a1->match_pinned[2];
+    const int32_t f1 = m.pinned[1], f2 = m.pinned[2];
     if (f1 & 64) return sfail(a1, NZ_ERR_STATE, "internal: the two engines no longer hold the same games");
     if (f1 || f2)
-      return sfail(a1, NZ_ERR_OVERFLOW, "device check failed (agent 1 flag %d, agent 2 flag %d: 1 arena full, 2 visit table/path too "
-                   "short, 4 move ended before its search, 8 forced action is not legal, 16 more legal actions than the bound "
-                   "computed at create, 32 game longer than that bound)", f1, f2);
-    *live = a1->match_pinned[0];
+      return sfail(a1, NZ_ERR_OVERFLOW, "device check failed (agent 1 flag %d, agent 2 flag %d: %s)", f1, f2, FLAG_TEXT);
+    *live = m.pinned[0];
     return NZ_OK;
   };
   nz_status st = NZ_OK;
@@ -3401,8 +3364,8 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
     if ((st = state_check(&live)) != NZ_OK) return st;
     if (live == 0) break;
     if (two_streams) {
-      S_HIP(a1, hipEventRecord(a1->ev_fork, s1));
-      S_HIP(a1, hipStreamWaitEvent(s2, a1->ev_fork, 0));
+      S_HIP(a1, hipEventRecord(m.ev_fork.get(), s1));
+      S_HIP(a1, hipStreamWaitEvent(s2, m.ev_fork.get(), 0));
     }
     // a persistent search is one launch; a wave-by-wave one keeps the host until its last wave: enqueue the former first
     if (!r1.persist && r2.persist) {
@@ -3417,10 +3380,10 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
       return st;
     }
     if (two_streams) {
-      S_HIP(a1, hipEventRecord(a1->ev_join, s2));
-      S_HIP(a1, hipStreamWaitEvent(s1, a1->ev_join, 0));
+      S_HIP(a1, hipEventRecord(m.ev_join.get(), s2));
+      S_HIP(a1, hipStreamWaitEvent(s1, m.ev_join.get(), 0));
     }
-    hipLaunchKernelGGL(match_handover_kernel, grid1, block1, 0, s1, m1, m2, G, MAX_MOVES, forced1, forced2, a1->match_actions);
+    hipLaunchKernelGGL(match_handover_kernel, grid1, block1, 0, s1, m1, m2, G, MAX_MOVES, forced1, forced2, m.actions.get());
     const dim3 grid_end((G + 63) / 64), block_end(64);
     hipLaunchKernelGGL(end_move_kernel, grid_end, block_end, 0, s1, a1->p, (const double*)nullptr, (const int32_t*)forced1);
     hipLaunchKernelGGL(compact_kernel, dim3(G), dim3(64), 0, s1, a1->p);
@@ -3428,8 +3391,8 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
     hipLaunchKernelGGL(compact_kernel, dim3(G), dim3(64), 0, s1, a2->p);
     S_HIP(a1, hipGetLastError());
   }
-  play_finish(a1);
-  play_finish(a2);
+  rest_counters(a1);
+  rest_counters(a2);
   int32_t live = 0;
   if ((st = state_check(&live)) != NZ_OK) return st;     // (the last decision's flags)
   a1->match_peer = a2;
@@ -3443,14 +3406,14 @@ extern "C" nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, n
   S_HIP(a1, hipSetDevice(a1->device));
   hipStream_t s = (hipStream_t)stream;
   const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
-  S_HIP(a1, hipMemsetAsync(a1->match_tally, 0, 8 * sizeof(int64_t), s));
+  S_HIP(a1, hipMemsetAsync(a1->match.tally.get(), 0, 8 * sizeof(int64_t), s));
   hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(a1->p), match_side(a2->p), G, MAX_MOVES,
-                     (const int32_t*)a1->match_actions, (unsigned long long*)a1->match_tally);
+                     (const int32_t*)a1->match.actions.get(), (unsigned long long*)a1->match.tally.get());
   S_HIP(a1, hipGetLastError());
   int64_t t[8];
-  S_HIP(a1, hipMemcpyAsync(t, a1->match_tally, sizeof(t), hipMemcpyDeviceToHost, s));
+  S_HIP(a1, hipMemcpyAsync(t, a1->match.tally.get(), sizeof(t), hipMemcpyDeviceToHost, s));
   if (actions_dev)
-    S_HIP(a1, hipMemcpyAsync(actions_dev, a1->match_actions, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    S_HIP(a1, hipMemcpyAsync(actions_dev, a1->match.actions.get(), (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   S_HIP(a1, hipStreamSynchronize(s));
   if (t[7] != 0)
     return sfail(a1, NZ_ERR_STATE, "internal: in %lld matches the two engines' records and the match record disagree", (long long)t[7]);
