@@ -551,6 +551,55 @@ nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search*
 nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, nz_scs_match_tally* out_host, int32_t* actions_dev,
                               void* stream);
 
+/* ---- evaluation matches against scripted agents on SCS, played inside the library ----------------------------------
+ * The cheaper tests a training run schedules (the bare policy against a random mover, MCTS against
+ * a random mover, MCTS against the bare policy), n_games matches at once on ONE handle.  Agent p1 moves when the game's
+ * player index is 1, p2 otherwise (as nz_scs_match_play).  The reference's Testing/Agents sources are not restated
+ * anywhere in this repository: the two scripted agents follow harness rules (parity unpinned):
+ *   NZ_AGENT_POLICY  at its own decisions evaluates the current position with `net` (its recurrent iterations as set)
+ *                    and plays the legal action with the largest softmax probability, the lowest flat action index
+ *                    winning a tie (np.argmax); no search, no tree, nothing on the opponent's turn;
+ *   NZ_AGENT_RANDOM  match i owns the stream np.random.RandomState(seeds_host[i]) (uint32 [n_games]; apart from the
+ *                    map's stream); at its own decision with n legal actions it draws k = rs.randint(n) (the legacy
+ *                    masked rejection on 32-bit words; n == 1 draws nothing) and plays the k-th legal action in
+ *                    ascending flat action index; nothing is drawn on the opponent's turn;
+ *   NZ_AGENT_MCTS    `h`'s own search with `net` (training = 0, keep_subtree = 1; the persistent route where available,
+ *                    exactly as nz_scs_search_play decides; nz_scs_search_persistent / _record / _cache work as there):
+ *                    it searches on every ply (its own choose_action, the opponent's update_subtree) and follows the
+ *                    scripted mover's action through nz_scs_search_apply's forced actions.
+ * At most one side is NZ_AGENT_MCTS; two are refused with NZ_ERR_ARG (each MCTS agent needs its own trees:
+ * nz_scs_match_play).  Without an MCTS side no simulation runs at all: the agents' kernel steps the games and keeps
+ * the handle's action record, and the trees stay the unexpanded roots of the reset.  Per decision, for all live
+ * matches, on the device: the MCTS side's search; each policy agent's positions written into its network's input rows
+ * and evaluated on a device-side count, one side after the other on `stream`, so the two sides may share one network
+ * object in any pairing (policy against policy included); one wavefront per match decides for the scripted mover.  The
+ * host waits once per decision, for the count of live matches, the engine's error flag and the agents' error words
+ * (a randint rejection cap or a live position without a legal action is NZ_ERR_OVERFLOW).  Per-game maps: as set on
+ * `h`.
+ * max_moves > 0 stops every match after that many decisions.  Resets `h`; the random agents' streams are rebuilt from
+ * the seeds, so a round is a function of its arguments.  Synchronises.  Afterwards nz_scs_search_status / _export read
+ * `h` as after nz_scs_search_play (a handle without an MCTS side holds the actions only, and 0 simulations).
+ * nz_scs_agent_match_result: the tally and the match record as nz_scs_match_result gives them.
+ * nz_scs_agent_match_decisions: a scripted side's (0: p1, 1: p2) decisions by the game's decision number, device
+ * pointers [n_games][M] (M of nz_scs_search_limits), any may be NULL: actions (-1 where the side did not decide), the
+ * legal actions it chose from, and for the policy agent the winning probability.
+ * nz_scs_agent_record / _record_read: the test hook of nz_scs_search_record / _record_read for a policy side -- the
+ * (digest, probs, value) rows of the chosen matches in the order the agent consumed them. */
+enum { NZ_AGENT_MCTS = 0, NZ_AGENT_POLICY = 1, NZ_AGENT_RANDOM = 2 };
+typedef struct nz_scs_agent {
+  int32_t kind;
+  nz_boardnet* net;            /* policy and MCTS agents */
+  const uint32_t* seeds_host;  /* random agents: [n_games] */
+} nz_scs_agent;
+nz_status nz_scs_agent_match_play(nz_scs_search* h, const nz_scs_agent* p1, const nz_scs_agent* p2, int32_t max_moves,
+                                  void* stream);
+nz_status nz_scs_agent_match_result(nz_scs_search* h, nz_scs_match_tally* out_host, int32_t* actions_dev, void* stream);
+nz_status nz_scs_agent_match_decisions(nz_scs_search* h, int32_t side, int32_t* actions_dev, int32_t* n_legal_dev,
+                                       float* probs_dev, void* stream);
+nz_status nz_scs_agent_record(nz_scs_search* h, int32_t side, const int32_t* games_host, int32_t n, int32_t capacity);
+nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, int32_t slot, int32_t* count, uint64_t* digests_host,
+                                   float* probs_host, float* values_host);
+
 /* ---- host random streams (numpy legacy RandomState, MT19937) --------------
  * Replaces the reference's use of the global np.random stream
  * (Explorer.py:77-78,89,199,208). */

@@ -68,6 +68,13 @@ class ScsMatchTally(Structure):
     _fields_ = [(k, c_int64) for k in ("matches", "p1_wins", "p2_wins", "draws", "unfinished", "length_sum", "length_max")]
 
 
+NZ_AGENT_MCTS, NZ_AGENT_POLICY, NZ_AGENT_RANDOM = 0, 1, 2
+
+
+class ScsAgent(Structure):
+    _fields_ = [("kind", c_int32), ("net", c_void_p), ("seeds_host", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/nuzero_amd.h declares
 SIGNATURES = {
     "nz_version": (c_char_p, []),
@@ -159,6 +166,11 @@ SIGNATURES = {
     "nz_scs_search_phase_ticks": (c_int32, [c_void_p, POINTER(c_int64)]),
     "nz_scs_match_play": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "nz_scs_match_result": (c_int32, [c_void_p, c_void_p, POINTER(ScsMatchTally), c_void_p, c_void_p]),
+    "nz_scs_agent_match_play": (c_int32, [c_void_p, POINTER(ScsAgent), POINTER(ScsAgent), c_int32, c_void_p]),
+    "nz_scs_agent_match_result": (c_int32, [c_void_p, POINTER(ScsMatchTally), c_void_p, c_void_p]),
+    "nz_scs_agent_match_decisions": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_scs_agent_record": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32]),
+    "nz_scs_agent_record_read": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "nz_replay_create": (c_int32, [POINTER(c_void_p), c_int64, c_int32, c_int32, c_int32]),
     "nz_replay_destroy": (None, [c_void_p]),
     "nz_replay_last_error": (c_char_p, [c_void_p]),

@@ -95,6 +95,26 @@ __host__ __device__ inline void scs_map_digest(const ScsRules& r, uint64_t out[2
   out[1] = mix64(d.b ^ (d.a << 9));
 }
 
+// 128-bit digest of a position's float32 planes [channels][tiles], element (c, t) read with at(c, t): order-free sums
+// of per-element mixes, so any lane order gives the same value (tests/scs_replay.py image_mix_digest is its twin).  All
+// 64 lanes call it together; every lane gets the digest.
+template <typename At>
+__device__ __forceinline__ void scs_image_digest_wave(At&& at, int channels, int tiles, int lane, uint64_t& hi, uint64_t& lo) {
+  uint64_t a = 0, b = 0;
+  for (int i = lane; i < channels * tiles; i += 64) {
+    const int c = i / tiles, t = i - c * tiles;
+    const uint64_t v = ((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, at(c, t));
+    a += mix64(v ^ 0x9e3779b97f4a7c15ull);
+    b += mix64(v * 0xd6e8feb86659fd93ull + 0x2545f4914f6cdd1dull);
+  }
+  for (int o = 32; o; o >>= 1) {
+    a += __shfl_xor((unsigned long long)a, o, 64);
+    b += __shfl_xor((unsigned long long)b, o, 64);
+  }
+  hi = mix64(a ^ (b >> 7));
+  lo = mix64(b ^ (a << 9));
+}
+
 // What a "Randomized" config draws per game (nz_scs_map_draw, checked and copied by nz_scs_search_set_map_draw); a
 // kernel argument, so it has fixed bounds.
 constexpr int SCS_DRAW_MAX_TYPES = 32;

@@ -2,8 +2,8 @@
 //
 // Restates what SCS_Game.load_game_from_config draws (SCS_Game.py:1678-1738) when numpy's global stream was seeded
 // with the game's seed just before (Training/Gamer.py:52), i.e. nuzero_amd.scs.randomized_map with RandomState(seed):
-//   * MT19937 as numpy's legacy RandomState: init_genrand for an integer seed (rng_host.cpp's seed_state), the twist,
-//     tempering, random_sample = the 53-bit double (a >> 5, b >> 6);
+//   * MT19937 as numpy's legacy RandomState (scs_mt.hpp, shared with the random evaluation agent): init_genrand for an
+//     integer seed, the twist, tempering, random_sample = the 53-bit double;
 //   * a tile's terrain: choice(len(types), p=dist) = searchsorted(cdf, random_sample(), side='right') on the float64
 //     cdf the host computed with numpy itself (cdf = p.cumsum(); cdf /= cdf[-1]);
 //   * a victory point: (choice(range(rows)), choice(range of the side's columns)), redrawn while it repeats one already
@@ -17,72 +17,14 @@
 
 #include "../../include/nuzero_amd.h"
 #include "scs_dev.hpp"
+#include "scs_mt.hpp"
 
 namespace nz {
 namespace {
 
-constexpr int MT_N = 624, MT_M = 397;
-// Bounds of the data-dependent loops.  A masked randint attempt succeeds with probability > 1/2, and the host refuses
-// more victory points than a side has cells, so neither bound is reached by a valid config; reaching one sets
-// SCS_DRAW_ERR_CAP for the game instead of spinning.
-constexpr int RANDINT_TRIES = 256;
+// Bound of the redraw loop: the host refuses more victory points than a side has cells, so a valid config never reaches
+// it (nor MT_RANDINT_TRIES, scs_mt.hpp); reaching one sets SCS_DRAW_ERR_CAP for the game instead of spinning.
 constexpr int VP_REDRAWS = 1 << 16;
-
-// The state lives in LDS (key) and in every lane's registers (pos); all lanes step it identically.
-struct Mt {
-  uint32_t* key;
-  int pos;
-  int lane;
-};
-
-// The MT19937 twist over the wavefront: word i needs the old i + 1 and, for i < 227, the old i + 397, else the NEW
-// i - 227 (and word 623 the new word 0).  In 64-word chunks taken in order, every read of a chunk sees the right
-// generation when all of the chunk's reads come before its writes: i + 397 is not yet rewritten, i - 227 lies in an
-// earlier chunk.
-__device__ void mt_twist(uint32_t* k, int lane) {
-  for (int c = 0; c < MT_N; c += 64) {
-    const int i = c + lane;
-    uint32_t v = 0;
-    if (i < MT_N) {
-      const uint32_t y = (k[i] & 0x80000000u) | (k[i + 1 < MT_N ? i + 1 : 0] & 0x7fffffffu);
-      v = k[i < MT_N - MT_M ? i + MT_M : i - (MT_N - MT_M)] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    __syncthreads();
-    if (i < MT_N) k[i] = v;
-    __syncthreads();
-  }
-}
-
-__device__ uint32_t mt_u32(Mt& m) {
-  if (m.pos == MT_N) {
-    mt_twist(m.key, m.lane);
-    m.pos = 0;
-  }
-  uint32_t y = m.key[m.pos++];
-  y ^= y >> 11;
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= y >> 18;
-  return y;
-}
-
-__device__ double mt_double(Mt& m) {
-  const uint32_t a = mt_u32(m) >> 5, b = mt_u32(m) >> 6;
-  return (a * 67108864.0 + b) / 9007199254740992.0;
-}
-
-// legacy randint(0, n) (choice(range(n))): -1 when the attempts ran out
-__device__ int mt_randint(Mt& m, int n) {
-  if (n <= 1) return 0;
-  const uint32_t rng = (uint32_t)(n - 1);
-  uint32_t mask = rng;
-  mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-  for (int t = 0; t < RANDINT_TRIES; ++t) {
-    const uint32_t v = mt_u32(m) & mask;
-    if (v <= rng) return (int)v;
-  }
-  return -1;
-}
 
 __global__ __launch_bounds__(64) void scs_draw_kernel(ScsDrawSpec sp, const ScsRules* __restrict__ tmpl, int64_t n,
                                                       const uint32_t* __restrict__ seeds, ScsRules* __restrict__ rows,
@@ -103,13 +45,7 @@ __global__ __launch_bounds__(64) void scs_draw_kernel(ScsDrawSpec sp, const ScsR
     uint64_t* dst = reinterpret_cast<uint64_t*>(&row);
     for (int i = lane; i < (int)(sizeof(ScsRules) / 8); i += 64) dst[i] = src[i];
   }
-  if (lane == 0) {
-    uint32_t s = seeds[g];
-    for (int i = 0; i < MT_N; ++i) {
-      key[i] = s;
-      s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)i + 1u;
-    }
-  }
+  mt_seed(key, seeds[g], lane);
   __syncthreads();
   // the template's map: what the sections the config gives in "Detailed" form stay
   const int T = row.tiles, cols = row.cols, nv0 = row.n_vp[0], nv = row.n_vp[0] + row.n_vp[1];

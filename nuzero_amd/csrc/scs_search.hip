@@ -29,6 +29,7 @@
 
 #include "../../include/nuzero_amd.h"
 #include "scs_dev.hpp"
+#include "scs_agents.hpp"
 #include "boardnet_internal.h"
 #include "hip_own.hpp"
 
@@ -787,22 +788,9 @@ constexpr int PERSIST_GAME_BYTES = 2 * PERSIST_STATE_BYTES + PERSIST_MASK_BYTES 
 constexpr int PERSIST_RULES_BYTES = (int)((sizeof(ScsRules) + 15) / 16 * 16);
 typedef const __attribute__((address_space(1))) u32x4* gptr4u;
 
-// 128-bit digest of a leaf's float32 planes [channels][tiles] as they sit in the staging rows ([tile][inp]); order-free
-// sums of per-element mixes, so any lane order gives the same value (tests/scs_replay.py image_mix_digest is its twin)
+// 128-bit digest of a leaf's float32 planes [channels][tiles] as they sit in the staging rows ([tile][inp])
 __device__ __forceinline__ void image_hash_wave(const float* stage, int inp, int channels, int tiles, int lane, uint64_t& hi, uint64_t& lo) {
-  uint64_t a = 0, b = 0;
-  for (int i = lane; i < channels * tiles; i += 64) {
-    const int c = i / tiles, t = i - c * tiles;
-    const uint64_t v = ((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, stage[t * inp + c]);
-    a += mix64(v ^ 0x9e3779b97f4a7c15ull);
-    b += mix64(v * 0xd6e8feb86659fd93ull + 0x2545f4914f6cdd1dull);
-  }
-  for (int o = 32; o; o >>= 1) {
-    a += __shfl_xor((unsigned long long)a, o, 64);
-    b += __shfl_xor((unsigned long long)b, o, 64);
-  }
-  hi = mix64(a ^ (b >> 7));
-  lo = mix64(b ^ (a << 9));
+  scs_image_digest_wave([&](int c, int t) { return stage[t * inp + c]; }, channels, tiles, lane, hi, lo);
 }
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
@@ -2097,6 +2085,46 @@ struct MatchBufs {                // nz_scs_match_play, kept on agent 1's handle
   }
 };
 
+struct AgentSideBufs {            // one scripted side of nz_scs_agent_match_play
+  DevBuf<uint32_t> seeds, mt_keys;               // random agent: the matches' seeds and MT19937 states
+  DevBuf<int32_t> mt_pos, count;
+  DevBuf<float> probs, value;                    // policy agent: this decision's evaluations by slot
+  DevBuf<int32_t> rec_action, rec_n_legal;       // the side's decisions [G][max_moves]
+  DevBuf<float> rec_prob;
+  // nz_scs_agent_record: the policy agent's evaluations of chosen matches
+  DevBuf<int32_t> hook_slot, hook_count;
+  DevBuf<uint64_t> hook_digest;
+  DevBuf<float> hook_probs, hook_value;
+  int32_t hook_slots = 0, hook_cap = 0;
+  // what a side of `kind` needs (an MCTS side: nothing); the hook's arrays are nz_scs_agent_record's
+  bool ensure(int kind, size_t G, size_t M, size_t A) {
+    if (kind == NZ_AGENT_MCTS) return true;
+    if (kind == NZ_AGENT_RANDOM && !(seeds.ensure(G) && mt_keys.ensure(G * 624) && mt_pos.ensure(G))) return false;
+    if (kind == NZ_AGENT_POLICY && !(count.ensure(1) && probs.ensure(G * A) && value.ensure(G))) return false;
+    return rec_action.ensure(G * M) && rec_n_legal.ensure(G * M) && rec_prob.ensure(G * M);
+  }
+  void bind(AgentSide& s) const {
+    s.probs = probs.get(); s.value = value.get(); s.count = count.get(); s.mt_keys = mt_keys.get(); s.mt_pos = mt_pos.get();
+    s.rec_action = rec_action.get(); s.rec_n_legal = rec_n_legal.get(); s.rec_prob = rec_prob.get();
+    s.hook_slot = hook_slots > 0 ? hook_slot.get() : nullptr; s.hook_cap = hook_cap; s.hook_count = hook_count.get();
+    s.hook_digest = hook_digest.get(); s.hook_probs = hook_probs.get(); s.hook_value = hook_value.get();
+  }
+};
+
+struct AgentBufs {                // nz_scs_agent_match_play
+  AgentSideBufs side[2];
+  // the forced actions of end_move [G], each match's evaluation slot [G] and error word [G], live matches and flags [3]
+  DevBuf<int32_t> forced, slot, err, state;
+  DevBuf<uint64_t> digest;        // [G][2]
+  DevBuf<int64_t> tally;          // [8]
+  PinnedBuf<int32_t> pinned;
+  int32_t kinds[2] = {-1, -1};    // of the last round; -1: none was played
+  bool ensure(const int kind[2], size_t G, size_t M, size_t A) {
+    return side[0].ensure(kind[0], G, M, A) && side[1].ensure(kind[1], G, M, A) && forced.ensure(G) && slot.ensure(G) && err.ensure(G) && state.ensure(3) &&
+           digest.ensure(G * 2) && tally.ensure(8) && pinned.ensure(3);
+  }
+};
+
 }  // namespace
 
 struct nz_scs_search {
@@ -2140,6 +2168,7 @@ struct nz_scs_search {
   int64_t n_drawn = 0;                        // games of the last draw; 0 when the games were set otherwise
   MatchBufs match;
   const nz_scs_search* match_peer = nullptr;    // agent 2 of the last round (compared, never followed)
+  AgentBufs agents;
 };
 
 namespace {
@@ -3249,7 +3278,8 @@ __global__ void match_handover_kernel(MatchSide a, MatchSide b, int n, int max_m
 
 // tally [8] (zeroed by the host): matches, wins of player 1 (terminal value +1), wins of player 2 (-1), draws,
 // unfinished (stopped at max_moves), sum and maximum of the match lengths, and the matches in which the two engines'
-// records or the match record disagree (a result with any of those is refused)
+// records or the match record disagree or the record has a gap (a result with any of those is refused).  A round on one
+// engine (nz_scs_agent_match_play) has no second side: b.real is null and `actions` is a's own record.
 __global__ void match_tally_kernel(MatchSide a, MatchSide b, int n, int max_moves, const int32_t* __restrict__ actions,
                                    unsigned long long* __restrict__ tally) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3261,10 +3291,11 @@ __global__ void match_tally_kernel(MatchSide a, MatchSide b, int n, int max_move
     length = st.length;
     value = st.terminal_value;
     done = st.terminal != 0;
-    bad = !match_in_step(st, b.real[g]) || length > max_moves;
+    const bool two = b.real != nullptr;
+    bad = (two && !match_in_step(st, b.real[g])) || length > max_moves;
     for (int m = 0; m < length && !bad; ++m) {
       const size_t at = (size_t)g * max_moves + m;
-      bad = a.rec_action[at] != actions[at] || b.rec_action[at] != actions[at] || actions[at] < 0;
+      bad = actions[at] < 0 || (two && (a.rec_action[at] != actions[at] || b.rec_action[at] != actions[at]));
     }
   }
   const int n_in = __popcll(__ballot(in)), n_p1 = __popcll(__ballot(in && done && value > 0)),
@@ -3421,5 +3452,222 @@ extern "C" nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, n
     out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
     out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
   }
+  return NZ_OK;
+}
+
+// ---- evaluation matches against scripted agents (nz_scs_agent_match_play) ----------------------------------------------
+// Tester.Test_using_agents where at most one side is an MctsAgent: the other sides are the bare policy or a random mover
+// (scs_agents.hip).  `h` holds the games; its own search is the MCTS side, which searches on every ply (the mover's
+// choose_action, the opponent's update_subtree) and takes the scripted mover's action through end_move_kernel's forced
+// actions.  Without an MCTS side no simulation runs: the agents' kernel steps the games itself and the handle's trees
+// stay the unexpanded roots of its reset.
+namespace {
+void agent_args(nz_scs_search* h, AgentArgs* a) {
+  AgentBufs& b = h->agents;
+  const ScsRules& R = h->host_rules;
+  a->rules = h->p.rules; a->rules_row = h->p.rules_row; a->real = h->p.real;
+  a->n_games = h->n_games; a->max_moves = h->p.max_moves; a->num_actions = R.planes * R.tiles;
+  a->forced = b.forced.get(); a->rec_action = h->p.rec_action; a->slot = b.slot.get(); a->digest = b.digest.get(); a->err = b.err.get();
+  for (int i = 0; i < 2; ++i) b.side[i].bind(a->side[i]);
+}
+}  // namespace
+
+extern "C" nz_status nz_scs_agent_match_play(nz_scs_search* h, const nz_scs_agent* p1, const nz_scs_agent* p2, int32_t max_moves,
+                                             void* stream) {
+  if (!h || !p1 || !p2) return sfail(h, NZ_ERR_ARG, "null argument");
+  const nz_scs_agent* const ag[2] = {p1, p2};
+  h->agents.kinds[0] = h->agents.kinds[1] = -1;
+  int mcts = -1;
+  for (int i = 0; i < 2; ++i) {
+    const int kind = ag[i]->kind;
+    if (kind != NZ_AGENT_MCTS && kind != NZ_AGENT_POLICY && kind != NZ_AGENT_RANDOM) return sfail(h, NZ_ERR_ARG, "agent %d: unknown kind %d", i + 1, kind);
+    if (kind != NZ_AGENT_RANDOM && !ag[i]->net) return sfail(h, NZ_ERR_ARG, "agent %d: a policy or MCTS agent needs a network", i + 1);
+    if (kind == NZ_AGENT_RANDOM && !ag[i]->seeds_host) return sfail(h, NZ_ERR_ARG, "agent %d: a random agent needs one seed per match", i + 1);
+    if (kind == NZ_AGENT_MCTS) {
+      if (mcts >= 0)
+        return sfail(h, NZ_ERR_ARG, "both agents are MCTS agents: each needs a handle of its own, use nz_scs_match_play");
+      mcts = i;
+    }
+  }
+  if (mcts >= 0 && h->cfg.training) return sfail(h, NZ_ERR_ARG, "evaluation agents are training = 0 engines (MctsAgent.py:14-20)");
+  if (mcts >= 0 && !h->cfg.keep_subtree) return sfail(h, NZ_ERR_ARG, "the MCTS agent keeps its subtree (keep_subtree = 1)");
+  S_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int G = h->n_games, MAX_MOVES = h->p.max_moves;
+  const ScsRules& R = h->host_rules;
+  const size_t A = (size_t)R.planes * R.tiles, GM = (size_t)G * MAX_MOVES;
+  if (R.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", R.planes);
+  if (h->n_game_rows > 0) {                    // every match on its own map
+    if (h->n_game_rows < G) return sfail(h, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)h->n_game_rows);
+    std::vector<int32_t> ident(G);
+    for (int g = 0; g < G; ++g) ident[g] = g;
+    S_HIP(h, hipStreamSynchronize(s));
+    S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  AgentBufs& b = h->agents;
+  const int kinds[2] = {p1->kind, p2->kind};
+  if (!b.ensure(kinds, (size_t)G, (size_t)MAX_MOVES, A)) return sfail(h, NZ_ERR_HIP, "allocation failed (agent buffers)");
+  PlayRoute route;
+  if (mcts >= 0) {
+    if (nz_status st = play_prepare(h, ag[mcts]->net, &route, stream)) return st;
+  } else {
+    h->persist_used = 0;
+  }
+  AgentArgs a{};
+  agent_args(h, &a);
+  a.step = mcts < 0 ? 1 : 0;
+  for (int i = 0; i < 2; ++i) {
+    AgentSide& sd = a.side[i];
+    sd.kind = ag[i]->kind;
+    if (sd.kind == NZ_AGENT_POLICY) {          // the network fits the game and holds every match's position
+      int32_t nin = 0, npol = 0, nrows = 0, ncols = 0, nmax = 0;
+      if (nz_boardnet_dims(ag[i]->net, &nin, &npol, &nrows, &ncols, &nmax) != NZ_OK) return sfail(h, NZ_ERR_ARG, "agent %d: bad network handle", i + 1);
+      if (nin != R.channels || npol != R.planes || nrows != R.rows || ncols != R.cols)
+        return sfail(h, NZ_ERR_ARG, "agent %d: network is %d planes -> %d planes on %dx%d, the game needs %d -> %d on %dx%d", i + 1, nin, npol,
+                     nrows, ncols, R.channels, R.planes, R.rows, R.cols);
+      if (nmax < G) return sfail(h, NZ_ERR_ARG, "agent %d: network max_batch %d < %d matches", i + 1, nmax, G);
+      if (nz_boardnet_input_rows(ag[i]->net, &sd.net_rows, &sd.row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "agent %d: bad network handle", i + 1);
+    }
+  }
+  if (nz_status st = nz_scs_search_reset(h, stream)) return st;
+  h->waves = 0;
+  h->round_games = 0;
+  h->match_peer = nullptr;
+  // the scripted sides' streams (rebuilt from the seeds every round) and records
+  for (int i = 0; i < 2; ++i) {
+    AgentSideBufs& sb = b.side[i];
+    if (ag[i]->kind == NZ_AGENT_MCTS) continue;
+    if (ag[i]->kind == NZ_AGENT_RANDOM) {
+      S_HIP(h, hipMemcpyAsync(sb.seeds.get(), ag[i]->seeds_host, (size_t)G * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      S_HIP(h, agent_seed_launch(sb.seeds.get(), sb.mt_keys.get(), sb.mt_pos.get(), G, s));
+    }
+    S_HIP(h, hipMemsetAsync(sb.rec_action.get(), 0xFF, GM * sizeof(int32_t), s));     // -1: not this side's decision
+    S_HIP(h, hipMemsetAsync(sb.rec_n_legal.get(), 0, GM * sizeof(int32_t), s));
+    S_HIP(h, hipMemsetAsync(sb.rec_prob.get(), 0, GM * sizeof(float), s));
+    if (sb.hook_slots > 0) S_HIP(h, hipMemsetAsync(sb.hook_count.get(), 0, (size_t)sb.hook_slots * sizeof(int32_t), s));
+  }
+  S_HIP(h, hipMemsetAsync(b.err.get(), 0, (size_t)G * sizeof(int32_t), s));
+  S_HIP(h, hipStreamSynchronize(s));           // (the seeds are the caller's memory)
+  const int move_limit = max_moves > 0 && max_moves < MAX_MOVES ? max_moves : MAX_MOVES;
+  auto state_check = [&](int32_t* live) -> nz_status {   // the decision's one wait: live matches, the engine's flag, the agents' error words
+    S_HIP(h, hipMemsetAsync(b.state.get(), 0, 3 * sizeof(int32_t), s));
+    S_HIP(h, agent_live_launch(h->p.real, G, h->p.error_flag, b.err.get(), b.state.get(), s));
+    S_HIP(h, hipMemcpyAsync(b.pinned.get(), b.state.get(), 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    S_HIP(h, hipStreamSynchronize(s));
+    if (b.pinned[1]) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s)", b.pinned[1], FLAG_TEXT);
+    if (b.pinned[2])
+      return sfail(h, NZ_ERR_OVERFLOW, "scripted agent check failed (flags %d: 1 randint rejection cap, 2 no legal action, "
+                   "4 game longer than the bound computed at create)", b.pinned[2]);
+    *live = b.pinned[0];
+    return NZ_OK;
+  };
+  nz_status st = NZ_OK;
+  for (int move = 0; move < move_limit; ++move) {
+    int32_t live = 0;
+    if ((st = state_check(&live)) != NZ_OK) return st;
+    if (live == 0) break;
+    if (mcts >= 0 && (st = search_move(h, ag[mcts]->net, route, s)) != NZ_OK) return st;
+    // The positions a policy agent decides go straight into its network's input rows; the count stays on the device.
+    // Side by side on the one stream: two policy agents may share a network, whose input rows hold one side's
+    // positions at a time (the evaluations land in the side's own probs / value).
+    for (int i = 0; i < 2; ++i) {
+      if (ag[i]->kind != NZ_AGENT_POLICY) continue;
+      S_HIP(h, hipMemsetAsync(b.side[i].count.get(), 0, sizeof(int32_t), s));
+      S_HIP(h, agent_image_launch(a, i, s));
+      if (nz_boardnet_forward_rows(ag[i]->net, G, b.side[i].count.get(), nullptr, b.side[i].probs.get(), b.side[i].value.get(), stream) != NZ_OK)
+        return sfail(h, NZ_ERR_HIP, "agent %d's network: %s", i + 1, nz_boardnet_last_error(ag[i]->net));
+    }
+    S_HIP(h, agent_act_launch(a, s));
+    if (mcts >= 0) {
+      hipLaunchKernelGGL(end_move_kernel, dim3((G + 63) / 64), dim3(64), 0, s, h->p, (const double*)nullptr, (const int32_t*)b.forced.get());
+      hipLaunchKernelGGL(compact_kernel, dim3(G), dim3(64), 0, s, h->p);
+      S_HIP(h, hipGetLastError());
+    }
+  }
+  rest_counters(h);
+  int32_t live = 0;
+  if ((st = state_check(&live)) != NZ_OK) return st;     // (the last decision's flags)
+  b.kinds[0] = p1->kind;
+  b.kinds[1] = p2->kind;
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_agent_match_result(nz_scs_search* h, nz_scs_match_tally* out_host, int32_t* actions_dev, void* stream) {
+  if (!h) return sfail(h, NZ_ERR_ARG, "null argument");
+  if (h->agents.kinds[0] < 0) return sfail(h, NZ_ERR_STATE, "no agent match round was played on this handle");
+  S_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int G = h->n_games, MAX_MOVES = h->p.max_moves;
+  S_HIP(h, hipMemsetAsync(h->agents.tally.get(), 0, 8 * sizeof(int64_t), s));
+  hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(h->p), MatchSide{}, G, MAX_MOVES,
+                     (const int32_t*)h->p.rec_action, (unsigned long long*)h->agents.tally.get());
+  S_HIP(h, hipGetLastError());
+  int64_t t[8];
+  S_HIP(h, hipMemcpyAsync(t, h->agents.tally.get(), sizeof(t), hipMemcpyDeviceToHost, s));
+  if (actions_dev)
+    S_HIP(h, hipMemcpyAsync(actions_dev, h->p.rec_action, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  if (t[7] != 0) return sfail(h, NZ_ERR_STATE, "internal: the action record of %lld matches has a gap", (long long)t[7]);
+  if (out_host) {
+    out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
+    out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
+  }
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_agent_match_decisions(nz_scs_search* h, int32_t side, int32_t* actions_dev, int32_t* n_legal_dev,
+                                                  float* probs_dev, void* stream) {
+  if (!h || side < 0 || side > 1) return sfail(h, NZ_ERR_ARG, "bad argument");
+  if (h->agents.kinds[0] < 0) return sfail(h, NZ_ERR_STATE, "no agent match round was played on this handle");
+  if (h->agents.kinds[side] == NZ_AGENT_MCTS) return sfail(h, NZ_ERR_ARG, "agent %d is the MCTS agent: read it with nz_scs_search_export", side + 1);
+  S_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  const AgentSideBufs& sb = h->agents.side[side];
+  const size_t GM = (size_t)h->n_games * h->p.max_moves;
+  if (actions_dev) S_HIP(h, hipMemcpyAsync(actions_dev, sb.rec_action.get(), GM * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (n_legal_dev) S_HIP(h, hipMemcpyAsync(n_legal_dev, sb.rec_n_legal.get(), GM * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (probs_dev) S_HIP(h, hipMemcpyAsync(probs_dev, sb.rec_prob.get(), GM * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return NZ_OK;
+}
+
+// Test hook: keep the policy agent's evaluations (digest of the planes, post-softmax probabilities, value) of `n` matches,
+// up to `capacity` each, in the order the agent consumed them.  n = 0: stop recording.
+extern "C" nz_status nz_scs_agent_record(nz_scs_search* h, int32_t side, const int32_t* games_host, int32_t n, int32_t capacity) {
+  if (!h || side < 0 || side > 1 || n < 0 || (n > 0 && (!games_host || capacity <= 0))) return sfail(h, NZ_ERR_ARG, "bad argument");
+  S_HIP(h, hipSetDevice(h->device));
+  S_HIP(h, hipDeviceSynchronize());
+  AgentSideBufs& sb = h->agents.side[side];
+  sb.hook_slots = sb.hook_cap = 0;
+  sb.hook_slot.reset(); sb.hook_count.reset(); sb.hook_digest.reset(); sb.hook_probs.reset(); sb.hook_value.reset();
+  if (n == 0) return NZ_OK;
+  std::vector<int32_t> slot(h->n_games, -1);
+  for (int i = 0; i < n; ++i) {
+    if (games_host[i] < 0 || games_host[i] >= h->n_games) return sfail(h, NZ_ERR_ARG, "no match %d", games_host[i]);
+    slot[games_host[i]] = i;
+  }
+  const size_t N = (size_t)n * capacity, A = (size_t)h->p.num_actions;
+  if (!(sb.hook_slot.ensure(slot.size()) && sb.hook_count.ensure(n) && sb.hook_digest.ensure(N * 2) && sb.hook_probs.ensure(N * A) &&
+        sb.hook_value.ensure(N))) {
+    sb.hook_slot.reset(); sb.hook_count.reset(); sb.hook_digest.reset(); sb.hook_probs.reset(); sb.hook_value.reset();
+    return sfail(h, NZ_ERR_HIP, "device allocation failed (recording %d matches x %d evaluations)", n, capacity);
+  }
+  S_HIP(h, hipMemcpy(sb.hook_slot.get(), slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
+  S_HIP(h, hipMemset(sb.hook_count.get(), 0, (size_t)n * 4));
+  sb.hook_slots = n;
+  sb.hook_cap = capacity;
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, int32_t slot, int32_t* count, uint64_t* digests_host,
+                                              float* probs_host, float* values_host) {
+  if (!h || side < 0 || side > 1 || !count || slot < 0 || slot >= h->agents.side[side].hook_slots) return sfail(h, NZ_ERR_ARG, "bad argument");
+  S_HIP(h, hipSetDevice(h->device));
+  S_HIP(h, hipDeviceSynchronize());
+  const AgentSideBufs& sb = h->agents.side[side];
+  S_HIP(h, hipMemcpy(count, sb.hook_count.get() + slot, 4, hipMemcpyDeviceToHost));
+  const size_t n = (size_t)std::min(*count, sb.hook_cap), A = (size_t)h->p.num_actions, at = (size_t)slot * sb.hook_cap;
+  if (digests_host) S_HIP(h, hipMemcpy(digests_host, sb.hook_digest.get() + 2 * at, n * 16, hipMemcpyDeviceToHost));
+  if (probs_host) S_HIP(h, hipMemcpy(probs_host, sb.hook_probs.get() + at * A, n * A * 4, hipMemcpyDeviceToHost));
+  if (values_host) S_HIP(h, hipMemcpy(values_host, sb.hook_value.get() + at, n * 4, hipMemcpyDeviceToHost));
   return NZ_OK;
 }

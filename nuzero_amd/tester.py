@@ -12,12 +12,20 @@ Evaluation agents are deterministic (no noise, max action), so matches on ONE ma
 means something on the reference's "Randomized" presets, `ScsGameConfig(path, per_game=True)`, one map per match
 drawn on the device from `seeds`.
 
-Out of scope: `RandomAgent`, `PolicyAgent` and SCS's scripted agents (only what oracle/agents.py restates of the
-reference's agents is built; the other agents' random draw order is not pinned anywhere in this repository), and
-Tic-Tac-Toe (two deterministic agents play ONE game there: the two-engine loop of INTEGRATION.md section 5 covers
-it, and there is no per-match variety to batch).
+Cheaper opponents (C ABI nz_scs_agent_match_*): `ScsAgentMatch` plays the same rounds on ONE engine when at most one
+side is an MCTS agent and the others are the bare policy `("policy",)` or a random mover `("random",)` -- the
+trainer's policy-vs-random, MCTS-vs-random and MCTS-vs-policy tests.  Their rules are harness rules (DESIGN.md section
+5b; the reference's Testing/Agents sources are not restated here, parity unpinned): the policy agent plays the legal
+action of largest softmax probability (lowest index on a tie, no search); the random agent of match i draws
+`RandomState(agent_seeds[i]).randint(n_legal)` at each of its own decisions and plays that legal action in ascending
+index.  `ScsTester.test_using_agents` takes these specs in place of a search config.
+
+Out of scope: SCS's scripted agents (the reference's hand-written SCS players), and Tic-Tac-Toe (two deterministic
+agents play ONE game there: the two-engine loop of INTEGRATION.md section 5 covers it, and there is no per-match
+variety to batch).
 """
-from ctypes import byref, c_void_p
+from collections.abc import Mapping
+from ctypes import byref, c_int32, c_void_p
 
 import numpy as np
 
@@ -91,21 +99,180 @@ class ScsMatch:
         return out
 
 
+def _agent_spec(spec):
+    """("mcts", search_cfg) | ("policy",) | ("random",) -> (kind, search config or None); a bare search config (any
+    mapping, as ScsMatch takes it) is an MCTS agent."""
+    if isinstance(spec, Mapping):
+        return "mcts", spec
+    if isinstance(spec, str):
+        spec = (spec,)
+    if not isinstance(spec, (tuple, list)) or not spec or spec[0] not in ("mcts", "policy", "random"):
+        raise ValueError(f"agent spec {spec!r}: (\"mcts\", search_cfg), (\"policy\",) or (\"random\",)")
+    if spec[0] == "mcts":
+        if len(spec) != 2 or not isinstance(spec[1], Mapping):
+            raise ValueError("an MCTS agent spec is (\"mcts\", search_cfg)")
+        return "mcts", spec[1]
+    if len(spec) != 1:
+        raise ValueError(f"agent spec {spec!r}: a {spec[0]} agent takes no arguments")
+    return spec[0], None
+
+
+# the search config of an engine that never searches (no MCTS side): the handle only holds the games.  Its tree arena
+# grows with the simulations per move, so one simulation keeps the unused arena at its smallest.
+_NO_SEARCH = {"Simulation": {"mcts_simulations": 1, "keep_subtree": True}, "UCT": {"pb_c_base": 10000, "pb_c_init": 1.15},
+              "Exploration": {"number_of_softmax_moves": 0, "epsilon_softmax_exploration": 0.0,
+                              "epsilon_random_exploration": 0.0, "value_factor": 1,
+                              "root_exploration_distribution": "gamma", "root_exploration_fraction": 0.0,
+                              "root_dist_alpha": 0.15, "root_dist_beta": 1}}
+
+
+class ScsAgentMatch:
+    """n_matches matches between agent1 (moves for player index 1) and agent2, at most one of them an MCTS agent:
+    specs ("mcts", search_cfg), ("policy",), ("random",).  `engine`: the one ScsSelfPlay that holds the games (the MCTS
+    side's search when there is one: persistent(), record(), cache(), status(), export() work as after play_native)."""
+
+    def __init__(self, config, agent1, agent2, n_matches, device=0):
+        from .scs import ScsGameConfig
+        self.kinds, cfgs = zip(*(_agent_spec(a) for a in (agent1, agent2)))
+        if self.kinds == ("mcts", "mcts"):
+            raise ValueError("two MCTS agents need an engine each: use ScsMatch")
+        for i, sc in enumerate(cfgs):
+            if sc is not None and not sc["Simulation"]["keep_subtree"]:
+                raise ValueError(f"agent {i + 1}: keep_subtree = False is not supported (an MctsAgent that drops its "
+                                 "tree never re-roots, MctsAgent.py:28-39; every shipped search config keeps it)")
+        if int(n_matches) <= 0:
+            raise ValueError("n_matches must be positive")
+        self.cfg = config if isinstance(config, ScsGameConfig) else ScsGameConfig(config)
+        self.n_matches = int(n_matches)
+        self.search_cfg = next((sc for sc in cfgs if sc is not None), None)
+        from .scs import ScsSelfPlay              # (needs the GPU from here on)
+        self.engine = ScsSelfPlay(self.cfg, self.search_cfg or _NO_SEARCH, self.n_matches, training=False, device=device)
+        self._recorded = ([], [])
+
+    def close(self):
+        self.engine.close()
+
+    def _check_play(self, nets, seeds, agent_seeds):
+        """What play() refuses before any GPU call; returns (map seeds, per-side uint32 seed arrays or None)."""
+        for i, (kind, net) in enumerate(zip(self.kinds, nets)):
+            if kind != "random" and net is None:
+                raise ValueError(f"agent {i + 1}: a {kind} agent needs a network")
+        n_random = self.kinds.count("random")
+        per_side = [None, None]
+        if n_random:
+            if agent_seeds is None:
+                raise ValueError("a random agent draws from RandomState(agent_seeds[i]) in match i: pass agent_seeds")
+            given = list(agent_seeds)
+            if n_random == 2 and len(given) == 2 and all(hasattr(x, "__len__") for x in given):
+                sides = [list(given[0]), list(given[1])]        # one list per random side
+            else:
+                sides = [given, given]
+            for i, kind in enumerate(self.kinds):
+                if kind != "random":
+                    continue
+                if len(sides[i]) != self.n_matches:
+                    raise ValueError(f"agent {i + 1}: {len(sides[i])} agent_seeds for {self.n_matches} matches")
+                from .scs import _seed_array
+                per_side[i] = _seed_array(sides[i])
+        if self.cfg.per_game:
+            if seeds is None:
+                raise ValueError("a per_game config draws one map per match: pass seeds")
+            seeds = list(seeds)
+            if len(seeds) != self.n_matches:
+                raise ValueError(f"{len(seeds)} seeds for {self.n_matches} matches")
+        return seeds, per_side
+
+    def play(self, net1, net2, seeds=None, agent_seeds=None, max_moves=None):
+        """One round, as ScsMatch.play.  net1 / net2: the BoardNet of a policy or MCTS side (None for a random side).
+        `agent_seeds` (random sides: required, one per match; with two random sides one list for both or a pair of
+        lists): match i's random agent is RandomState(agent_seeds[i]), rebuilt every round.  Returns ScsMatch.play's
+        dict plus "agent_actions" / "agent_n_legal": per side int32 [N, T] by decision number (-1 / 0 where the side
+        did not decide; None for the MCTS side), and "agent_probs" (the policy agent's winning probabilities)."""
+        import torch
+        from . import _lib
+        nets = (net1, net2)
+        seeds, side_seeds = self._check_play(nets, seeds, agent_seeds)
+        e = self.engine
+        if self.cfg.per_game:
+            e.set_games(seeds)
+        code = {"mcts": _lib.NZ_AGENT_MCTS, "policy": _lib.NZ_AGENT_POLICY, "random": _lib.NZ_AGENT_RANDOM}
+        ag = [_lib.ScsAgent(kind=code[k], net=(n._h if k != "random" else None),
+                            seeds_host=(s.ctypes.data if s is not None else None))
+              for k, n, s in zip(self.kinds, nets, side_seeds)]
+        stream = c_void_p(torch.cuda.current_stream().cuda_stream)
+        e._check(_lib.lib.nz_scs_agent_match_play(e._h, byref(ag[0]), byref(ag[1]), int(max_moves or 0), stream))
+        tally = _lib.ScsMatchTally()
+        actions = torch.empty((self.n_matches, e.MAX_MOVES), dtype=torch.int32, device=e.device)
+        e._check(_lib.lib.nz_scs_agent_match_result(e._h, byref(tally), c_void_p(actions.data_ptr()), stream))
+        st = e.status()
+        out = {k: int(getattr(tally, k)) for k, _ in _lib.ScsMatchTally._fields_}
+        T = max(1, out["length_max"])
+        out["actions"] = actions[:, :T].cpu().numpy()
+        out["lengths"], out["outcomes"] = st[:, 6].copy(), st[:, 5].copy()
+        out["agent_actions"], out["agent_n_legal"], out["agent_probs"] = [None, None], [None, None], [None, None]
+        for i, kind in enumerate(self.kinds):
+            if kind == "mcts":
+                continue
+            a = torch.empty((self.n_matches, e.MAX_MOVES), dtype=torch.int32, device=e.device)
+            n = torch.empty_like(a)
+            p = torch.empty((self.n_matches, e.MAX_MOVES), dtype=torch.float32, device=e.device)
+            e._check(_lib.lib.nz_scs_agent_match_decisions(e._h, i, c_void_p(a.data_ptr()), c_void_p(n.data_ptr()),
+                                                           c_void_p(p.data_ptr()), stream))
+            out["agent_actions"][i], out["agent_n_legal"][i] = a[:, :T].cpu().numpy(), n[:, :T].cpu().numpy()
+            out["agent_probs"][i] = p[:, :T].cpu().numpy()
+        return out
+
+    # ---- test hook: a policy side's evaluations in the order consumed (nz_scs_agent_record) ----
+    def record(self, side, games, capacity):
+        from . import _lib
+        games = np.ascontiguousarray(np.asarray(list(games), dtype=np.int32))
+        self._recorded[side][:] = [int(g) for g in games]
+        self.engine._check(_lib.lib.nz_scs_agent_record(self.engine._h, int(side), c_void_p(games.ctypes.data), len(games),
+                                                        int(capacity)))
+        self._record_capacity = int(capacity)
+
+    def records(self, side):
+        """{match: (digests uint64 [n, 2], probs float32 [n, A], values float32 [n])} of the recorded matches."""
+        from . import _lib
+        out, A, e = {}, self.cfg.planes * self.cfg.rows * self.cfg.cols, self.engine
+        for slot, g in enumerate(self._recorded[side]):
+            count = c_int32(0)
+            e._check(_lib.lib.nz_scs_agent_record_read(e._h, int(side), slot, byref(count), None, None, None))
+            if count.value > self._record_capacity:
+                raise RuntimeError(f"match {g} consumed {count.value} evaluations, capacity {self._record_capacity}")
+            n = count.value
+            dig, pr, va = np.empty((n, 2), np.uint64), np.empty((n, A), np.float32), np.empty((n,), np.float32)
+            e._check(_lib.lib.nz_scs_agent_record_read(e._h, int(side), slot, byref(count), c_void_p(dig.ctypes.data),
+                                                       c_void_p(pr.ctypes.data), c_void_p(va.ctypes.data)))
+            out[g] = (dig, pr, va)
+        return out
+
+
 class ScsTester:
-    """The shape of the reference's Tester for SCS: `test_using_agents` plays n matches between two MCTS agents and
-    returns (p1_wins, p2_wins, draws), as Test_using_agents counts them over n games (Tester.py:46-121)."""
+    """The shape of the reference's Tester for SCS: `test_using_agents` plays n matches between two agents and returns
+    (p1_wins, p2_wins, draws), as Test_using_agents counts them over n games (Tester.py:46-121).  An agent is a search
+    config (an MCTS agent, as before) or a spec ("mcts", search_cfg) / ("policy",) / ("random",); two MCTS agents play
+    on ScsMatch, every other pairing on ScsAgentMatch."""
 
     def __init__(self, config, device=0):
         self.config, self.device = config, device
         self._match = None
 
-    def test_using_agents(self, search_cfg_1, net1, search_cfg_2, net2, n, seeds=None, max_moves=None):
-        key = (repr(search_cfg_1), repr(search_cfg_2), int(n))
+    def test_using_agents(self, search_cfg_1, net1, search_cfg_2, net2, n, seeds=None, max_moves=None, agent_seeds=None):
+        (k1, c1), (k2, c2) = _agent_spec(search_cfg_1), _agent_spec(search_cfg_2)
+        scripted = (k1, k2) != ("mcts", "mcts")
+        key = (repr((k1, c1)), repr((k2, c2)), int(n)) if scripted else (repr(search_cfg_1), repr(search_cfg_2), int(n))
         if self._match is None or self._match[0] != key:
             if self._match is not None:
                 self._match[1].close()
-            self._match = (key, ScsMatch(self.config, search_cfg_1, search_cfg_2, n, device=self.device))
-        r = self._match[1].play(net1, net2, seeds=seeds, max_moves=max_moves)
+                self._match = None
+            m = (ScsAgentMatch(self.config, (k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device)
+                 if scripted else ScsMatch(self.config, c1, c2, n, device=self.device))
+            self._match = (key, m)
+        if scripted:
+            r = self._match[1].play(net1, net2, seeds=seeds, agent_seeds=agent_seeds, max_moves=max_moves)
+        else:
+            r = self._match[1].play(net1, net2, seeds=seeds, max_moves=max_moves)
         return r["p1_wins"], r["p2_wins"], r["draws"]
 
     Test_using_agents = test_using_agents
