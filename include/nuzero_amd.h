@@ -239,6 +239,18 @@ nz_status nz_engine_net_flops(const nz_engine* e, double* flops_host);
  * planes (f32_flops). */
 nz_status nz_engine_net_matrix_flops(const nz_engine* e, double* bf16_flops_host, double* f32_flops_host);
 
+/* The job lists the fused network kernel runs for `net` (what nz_engine_set_weights compiles; host only, no device is
+ * touched): one row of NZ_NET_JOB_FIELDS int32 per job -- wave, stage, output-cell group, the group's cells (bit o =
+ * cell o), K groups, first source slot (-1: split over a buffer and the strip), source buffer, destination (0, 1:
+ * activation buffers, 2: policy logits, 3: value, 4: the strip), residual buffer or -1, activation (0 none, 1 relu,
+ * 2 tanh, 3 elu), destination tile, 1 if the input planes are read, 1 if the job's epilogue is issued cell by cell
+ * inside its K loop.  Writes at most max_jobs rows and sets *n_jobs to the number of jobs. */
+#define NZ_NET_JOB_FIELDS 13
+nz_status nz_net_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t* jobs, int32_t max_jobs,
+                         int32_t* n_jobs);
+/* last conv tap (0..8, row-major over (dy, dx) in -1..1) that reaches output cell `cell` of the 3x3 board; -1: no such cell */
+int32_t nz_net_final_tap(int32_t cell);
+
 /* ---- stand-alone operators (same kernels, callable by themselves) ---------
  * Network_Manager.inference for a batch (Network_Manager.py:46-64):
  * states float[B][C][3][3] -> logits float[B][P*9], value float[B]; and the

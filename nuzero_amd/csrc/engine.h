@@ -138,9 +138,27 @@ struct NetJob {
   int8_t src, dst;     // activation buffers 0..1; dst NET_DST_POLICY / NET_DST_VALUE = network outputs
   int8_t res;          // residual buffer or -1
   int8_t act;          // 0 none, 1 relu, 2 tanh, 3 elu
-  int8_t stage_end;    // 1: workgroup barrier after this job
+  int8_t flags;        // NET_JOB_STAGE_END | NET_JOB_PROGRESSIVE
   int8_t dtile;        // 16-channel tile of the destination rows the epilogue writes (dst a buffer or the strip)
 };
+constexpr int NET_JOB_STAGE_END = 1;     // NetJob::flags: workgroup barrier after this job
+// NetJob::flags: the epilogue of each output cell that is final before the K loop's last tap is issued between the
+// MFMAs of the remaining taps (net_dev.hpp ProgEpi).  The cell's LDS rows are then written while the job still reads
+// operands, so the host sets it only where no job of the stage reads, as an MFMA operand, an area the job writes.
+constexpr int NET_JOB_PROGRESSIVE = 2;
+// cells (bit o) of output-cell group og (net_dev.hpp)
+__host__ __device__ constexpr int og_mask(int og) {
+  return og == 0 ? 0x1FF : og == 1 ? 0x011 : og == 2 ? 0x00A : og == 3 ? 0x0A0 : og == 4 ? 0x144 :
+         og == 5 ? 0x02F : og == 6 ? 0x1D0 : 0;
+}
+// last tap (0..8, tap = 3 (dy + 1) + (dx + 1), input cell = output cell + (dy, dx)) that reaches output cell o of the 3x3 board
+__host__ __device__ constexpr int net_final_tap(int o) {
+  return 3 * ((o / 3 < 2 ? 1 : 0) + 1) + ((o % 3 < 2 ? 1 : 0) + 1);
+}
+// The groups the kernel has the progressive form for: the late half {4,6,7,8} and the quarters {5,7} {2,6,8}, whose
+// epilogues nothing else on their SIMD covers.  (The early half {0,1,2,3,5} has two early cells and three pairs after
+// them, and its epilogue already runs under the late half's MFMAs; the other quarters have no early cell.)
+__host__ __device__ constexpr bool net_og_progressive(int cells) { return cells == 0x1D0 || cells == 0x0A0 || cells == 0x144; }
 constexpr int NET_WAVES_HOST = 8;
 constexpr int NET_MAX_JOBS = 192;
 constexpr int OG_NONE = 7;

@@ -264,6 +264,25 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
     if (u.job.dst == NET_DST_STRIP && (u.job.dtile != 0 || u.job.act != 1 || u.job.res >= 0)) return false;
     if (u.job.sslot == NET_SSLOT_SPLIT && u.job.kgroups != 1) return false;
   }
+  // Progressive epilogue (NET_JOB_PROGRESSIVE, net_dev.hpp ProgEpi): the job writes an output cell's rows while its own K
+  // loop, and the other jobs' of the stage, still read MFMA operands.  Hazard rule: allowed only if no job of the stage
+  // reads an area the job writes -- areas are the activation buffers and the strip; a K loop reads its source buffer
+  // (and the strip for NET_SSLOT_SPLIT).  The residual is no operand: it is read by the wave that writes those very
+  // channels and cells, in program order, so residual blocks qualify (their source is the other buffer).  The kernel
+  // has the form for ReLU (with or without residual) and tanh into a buffer, for K loops without the input-plane step
+  // (whose MFMAs come after the last tap), and for the groups of net_og_progressive; policy and value
+  // outputs, the strip, ELU and everything else keep the end-of-job epilogue.
+  unsigned read_areas = 0;   // bit b: buffer b; bit NET_ACT_BUFFERS: the strip
+  for (const Unit& u : units) {
+    if (u.job.kgroups > 0) read_areas |= 1u << u.job.src;
+    if (u.job.sslot == NET_SSLOT_SPLIT) read_areas |= 1u << NET_ACT_BUFFERS;
+  }
+  for (Unit& u : units) {
+    NetJob& j = u.job;
+    const bool form = j.dst >= 0 && j.dst < NET_ACT_BUFFERS && j.kgroups >= 1 && !j.extra && j.sslot != NET_SSLOT_SPLIT &&
+                      net_og_progressive(og_mask(j.og)) && (j.res >= 0 ? j.act == 1 : (j.act == 1 || j.act == 2));
+    if (form && !((read_areas >> j.dst) & 1)) j.flags |= NET_JOB_PROGRESSIVE;
+  }
   int load[NET_WAVES_HOST];
   std::vector<int> who(units.size());
   deal(units, load, who.data());
@@ -281,9 +300,113 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
       j.og = OG_NONE;
       pg.jobs[w][pg.n_jobs[w]++] = j;
     }
-    pg.jobs[w][pg.n_jobs[w] - 1].stage_end = 1;
+    pg.jobs[w][pg.n_jobs[w] - 1].flags |= NET_JOB_STAGE_END;
   }
   return true;
+}
+
+// What nz_engine_set_weights derives from the description alone: no device, no weight values.
+struct ConvShape { int cout, cin, k; };
+struct NetLayout {
+  bool recall;
+  int iterations, trunk_tensors, trunk_k;
+  std::vector<ConvShape> shapes;                 // in state_dict order
+  int cin_main(int i, int in_planes) const {     // channels read from an activation buffer; the rest are the input planes
+    const bool with_planes = (i == 0) || (recall && i == 1);
+    return with_planes ? shapes[i].cin - in_planes : shapes[i].cin;
+  }
+};
+std::string text(const char* fmt, ...) {
+  char buf[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return buf;
+}
+// "" or what is wrong with the description
+std::string net_layout(const nz_net_desc* net, int recurrent_iterations, NetLayout& L) {
+  if (net->hex) return "hexagonal convolutions are built for nz_boardnet_* only";
+  if (net->in_channels != 2 || net->policy_channels != 1) return "Tic-Tac-Toe nets take 2 input planes and 1 policy plane";
+  if (net->width <= 0 || net->width > 64 || net->width % 4 != 0) return "width must be a multiple of 4 in (0, 64]";
+  if (net->num_blocks < 0 || recurrent_iterations < 0) return "negative block/iteration count";
+  const int arch = net->arch;
+  if (arch != NZ_ARCH_RECURRENT && arch != NZ_ARCH_RESNET && arch != NZ_ARCH_CONVNET) return text("unknown architecture %d", arch);
+  L.trunk_k = arch == NZ_ARCH_CONVNET ? net->kernel_size : 3;
+  if (L.trunk_k != 1 && L.trunk_k != 3) return "ConvNet kernel_size must be 1 or 3";
+  L.recall = arch == NZ_ARCH_RECURRENT && net->recall;
+  L.iterations = arch == NZ_ARCH_RECURRENT ? recurrent_iterations : 1;
+  L.trunk_tensors = arch == NZ_ARCH_CONVNET ? 1 + net->num_blocks : 1 + (L.recall ? 1 : 0) + 2 * net->num_blocks;
+  if (1 + L.iterations * (L.trunk_tensors - 1) + 24 > NET_MAX_JOBS)
+    return text("too many layers for one fused launch (%d iterations)", recurrent_iterations);
+  const int W = net->width, IN = net->in_channels;
+  std::vector<ConvShape>& shapes = L.shapes;
+  shapes.clear();
+  shapes.push_back({W, IN, L.trunk_k});
+  if (L.recall) shapes.push_back({W, W + IN, 3});
+  for (int i = (int)shapes.size(); i < L.trunk_tensors; ++i) shapes.push_back({W, W, L.trunk_k});
+  for (int i = 0; i < 2; ++i)
+    shapes.push_back({head_channel(W, net->policy_channels, 2, i + 1), head_channel(W, net->policy_channels, 2, i), 3});
+  for (int i = 0; i < 4; ++i) shapes.push_back({head_channel(W, 1, 4, i + 1), head_channel(W, 1, 4, i), 3});
+  return "";
+}
+// The network as per-wave job lists (`convs`: the packed tensors' layout); `flops`: in-bounds taps only, 2 * Cout * Cin *
+// 49 per 3x3 conv application (9 for 1x1).  "" or why it does not fit one fused launch.
+std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::vector<PackedConv>& convs, NetProgram& pg,
+                        double& flops) {
+  const std::vector<ConvShape>& shapes = L.shapes;
+  const int arch = net->arch, trunk_tensors = L.trunk_tensors, iterations = L.iterations;
+  const bool recall = L.recall;
+  flops = 0.0;
+  // stages; activation buffers 0/1 ping-pong, `cur` holds the running trunk output.
+  // act: 1 relu, 2 tanh, 3 elu
+  memset(&pg, 0, sizeof(pg));
+  bool ok = true;
+  int cur = 0;
+  auto stage = [&](std::vector<StageConv> convs_in_stage) {
+    for (const StageConv& sc : convs_in_stage)
+      flops += 2.0 * shapes[sc.tensor].cout * shapes[sc.tensor].cin * (shapes[sc.tensor].k == 3 ? 49.0 : 9.0);
+    ok = ok && add_stage(pg, convs, convs_in_stage);
+  };
+  if (arch == NZ_ARCH_CONVNET) {                                      // ConvNet.py:20-40: (conv, ELU) x (1 + num_layers)
+    stage({{0, 0, cur, -1, 3, true}});
+    for (int i = 1; i < trunk_tensors; ++i) { stage({{i, cur, cur ^ 1, -1, 3, true}}); cur ^= 1; }
+  } else {
+    stage({{0, 0, cur, -1, 1, true}});                                // projection / input block + ReLU
+    const int first_block = recall ? 2 : 1;
+    for (int it = 0; it < iterations; ++it) {
+      if (recall) { stage({{1, cur, cur ^ 1, -1, 0, true}}); cur ^= 1; }    // cat([thought, x]) conv, no activation
+      for (int b = 0; b < net->num_blocks; ++b) {                         // relu(conv2(relu(conv1(t))) + t)
+        stage({{first_block + 2 * b, cur, cur ^ 1, -1, 1, true}});
+        stage({{first_block + 2 * b + 1, cur ^ 1, cur, cur, 1, true}});
+      }
+    }
+  }
+  const int ph = trunk_tensors, vh = ph + 2;
+  const int vact = net->value_activation == NZ_ACT_RELU ? 1 : 2;
+  const int side = cur ^ 1;
+  // The two heads side by side, four stages: both first convs read the trunk output, the value head's into `side`'s
+  // first tiles, the policy head's into the tiles after them and past the fourth into the strip (64 channels: 48 + 32
+  // = 3 + 2 tiles); then both second convs (the trunk output is dead: the value head's goes there), then the value
+  // head's last two.  The policy head's second conv reads its K group from where the first wrote it: slots 2 tv0.. of
+  // `side`, or slots 6-7 and the strip.
+  const int tv0 = convs[vh].ntiles, tp0 = convs[ph].ntiles;
+  if (tv0 + tp0 > 5 || (tv0 + tp0 == 5 && tv0 != 3)) return text("head layout: %d + %d tiles", tv0, tp0);
+  const int p1_sslot = tv0 + tp0 <= 4 ? 2 * tv0 : NET_SSLOT_SPLIT;
+  stage({{vh, cur, side, -1, vact, true, 0, 0}, {ph, cur, side, -1, 1, true, 0, tv0}});
+  stage({{vh + 1, side, cur, -1, vact, true}, {ph + 1, side, NET_DST_POLICY, -1, 0, true, p1_sslot, 0}});
+  stage({{vh + 2, cur, side, -1, vact, true}});
+  stage({{vh + 3, side, NET_DST_VALUE, -1, 0, true}});                      // per-cell outputs; net_tile takes the mean
+  if (!ok) return text("network too deep for one fused launch (%d iterations)", iterations);
+  for (int w = 0; w < NET_WAVES_HOST; ++w) {     // prefetch chain: each job names the next weight stream
+    int32_t next = -1;
+    for (int j = pg.n_jobs[w] - 1; j >= 0; --j) {
+      pg.jobs[w][j].next_w_off = next;
+      if (pg.jobs[w][j].og != OG_NONE && pg.jobs[w][j].kgroups > 0) next = pg.jobs[w][j].w_off;
+    }
+    pg.first_w_off[w] = next;
+  }
+  return "";
 }
 
 hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
@@ -452,36 +575,13 @@ nz_status nz_engine_dims(const nz_engine* e, nz_dims* out) {
 nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const float* const* weights,
                                 int32_t n_tensors, int32_t recurrent_iterations) {
   if (!e || !net || !weights) return NZ_ERR_ARG;
-  if (net->hex) return fail(e, NZ_ERR_ARG, "hexagonal convolutions are built for nz_boardnet_* only");
-  if (net->in_channels != 2 || net->policy_channels != 1)
-    return fail(e, NZ_ERR_ARG, "Tic-Tac-Toe nets take 2 input planes and 1 policy plane");
-  if (net->width <= 0 || net->width > 64 || net->width % 4 != 0)
-    return fail(e, NZ_ERR_ARG, "width must be a multiple of 4 in (0, 64]");
-  if (net->num_blocks < 0 || recurrent_iterations < 0) return fail(e, NZ_ERR_ARG, "negative block/iteration count");
-  const int arch = net->arch;
-  if (arch != NZ_ARCH_RECURRENT && arch != NZ_ARCH_RESNET && arch != NZ_ARCH_CONVNET)
-    return fail(e, NZ_ERR_ARG, "unknown architecture %d", arch);
-  const int trunk_k = arch == NZ_ARCH_CONVNET ? net->kernel_size : 3;
-  if (trunk_k != 1 && trunk_k != 3) return fail(e, NZ_ERR_ARG, "ConvNet kernel_size must be 1 or 3");
-  const bool recall = arch == NZ_ARCH_RECURRENT && net->recall;
-  const int iterations = arch == NZ_ARCH_RECURRENT ? recurrent_iterations : 1;
-  const int trunk_tensors = arch == NZ_ARCH_CONVNET ? 1 + net->num_blocks : 1 + (recall ? 1 : 0) + 2 * net->num_blocks;
-  const int expect = trunk_tensors + 2 + 4;
+  NetLayout L;
+  const std::string bad = net_layout(net, recurrent_iterations, L);
+  if (!bad.empty()) return fail(e, NZ_ERR_ARG, "%s", bad.c_str());
+  const int expect = (int)L.shapes.size();
   if (n_tensors != expect) return fail(e, NZ_ERR_ARG, "expected %d weight tensors, got %d", expect, n_tensors);
-  if (1 + iterations * (trunk_tensors - 1) + 24 > NET_MAX_JOBS)
-    return fail(e, NZ_ERR_ARG, "too many layers for one fused launch (%d iterations)", recurrent_iterations);
   NZ_HIP(e, hipSetDevice(e->device));
-
-  const int W = net->width, IN = net->in_channels;
-  // tensor shapes in state_dict order
-  struct Shape { int cout, cin, k; };
-  std::vector<Shape> shapes;
-  shapes.push_back({W, IN, trunk_k});
-  if (recall) shapes.push_back({W, W + IN, 3});
-  for (int i = (int)shapes.size(); i < trunk_tensors; ++i) shapes.push_back({W, W, trunk_k});
-  for (int i = 0; i < 2; ++i)
-    shapes.push_back({head_channel(W, net->policy_channels, 2, i + 1), head_channel(W, net->policy_channels, 2, i), 3});
-  for (int i = 0; i < 4; ++i) shapes.push_back({head_channel(W, 1, 4, i + 1), head_channel(W, 1, 4, i), 3});
+  const std::vector<ConvShape>& shapes = L.shapes;
 
   std::vector<std::vector<float>> host(n_tensors);
   for (int i = 0; i < n_tensors; ++i) {
@@ -498,62 +598,14 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
 
   std::vector<float> packed;
   std::vector<PackedConv> convs(n_tensors);
-  double flops = 0.0;   // in-bounds taps only: 2 * Cout * Cin * 49 per 3x3 conv application (9 for 1x1)
   for (int i = 0; i < n_tensors; ++i) {
-    const bool with_planes = (i == 0) || (recall && i == 1);
-    const int cin_main = with_planes ? shapes[i].cin - IN : shapes[i].cin;
-    convs[i] = pack_conv(host[i].data(), shapes[i].cout, shapes[i].cin, cin_main, packed);
+    convs[i] = pack_conv(host[i].data(), shapes[i].cout, shapes[i].cin, L.cin_main(i, net->in_channels), packed);
   }
 
-  // stages; activation buffers 0/1 ping-pong, `cur` holds the running trunk output.
-  // act: 1 relu, 2 tanh, 3 elu
   NetProgram& pg = e->prog_host;
-  memset(&pg, 0, sizeof(pg));
-  bool ok = true;
-  int cur = 0;
-  auto stage = [&](std::vector<StageConv> convs_in_stage) {
-    for (const StageConv& sc : convs_in_stage)
-      flops += 2.0 * shapes[sc.tensor].cout * shapes[sc.tensor].cin * (shapes[sc.tensor].k == 3 ? 49.0 : 9.0);
-    ok = ok && add_stage(pg, convs, convs_in_stage);
-  };
-  if (arch == NZ_ARCH_CONVNET) {                                      // ConvNet.py:20-40: (conv, ELU) x (1 + num_layers)
-    stage({{0, 0, cur, -1, 3, true}});
-    for (int i = 1; i < trunk_tensors; ++i) { stage({{i, cur, cur ^ 1, -1, 3, true}}); cur ^= 1; }
-  } else {
-    stage({{0, 0, cur, -1, 1, true}});                                // projection / input block + ReLU
-    const int first_block = recall ? 2 : 1;
-    for (int it = 0; it < iterations; ++it) {
-      if (recall) { stage({{1, cur, cur ^ 1, -1, 0, true}}); cur ^= 1; }    // cat([thought, x]) conv, no activation
-      for (int b = 0; b < net->num_blocks; ++b) {                         // relu(conv2(relu(conv1(t))) + t)
-        stage({{first_block + 2 * b, cur, cur ^ 1, -1, 1, true}});
-        stage({{first_block + 2 * b + 1, cur ^ 1, cur, cur, 1, true}});
-      }
-    }
-  }
-  const int ph = trunk_tensors, vh = ph + 2;
-  const int vact = net->value_activation == NZ_ACT_RELU ? 1 : 2;
-  const int side = cur ^ 1;
-  // The two heads side by side, four stages: both first convs read the trunk output, the value head's into `side`'s
-  // first tiles, the policy head's into the tiles after them and past the fourth into the strip (64 channels: 48 + 32
-  // = 3 + 2 tiles); then both second convs (the trunk output is dead: the value head's goes there), then the value
-  // head's last two.  The policy head's second conv reads its K group from where the first wrote it: slots 2 tv0.. of
-  // `side`, or slots 6-7 and the strip.
-  const int tv0 = convs[vh].ntiles, tp0 = convs[ph].ntiles;
-  if (tv0 + tp0 > 5 || (tv0 + tp0 == 5 && tv0 != 3)) return fail(e, NZ_ERR_ARG, "head layout: %d + %d tiles", tv0, tp0);
-  const int p1_sslot = tv0 + tp0 <= 4 ? 2 * tv0 : NET_SSLOT_SPLIT;
-  stage({{vh, cur, side, -1, vact, true, 0, 0}, {ph, cur, side, -1, 1, true, 0, tv0}});
-  stage({{vh + 1, side, cur, -1, vact, true}, {ph + 1, side, NET_DST_POLICY, -1, 0, true, p1_sslot, 0}});
-  stage({{vh + 2, cur, side, -1, vact, true}});
-  stage({{vh + 3, side, NET_DST_VALUE, -1, 0, true}});                      // per-cell outputs; net_tile takes the mean
-  if (!ok) return fail(e, NZ_ERR_ARG, "network too deep for one fused launch (%d iterations)", recurrent_iterations);
-  for (int w = 0; w < NET_WAVES_HOST; ++w) {     // prefetch chain: each job names the next weight stream
-    int32_t next = -1;
-    for (int j = pg.n_jobs[w] - 1; j >= 0; --j) {
-      pg.jobs[w][j].next_w_off = next;
-      if (pg.jobs[w][j].og != OG_NONE && pg.jobs[w][j].kgroups > 0) next = pg.jobs[w][j].w_off;
-    }
-    pg.first_w_off[w] = next;
-  }
+  double flops = 0.0;
+  const std::string deep = compile_net(net, L, convs, pg, flops);
+  if (!deep.empty()) return fail(e, NZ_ERR_ARG, "%s", deep.c_str());
   e->algorithmic_flops_per_position = flops;
   {   // what the matrix cores execute for one tile of 16 positions (net_dev.hpp): six bf16 MFMAs per
       // (input cell, tap) pair and 32-channel K group, one float32 MFMA per pair for the input planes
@@ -579,6 +631,51 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
   e->tp.table = nullptr;
   return NZ_OK;
 }
+
+nz_status nz_net_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t* jobs, int32_t max_jobs,
+                         int32_t* n_jobs) {
+  if (!net || !n_jobs || (!jobs && max_jobs > 0)) return NZ_ERR_ARG;
+  NetLayout L;
+  std::string bad = net_layout(net, recurrent_iterations, L);
+  std::vector<float> packed;
+  std::vector<PackedConv> convs(L.shapes.size());
+  NetProgram* pg = new NetProgram;
+  if (bad.empty()) {
+    for (size_t i = 0; i < L.shapes.size(); ++i) {   // the layout only: zero weights
+      const std::vector<float> zeros((size_t)L.shapes[i].cout * L.shapes[i].cin * 9, 0.f);
+      convs[i] = pack_conv(zeros.data(), L.shapes[i].cout, L.shapes[i].cin, L.cin_main((int)i, net->in_channels), packed);
+    }
+    double flops = 0.0;
+    bad = compile_net(net, L, convs, *pg, flops);
+  }
+  if (!bad.empty()) {
+    delete pg;
+    g_create_error = bad;
+    return NZ_ERR_ARG;
+  }
+  int32_t n = 0;
+  for (int w = 0; w < NET_WAVES_HOST; ++w) {
+    int stage = 0;
+    for (int j = 0; j < pg->n_jobs[w]; ++j) {
+      const NetJob& job = pg->jobs[w][j];
+      if (job.og != OG_NONE) {
+        if (n < max_jobs) {
+          const int32_t row[NZ_NET_JOB_FIELDS] = {w, stage, job.og, og_mask(job.og), job.kgroups, job.sslot, job.src, job.dst,
+                                                  job.res, job.act, job.dtile, job.extra,
+                                                  (job.flags & NET_JOB_PROGRESSIVE) ? 1 : 0};
+          memcpy(jobs + (size_t)n * NZ_NET_JOB_FIELDS, row, sizeof(row));
+        }
+        ++n;
+      }
+      if (job.flags & NET_JOB_STAGE_END) ++stage;
+    }
+  }
+  delete pg;
+  *n_jobs = n;
+  return NZ_OK;
+}
+
+int32_t nz_net_final_tap(int32_t cell) { return cell >= 0 && cell < 9 ? net_final_tap(cell) : -1; }
 
 nz_status nz_engine_set_table(nz_engine* e, const float* table, int32_t n_rows) {
   if (!e || !table) return NZ_ERR_ARG;

@@ -83,10 +83,7 @@ static_assert(NET_KG_DWORDS == 9 * TAP_DWORDS && NET_KG_CHANNELS == 32, "host pa
 // ((input cell, tap) pairs: 49 | 13, 12, 12, 12 | 26, 23).  The halves of a tile go to the two waves of a SIMD: the older
 // wave wins the matrix pipe, so its epilogue runs under the other's MFMAs and one epilogue is left when those end.
 // (An uneven 7 + 2 split leaves a shorter epilogue but measured the same and spilled four registers in the large job.)
-__host__ __device__ constexpr int og_mask(int og) {
-  return og == 0 ? 0x1FF : og == 1 ? 0x011 : og == 2 ? 0x00A : og == 3 ? 0x0A0 : og == 4 ? 0x144 :
-         og == 5 ? 0x02F : og == 6 ? 0x1D0 : 0;
-}
+// (og_mask: engine.h)
 
 // byte offset of the 16-byte slot holding channels 8 s .. 8 s + 7 of (cell, pos) inside one piece
 __device__ __forceinline__ int slot_addr(int cell, int pos, int s) {
@@ -126,6 +123,43 @@ constexpr int last_use() {
          pair_used<OMASK, I, 5>() ? 5 : pair_used<OMASK, I, 4>() ? 4 : pair_used<OMASK, I, 3>() ? 3 :
          pair_used<OMASK, I, 2>() ? 2 : pair_used<OMASK, I, 1>() ? 1 : 0;
 }
+// last valid tap of output cell O (engine.h net_final_tap): in the tap-major K loop the cell's accumulator is final once
+// that tap of the job's last K group has issued -- cell 8 after tap 4, cells 6, 7 after tap 5, cells 2, 5 after tap 7
+template <int OMASK, int O>
+constexpr int final_tap() {
+  static_assert((OMASK >> O) & 1, "cell of the job's group");
+  return net_final_tap(O);
+}
+static_assert(net_final_tap(8) == 4 && net_final_tap(6) == 5 && net_final_tap(7) == 5 && net_final_tap(2) == 7 &&
+              net_final_tap(5) == 7 && net_final_tap(0) == 8 && net_final_tap(1) == 8 && net_final_tap(3) == 8 &&
+              net_final_tap(4) == 8, "tap = 3 (dy + 1) + (dx + 1), input cell = output cell + (dy, dx)");
+// (input cell, tap) pairs of the group that issue before pair (I, TAP) in a K group (tap-major, input cells ascending);
+// pairs_before(omask, 9, 0): all of them
+constexpr int pairs_before(int omask, int tap, int i) {
+  int n = 0;
+  for (int t = 0; t < 9; ++t)
+    for (int c = 0; c < CELLS; ++c) {
+      const int oy = c / 3 - (t / 3 - 1), ox = c % 3 - (t % 3 - 1);
+      const bool used = oy >= 0 && oy < 3 && ox >= 0 && ox < 3 && ((omask >> (oy * 3 + ox)) & 1);
+      if (used && (t < tap || (t == tap && c < i))) ++n;
+    }
+  return n;
+}
+static_assert(pairs_before(0x1FF, 9, 0) == 49 && pairs_before(0x02F, 9, 0) == 26 && pairs_before(0x1D0, 9, 0) == 23, "og_mask");
+// The group's early cells -- final before tap 8 -- in the order they become final (then by index): how many, and the
+// qi-th of them (-1: none)
+constexpr int early_cell(int omask, int qi) {
+  for (int t = 0; t < 8; ++t)
+    for (int o = 0; o < CELLS; ++o)
+      if (((omask >> o) & 1) && net_final_tap(o) == t && qi-- == 0) return o;
+  return -1;
+}
+constexpr int early_cells(int omask) {
+  int n = 0;
+  while (early_cell(omask, n) >= 0) ++n;
+  return n;
+}
+
 // When cell I's operands of the SECOND K group are read, on a timeline of 18 steps (step s < 9: after tap s of the first
 // K group; step 9 + t: before tap t of the second): not before the first group is done with the registers, and not
 // earlier than REFILL_AHEAD taps before the second group needs them -- operands that sit in registers for a whole K
@@ -167,17 +201,24 @@ __device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast
 __device__ __forceinline__ f32x4 mfma_bf16(const u32x4& w, const u32x4& x, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
 }
-template <int OMASK, int I, int TAP>
-__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w) {
+// The K loop's MFMAs carry slots: slot g follows the g-th MFMA of a K group (in issue order) and runs whatever the
+// epilogue scheduler `e` has placed there (ProgEpi below; NoEpi: nothing, the chain is as before).
+struct NoEpi {
+  template <int G>
+  __device__ __forceinline__ void slot(const f32x4 (&)[CELLS]) {}
+};
+template <int OMASK, int I, int TAP, typename E>
+__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w, E& e) {
   if constexpr (pair_used<OMASK, I, TAP>()) {
     constexpr int o = TapMap<I, TAP>::o;
+    constexpr int g = 6 * pairs_before(OMASK, TAP, I);
     // small terms first; one accumulator chain issues at the full rate
-    acc[o] = mfma_bf16(w.p[1], x[I].p[1], acc[o]);
-    acc[o] = mfma_bf16(w.p[0], x[I].p[2], acc[o]);
-    acc[o] = mfma_bf16(w.p[2], x[I].p[0], acc[o]);
-    acc[o] = mfma_bf16(w.p[0], x[I].p[1], acc[o]);
-    acc[o] = mfma_bf16(w.p[1], x[I].p[0], acc[o]);
-    acc[o] = mfma_bf16(w.p[0], x[I].p[0], acc[o]);
+    acc[o] = mfma_bf16(w.p[1], x[I].p[1], acc[o]); e.template slot<g + 0>(acc);
+    acc[o] = mfma_bf16(w.p[0], x[I].p[2], acc[o]); e.template slot<g + 1>(acc);
+    acc[o] = mfma_bf16(w.p[2], x[I].p[0], acc[o]); e.template slot<g + 2>(acc);
+    acc[o] = mfma_bf16(w.p[0], x[I].p[1], acc[o]); e.template slot<g + 3>(acc);
+    acc[o] = mfma_bf16(w.p[1], x[I].p[0], acc[o]); e.template slot<g + 4>(acc);
+    acc[o] = mfma_bf16(w.p[0], x[I].p[0], acc[o]); e.template slot<g + 5>(acc);
     // keep the chain together: the scheduler would interleave it with the other pairs' chains, and
     // round-robin over accumulators issues at 21 cycles per MFMA instead of 16
     // (scripts/microbench/mfma_bf16_rate.hip)
@@ -185,11 +226,11 @@ __device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)
   }
 }
 // all (input cell, TAP) pairs of the job's output cells: independent accumulators
-template <int OMASK, int TAP>
-__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w) {
-  pair_mfma<OMASK, 0, TAP>(acc, x, w); pair_mfma<OMASK, 1, TAP>(acc, x, w); pair_mfma<OMASK, 2, TAP>(acc, x, w);
-  pair_mfma<OMASK, 3, TAP>(acc, x, w); pair_mfma<OMASK, 4, TAP>(acc, x, w); pair_mfma<OMASK, 5, TAP>(acc, x, w);
-  pair_mfma<OMASK, 6, TAP>(acc, x, w); pair_mfma<OMASK, 7, TAP>(acc, x, w); pair_mfma<OMASK, 8, TAP>(acc, x, w);
+template <int OMASK, int TAP, typename E>
+__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w, E& e) {
+  pair_mfma<OMASK, 0, TAP>(acc, x, w, e); pair_mfma<OMASK, 1, TAP>(acc, x, w, e); pair_mfma<OMASK, 2, TAP>(acc, x, w, e);
+  pair_mfma<OMASK, 3, TAP>(acc, x, w, e); pair_mfma<OMASK, 4, TAP>(acc, x, w, e); pair_mfma<OMASK, 5, TAP>(acc, x, w, e);
+  pair_mfma<OMASK, 6, TAP>(acc, x, w, e); pair_mfma<OMASK, 7, TAP>(acc, x, w, e); pair_mfma<OMASK, 8, TAP>(acc, x, w, e);
 }
 
 template <int OMASK, int I>
@@ -280,37 +321,38 @@ __device__ __forceinline__ void refill(Pieces (&x)[CELLS], const unsigned char* 
 // weight stream runs three taps ahead, also across jobs and stage barriers.  PART 1 / 2: the first / second K group of a
 // two-group job -- the activation operands of the second group are read in place (LDS slot address a1) at their
 // refill_step, some after a tap of the first group, the others before a tap of the second; PART 0: a one-group job.
-template <int OMASK, int PART>
+// `e`: the epilogue scheduler of the job's LAST K group (PART 0 / 2; NoEpi for PART 1).
+template <int OMASK, int PART, typename E>
 __device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Pieces (&x)[CELLS], FragS& f,
                                        const unsigned char* __restrict__ src, int a1,
-                                       const float* __restrict__ wc, const float* __restrict__ wn, int lane) {
+                                       const float* __restrict__ wc, const float* __restrict__ wn, int lane, E& e) {
   constexpr bool A = PART == 1, B = PART == 2;
   if constexpr (B) refill<OMASK, 9>(x, src, a1);
-  tap_mfma<OMASK, 0>(acc, x, f.rb[0]); load_tap(f.rb[0], wc + 3 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 0>(acc, x, f.rb[0], e); load_tap(f.rb[0], wc + 3 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 0>(x, src, a1);
   if constexpr (B) refill<OMASK, 10>(x, src, a1);
-  tap_mfma<OMASK, 1>(acc, x, f.rb[1]); load_tap(f.rb[1], wc + 4 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 1>(acc, x, f.rb[1], e); load_tap(f.rb[1], wc + 4 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 1>(x, src, a1);
   if constexpr (B) refill<OMASK, 11>(x, src, a1);
-  tap_mfma<OMASK, 2>(acc, x, f.rb[2]); load_tap(f.rb[2], wc + 5 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 2>(acc, x, f.rb[2], e); load_tap(f.rb[2], wc + 5 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 2>(x, src, a1);
   if constexpr (B) refill<OMASK, 12>(x, src, a1);
-  tap_mfma<OMASK, 3>(acc, x, f.rb[0]); load_tap(f.rb[0], wc + 6 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 3>(acc, x, f.rb[0], e); load_tap(f.rb[0], wc + 6 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 3>(x, src, a1);
   if constexpr (B) refill<OMASK, 13>(x, src, a1);
-  tap_mfma<OMASK, 4>(acc, x, f.rb[1]); load_tap(f.rb[1], wc + 7 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 4>(acc, x, f.rb[1], e); load_tap(f.rb[1], wc + 7 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 4>(x, src, a1);
   if constexpr (B) refill<OMASK, 14>(x, src, a1);
-  tap_mfma<OMASK, 5>(acc, x, f.rb[2]); load_tap(f.rb[2], wc + 8 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 5>(acc, x, f.rb[2], e); load_tap(f.rb[2], wc + 8 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 5>(x, src, a1);
   if constexpr (B) refill<OMASK, 15>(x, src, a1);
-  tap_mfma<OMASK, 6>(acc, x, f.rb[0]); load_tap(f.rb[0], wn + 0 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 6>(acc, x, f.rb[0], e); load_tap(f.rb[0], wn + 0 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 6>(x, src, a1);
   if constexpr (B) refill<OMASK, 16>(x, src, a1);
-  tap_mfma<OMASK, 7>(acc, x, f.rb[1]); load_tap(f.rb[1], wn + 1 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 7>(acc, x, f.rb[1], e); load_tap(f.rb[1], wn + 1 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 7>(x, src, a1);
   if constexpr (B) refill<OMASK, 17>(x, src, a1);
-  tap_mfma<OMASK, 8>(acc, x, f.rb[2]); load_tap(f.rb[2], wn + 2 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 8>(acc, x, f.rb[2], e); load_tap(f.rb[2], wn + 2 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 8>(x, src, a1);
 }
 // All K groups of one job as straight-line code (KG = 1 or 2: layers are at most 64 channels wide;
@@ -318,20 +360,21 @@ __device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Pieces (&x)[CELLS], 
 // ring holds the first three taps of the job's first K group; on exit those of the next job that reads
 // weights (`w_after`; the stream's start when there is none).  The K groups start at slot `sslot` of the source rows
 // (NET_SSLOT_SPLIT: one K group from two areas, load_cells_split).
-template <int OMASK, int KG>
+template <int OMASK, int KG, typename E>
 __device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragS& f, const unsigned char* __restrict__ src,
                                           const unsigned char* __restrict__ strip, int sslot,
-                                          const float* __restrict__ w, const float* __restrict__ w_after, int lane) {
+                                          const float* __restrict__ w, const float* __restrict__ w_after, int lane, E& e) {
   const int pos = lane & 15, quad = lane >> 4;
   Pieces x[CELLS];
   if (KG == 1 && sslot == NET_SSLOT_SPLIT) load_cells_split<OMASK>(x, src, strip, pos, quad);
   else load_cells<OMASK>(x, src, slot_addr(0, pos, sslot + quad));
   if constexpr (KG == 2) {
     const int a1 = slot_addr(0, pos, sslot + 4 + quad);
-    kgroup<OMASK, 1>(acc, x, f, src, a1, w, w + NET_KG_DWORDS, lane);
-    kgroup<OMASK, 2>(acc, x, f, src, a1, w + NET_KG_DWORDS, w_after, lane);
+    NoEpi none;
+    kgroup<OMASK, 1>(acc, x, f, src, a1, w, w + NET_KG_DWORDS, lane, none);
+    kgroup<OMASK, 2>(acc, x, f, src, a1, w + NET_KG_DWORDS, w_after, lane, e);
   } else {
-    kgroup<OMASK, 0>(acc, x, f, src, 0, w, w_after, lane);
+    kgroup<OMASK, 0>(acc, x, f, src, 0, w, w_after, lane, e);
   }
 }
 
@@ -377,12 +420,121 @@ __device__ __forceinline__ void extra_planes(f32x4 (&acc)[CELLS], const float* _
 // ds_write_b64 per piece (and one ds_read_b64 per piece for the residual, which the three pieces
 // reproduce exactly).  Output cell o lives o * 2048 bytes after cell 0.
 // STRIP: dst is the strip (its only tile; nt is ignored).
+// first MFMA slot of the last K group (slot g follows its g-th MFMA) for the steps of the qi-th early cell, `ns` steps a
+// cell: not before the first MFMA of the tap after the cell's final one, and after the cell queued before it
+constexpr int early_begin(int omask, int ns, int qi) {
+  int b = 0, end = 0;
+  for (int q = 0; q <= qi; ++q) {
+    const int start = 6 * pairs_before(omask, net_final_tap(early_cell(omask, q)) + 1, 0);
+    b = start > end ? start : end;
+    end = b + ns;
+  }
+  return b;
+}
+// One cell's epilogue is a fixed sequence of steps of a few VALU instructions each, so that the K loop can issue it step
+// by step between its MFMAs (ProgEpi) and the end-of-job form runs the very same steps back to back (epilogue_cell):
+//   residual (RES: 8 steps, per channel the three pieces' conversion, then the sum; else one empty step, which keeps a
+//   cell's first read of its accumulator an MFMA away from the MFMA that wrote it) | activation (tanh, elu: one step per
+//   channel; else one) | split and store (7: piece 0, remainders of channels 0-1, of 2-3, piece 1, again, piece 2)
+template <int ACT, bool RES>
+constexpr int epi_steps() { return (RES ? 8 : 1) + (ACT >= 2 ? 4 : 1) + 7; }
+struct EpiRegs {
+  f32x4 v;          // the four channels: accumulator (+ residual), activated
+  u32x2 q[3];       // the residual's three pieces
+  float c[3];
+  float r[4];       // remainders of the split
+};
+template <int ACT>
+__device__ __forceinline__ float epi_act(float x) {
+  if constexpr (ACT == 1) x = fmaxf(x, 0.0f);
+  if constexpr (ACT == 2) x = tanh_fast(x);
+  if constexpr (ACT == 3) x = x > 0.0f ? x : expm1f(x);      // nn.ELU(), alpha = 1
+  return x;
+}
+__device__ __forceinline__ float epi_rem(float x) { return x - __builtin_bit_cast(float, trunc_bf16(x)); }
+// this lane's byte offset inside cell 0 of one piece: half a 16-byte slot (four channels)
+template <bool STRIP>
+__device__ __forceinline__ int epi_off(int lane, int nt) {
+  const int pos = lane & 15, quad = lane >> 4;
+  return (STRIP ? strip_addr(0, pos, quad >> 1) : slot_addr(0, pos, nt * 2 + (quad >> 1))) + (quad & 1) * 8;
+}
+template <int O>
+__device__ __forceinline__ void epi_read_res(u32x2 (&q)[3], const unsigned char* res, int off) {
+#pragma unroll
+  for (int piece = 0; piece < 3; ++piece)
+    q[piece] = *reinterpret_cast<const u32x2*>(res + piece * PIECE_BYTES + O * (POS * 128) + off);
+}
+// step K of cell O: `a` is its accumulator
+template <int ACT, bool RES, bool STRIP, int O, int K>
+__device__ __forceinline__ void epi_step(EpiRegs& s, const f32x4& a, unsigned char* __restrict__ dst, int off) {
+  constexpr int PB = STRIP ? STRIP_PIECE_BYTES : PIECE_BYTES, CB = STRIP ? POS * 32 : POS * 128;
+  constexpr int NR = RES ? 8 : 1, NA = ACT >= 2 ? 4 : 1;
+  static_assert(K >= 0 && K < NR + NA + 7, "step of the sequence");
+  if constexpr (K < NR) {
+    if constexpr (RES) {
+      constexpr int r = K >> 1;                  // channel: word r / 2 of each piece, its low (even r) or high half
+      if constexpr ((K & 1) == 0) {
+#pragma unroll
+        for (int piece = 0; piece < 3; ++piece) s.c[piece] = (r & 1) ? bf16_hi(s.q[piece][r >> 1]) : bf16_lo(s.q[piece][r >> 1]);
+      } else {
+        s.v[r] = a[r] + ((s.c[0] + s.c[1]) + s.c[2]);
+      }
+    }
+  } else if constexpr (K < NR + NA) {
+    if constexpr (NA == 4) {
+      constexpr int r = K - NR;
+      s.v[r] = epi_act<ACT>(RES ? s.v[r] : a[r]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s.v[r] = epi_act<ACT>(RES ? s.v[r] : a[r]);
+    }
+  } else {
+    constexpr int P = K - NR - NA;
+    unsigned char* const d = dst + O * CB + off;
+    if constexpr (P == 0) *reinterpret_cast<u32x2*>(d + 0 * PB) = u32x2{pack_hi16(s.v[0], s.v[1]), pack_hi16(s.v[2], s.v[3])};
+    if constexpr (P == 1) { s.r[0] = epi_rem(s.v[0]); s.r[1] = epi_rem(s.v[1]); }
+    if constexpr (P == 2) { s.r[2] = epi_rem(s.v[2]); s.r[3] = epi_rem(s.v[3]); }
+    if constexpr (P == 3) *reinterpret_cast<u32x2*>(d + 1 * PB) = u32x2{pack_hi16(s.r[0], s.r[1]), pack_hi16(s.r[2], s.r[3])};
+    if constexpr (P == 4) { s.r[0] = epi_rem(s.r[0]); s.r[1] = epi_rem(s.r[1]); }
+    if constexpr (P == 5) { s.r[2] = epi_rem(s.r[2]); s.r[3] = epi_rem(s.r[3]); }
+    if constexpr (P == 6) *reinterpret_cast<u32x2*>(d + 2 * PB) = u32x2{pack_hi16(s.r[0], s.r[1]), pack_hi16(s.r[2], s.r[3])};
+  }
+}
+// steps K0 .. the last of cell O
+template <int ACT, bool RES, bool STRIP, int O, int K0>
+__device__ __forceinline__ void epi_steps_from(EpiRegs& s, const f32x4& a, unsigned char* __restrict__ dst, int off) {
+  if constexpr (K0 < epi_steps<ACT, RES>()) {
+    epi_step<ACT, RES, STRIP, O, K0>(s, a, dst, off);
+    epi_steps_from<ACT, RES, STRIP, O, K0 + 1>(s, a, dst, off);
+  }
+}
+// the whole epilogue of one cell; `q`: its residual pieces, already read (RES)
+template <int O, int ACT, bool RES, bool STRIP>
+__device__ __forceinline__ void epilogue_cell(const f32x4& a, const u32x2 (&q)[3], unsigned char* __restrict__ dst, int off) {
+  EpiRegs s;
+  if constexpr (RES) { s.q[0] = q[0]; s.q[1] = q[1]; s.q[2] = q[2]; }
+  epi_steps_from<ACT, RES, STRIP, O, 0>(s, a, dst, off);
+}
+// the cells of CMASK at the end of the job: all residual reads in flight at once, before any write
+template <int CMASK, int ACT, bool RES, bool STRIP, int O = 0>
+__device__ __forceinline__ void epilogue_cells(const f32x4 (&acc)[CELLS], const u32x2 (&q)[CELLS][3],
+                                               unsigned char* __restrict__ dst, int off) {
+  if constexpr (O < CELLS) {
+    if constexpr ((CMASK >> O) & 1) epilogue_cell<O, ACT, RES, STRIP>(acc[O], q[O], dst, off);
+    epilogue_cells<CMASK, ACT, RES, STRIP, O + 1>(acc, q, dst, off);
+  }
+}
+template <int CMASK, int O = 0>
+__device__ __forceinline__ void epi_read_cells(u32x2 (&q)[CELLS][3], const unsigned char* res, int off) {
+  if constexpr (O < CELLS) {
+    if constexpr ((CMASK >> O) & 1) epi_read_res<O>(q[O], res, off);
+    epi_read_cells<CMASK, O + 1>(q, res, off);
+  }
+}
 template <int OMASK, int ACT, bool RES, bool STRIP = false>
 __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[CELLS], unsigned char* __restrict__ dst,
                                              const unsigned char* res, int lane, int nt) {
-  const int pos = lane & 15, quad = lane >> 4;
-  constexpr int PB = STRIP ? STRIP_PIECE_BYTES : PIECE_BYTES, CB = STRIP ? POS * 32 : POS * 128;
-  const int off = (STRIP ? strip_addr(0, pos, quad >> 1) : slot_addr(0, pos, nt * 2 + (quad >> 1))) + (quad & 1) * 8;
+  const int off = epi_off<STRIP>(lane, nt);
 #ifdef NZ_ABLATE_EPI   // timing-only build: one store per job instead of the epilogue (outputs are wrong)
   {
     float t = 0.f;
@@ -393,39 +545,76 @@ __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[CELLS], unsigned
   }
 #endif
   u32x2 q[CELLS][3];
-  if constexpr (RES) {                                     // all residual reads in flight at once, before any write
-#pragma unroll
-    for (int o = 0; o < CELLS; ++o)
-#pragma unroll
-      for (int piece = 0; piece < 3; ++piece)
-        if ((OMASK >> o) & 1) q[o][piece] = *reinterpret_cast<const u32x2*>(res + piece * PIECE_BYTES + o * (POS * 128) + off);
-  }
-#pragma unroll
-  for (int o = 0; o < CELLS; ++o) {
-    if (!((OMASK >> o) & 1)) continue;
-    f32x4 v = acc[o];
-    if constexpr (RES) {
-      v[0] += (bf16_lo(q[o][0][0]) + bf16_lo(q[o][1][0])) + bf16_lo(q[o][2][0]);
-      v[1] += (bf16_hi(q[o][0][0]) + bf16_hi(q[o][1][0])) + bf16_hi(q[o][2][0]);
-      v[2] += (bf16_lo(q[o][0][1]) + bf16_lo(q[o][1][1])) + bf16_lo(q[o][2][1]);
-      v[3] += (bf16_hi(q[o][0][1]) + bf16_hi(q[o][1][1])) + bf16_hi(q[o][2][1]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float x = v[r];
-      if constexpr (ACT == 1) x = fmaxf(x, 0.0f);
-      if constexpr (ACT == 2) x = tanh_fast(x);
-      if constexpr (ACT == 3) x = x > 0.0f ? x : expm1f(x);      // nn.ELU(), alpha = 1
-      v[r] = x;
-    }
-    uint32_t a0, a1, a2, b0, b1, b2;
-    split_pair(v[0], v[1], a0, a1, a2);
-    split_pair(v[2], v[3], b0, b1, b2);
-    *reinterpret_cast<u32x2*>(dst + 0 * PB + o * CB + off) = u32x2{a0, b0};
-    *reinterpret_cast<u32x2*>(dst + 1 * PB + o * CB + off) = u32x2{a1, b1};
-    *reinterpret_cast<u32x2*>(dst + 2 * PB + o * CB + off) = u32x2{a2, b2};
-  }
+  if constexpr (RES) epi_read_cells<OMASK>(q, res, off);
+  epilogue_cells<OMASK, ACT, RES, STRIP>(acc, q, dst, off);
 }
+
+// Progressive epilogue (NetJob flag NET_JOB_PROGRESSIVE; destination an activation buffer).  The job's early cells are
+// queued in the order they become final; cell qi's steps take the MFMA slots of the last K group from `begin(qi)` on, one
+// step per slot: not before the first MFMA of the tap after its final one, and after the cell queued before it.  Its
+// residual pieces are read READ_AHEAD slots earlier (the registers are free: the previous cell is past its residual
+// steps), so the wait in front of its first use is a counted one on loads a whole chain old.  Every slot with work is
+// fenced: the steps stay between the two MFMAs they were placed between, and each six-MFMA chain stays one chain.  What
+// the K loop has no slots left for, and the cells final at tap 8, run at the end of the job (`finish`).  No work moves
+// between waves, nothing is read or computed twice: per cell the same steps on the same values as epilogue_cell.
+template <int OMASK, int ACT, bool RES>
+struct ProgEpi {
+  static constexpr int NS = epi_steps<ACT, RES>(), NQ = early_cells(OMASK), SLOTS = 6 * pairs_before(OMASK, 9, 0);
+  static constexpr int READ_AHEAD = 6;
+  static constexpr int LATE = OMASK & 0x01B;          // cells 0, 1, 3, 4: final at tap 8
+  static_assert(NQ >= 1 && NQ <= 3, "groups with early cells");
+  static constexpr int B0 = early_begin(OMASK, NS, 0), B1 = NQ > 1 ? early_begin(OMASK, NS, 1) : 0, B2 = NQ > 2 ? early_begin(OMASK, NS, 2) : 0;
+  static constexpr int C0 = early_cell(OMASK, 0), C1 = early_cell(OMASK, 1), C2 = early_cell(OMASK, 2);
+  static constexpr int FIRST = RES ? B0 - READ_AHEAD : B0;     // the first slot with work: `off` is derived there
+  static_assert(FIRST >= 0 && FIRST < SLOTS && (!RES || READ_AHEAD <= NS - 8), "reads land inside the K group, behind the residual steps");
+  static constexpr int cell(int qi) { return qi == 0 ? C0 : qi == 1 ? C1 : C2; }
+  static constexpr int begin(int qi) { return qi == 0 ? B0 : qi == 1 ? B1 : B2; }
+  static constexpr int read_slot(int qi) { return begin(qi) - READ_AHEAD; }
+
+  EpiRegs s;
+  unsigned char* dst;
+  const unsigned char* res;
+  int lane, nt, off;
+
+  template <int QI, int G>
+  __device__ __forceinline__ void slot_of(const f32x4 (&acc)[CELLS]) {
+    if constexpr (QI < NQ) {
+      if constexpr (RES && G == read_slot(QI)) epi_read_res<cell(QI)>(s.q, res, off);
+      if constexpr (G >= begin(QI) && G < begin(QI) + NS) epi_step<ACT, RES, false, cell(QI), G - begin(QI)>(s, acc[cell(QI)], dst, off);
+    }
+  }
+  template <int QI, int G>
+  static constexpr bool busy() {
+    if constexpr (QI < NQ) return (RES && G == read_slot(QI)) || (G >= begin(QI) && G < begin(QI) + NS);
+    return false;
+  }
+  template <int G>
+  __device__ __forceinline__ void slot(const f32x4 (&acc)[CELLS]) {
+    if constexpr (busy<0, G>() || busy<1, G>() || busy<2, G>()) {
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (G == FIRST) off = epi_off<false>(lane, nt);
+      slot_of<0, G>(acc); slot_of<1, G>(acc); slot_of<2, G>(acc);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // after the K loop: what is left of the early cells, in queue order, then the cells final at tap 8
+  template <int QI>
+  __device__ __forceinline__ void finish_early(const f32x4 (&acc)[CELLS]) {
+    if constexpr (QI < NQ) {
+      if constexpr (RES && read_slot(QI) >= SLOTS) epi_read_res<cell(QI)>(s.q, res, off);
+      constexpr int done = SLOTS - begin(QI);
+      epi_steps_from<ACT, RES, false, cell(QI), (done > 0 ? done : 0)>(s, acc[cell(QI)], dst, off);
+      finish_early<QI + 1>(acc);
+    }
+  }
+  __device__ __forceinline__ void finish(const f32x4 (&acc)[CELLS]) {
+    u32x2 q[CELLS][3];
+    if constexpr (RES) epi_read_cells<LATE>(q, res, off);
+    finish_early<0>(acc);
+    epilogue_cells<LATE, ACT, RES, false>(acc, q, dst, off);
+  }
+};
+
 template <int OMASK>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob& job, unsigned char* __restrict__ lds,
                                          unsigned char* __restrict__ strip, int lane, int policy_channels, int n_valid,
@@ -476,25 +665,67 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob
 
 // one job: K loop, input-plane step, epilogue
 template <int OMASK, typename Stamp, typename Fetch>
-__device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float* __restrict__ W,
-                                        const float* w_after, unsigned char* __restrict__ lds,
-                                        unsigned char* __restrict__ strip,
-                                        const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
-                                        float* logits, float* value, Stamp&& stamp, Fetch&& fetch_next) {
+__device__ __forceinline__ void run_job_plain(const NetJob& job, FragS& f, const float* __restrict__ W,
+                                              const float* w_after, unsigned char* __restrict__ lds,
+                                              unsigned char* __restrict__ strip,
+                                              const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
+                                              float* logits, float* value, Stamp&& stamp, Fetch&& fetch_next) {
   // per-lane LDS addresses are derived inside the job from an opaque copy of the lane id: hoisted out of the job loop
   // they are spilled and reloaded in the middle of the K loop, behind a wait for the whole weight stream
   asm volatile("" : "+v"(lane));
   f32x4 acc[CELLS];
 #pragma unroll
   for (int o = 0; o < CELLS; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (job.kgroups == 2) job_kloop<OMASK, 2>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane);
-  else if (job.kgroups == 1) job_kloop<OMASK, 1>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane);
+  NoEpi none;
+  if (job.kgroups == 2) job_kloop<OMASK, 2>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane, none);
+  else if (job.kgroups == 1) job_kloop<OMASK, 1>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane, none);
   stamp(0);
   if (job.extra) extra_planes<OMASK>(acc, W + job.wx_off, inp, lane);
   stamp(1);
   fetch_next();          // the next job's descriptor: in flight under the epilogue, in no register during the K loop
   epilogue<OMASK>(acc, job, lds, strip, lane, policy_channels, n_valid, logits, value);   // `value`: the per-cell staging area
   stamp(2);
+}
+// a job flagged NET_JOB_PROGRESSIVE: one or two K groups from a buffer, no input planes, destination a buffer; the
+// epilogue kind is fixed before the K loop
+template <int OMASK, int ACT, bool RES, typename Stamp, typename Fetch>
+__device__ __forceinline__ void run_job_prog(const NetJob& job, FragS& f, const float* __restrict__ W,
+                                             const float* w_after, unsigned char* __restrict__ lds,
+                                             unsigned char* __restrict__ strip, int lane, Stamp&& stamp, Fetch&& fetch_next) {
+  asm volatile("" : "+v"(lane));                // as in run_job_plain
+  f32x4 acc[CELLS];
+#pragma unroll
+  for (int o = 0; o < CELLS; ++o) acc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
+  ProgEpi<OMASK, ACT, RES> e;
+  e.dst = lds + job.dst * ACT_BYTES;
+  e.res = lds + (RES ? job.res : 0) * ACT_BYTES;
+  e.lane = lane;
+  e.nt = job.dtile;
+  if (job.kgroups == 2) job_kloop<OMASK, 2>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane, e);
+  else job_kloop<OMASK, 1>(acc, f, lds + job.src * ACT_BYTES, strip, job.sslot, W + job.w_off, w_after, lane, e);
+  stamp(0);
+  stamp(1);
+  fetch_next();
+  e.finish(acc);
+  stamp(2);
+}
+template <int OMASK, typename Stamp, typename Fetch>
+__device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float* __restrict__ W,
+                                        const float* w_after, unsigned char* __restrict__ lds,
+                                        unsigned char* __restrict__ strip,
+                                        const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
+                                        float* logits, float* value, Stamp&& stamp, Fetch&& fetch_next) {
+#ifndef NZ_ABLATE_EPI
+  if constexpr (net_og_progressive(OMASK)) {
+    if (job.flags & NET_JOB_PROGRESSIVE) {      // (engine.hip add_stage: ReLU with or without residual, or tanh)
+      if (job.res >= 0) run_job_prog<OMASK, 1, true>(job, f, W, w_after, lds, strip, lane, stamp, fetch_next);
+      else if (job.act == 2) run_job_prog<OMASK, 2, false>(job, f, W, w_after, lds, strip, lane, stamp, fetch_next);
+      else run_job_prog<OMASK, 1, false>(job, f, W, w_after, lds, strip, lane, stamp, fetch_next);
+      return;
+    }
+  }
+#endif
+  run_job_plain<OMASK>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, value, stamp, fetch_next);
 }
 
 // Run the compiled network on the 16 positions whose input planes are in `inp`
@@ -585,11 +816,11 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       }
     }
     stamp(2);
-    if (job.stage_end) __syncthreads();
+    if (job.flags & NET_JOB_STAGE_END) __syncthreads();
     stamp(3);
 #ifdef NZ_STAGE_STAMPS   // diagnostic build: per-stage ticks of waves 0 and 4 of workgroup 0 (K loops + planes, epilogue, barrier)
     if constexpr (STAMPS) {
-      if (job.stage_end && blockIdx.x == 0 && (tid == 0 || tid == 256) && n_st < 24) {
+      if ((job.flags & NET_JOB_STAGE_END) && blockIdx.x == 0 && (tid == 0 || tid == 256) && n_st < 24) {
         st_rec[n_st][0] = tk[0] + tk[1] - pk[0]; st_rec[n_st][1] = tk[2] - pk[1]; st_rec[n_st][2] = tk[3] - pk[2];
         ++n_st;
         pk[0] = tk[0] + tk[1]; pk[1] = tk[2]; pk[2] = tk[3];
