@@ -612,6 +612,45 @@ nz_status nz_scs_agent_record(nz_scs_search* h, int32_t side, const int32_t* gam
 nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, int32_t slot, int32_t* count, uint64_t* digests_host,
                                    float* probs_host, float* values_host);
 
+/* ---- Tic-Tac-Toe evaluation matches played inside the library ---------------------------------------------------------
+ * Tester.Test_using_agents on Tic-Tac-Toe: n_games matches between side 1 (moves for player 1, the first mover, as in
+ * oracle/agents.py play_match) and side 2, each an NZ_AGENT_MCTS, NZ_AGENT_POLICY or NZ_AGENT_RANDOM.  The scripted
+ * agents follow the harness rules of nz_scs_agent_match_play (parity unpinned):
+ *   NZ_AGENT_MCTS    an engine created with training = 0 (keep_subtree = 1) with weights or a table: it searches on every
+ *                    ply (its own choose_action, the opponent's update_subtree) and follows the other side's action as
+ *                    nz_engine_apply(actions_dev) takes it;
+ *   NZ_AGENT_POLICY  an engine (training = 0) of which only the network or table is used: at its own plies the current
+ *                    position is evaluated and the legal cell of largest softmax probability is played, the lowest cell
+ *                    index winning a tie (np.argmax).  Two policy sides may share one engine;
+ *   NZ_AGENT_RANDOM  engine NULL; match i owns np.random.RandomState(agent_seeds[i]) (uint32 [n_games]), draws
+ *                    k = rs.randint(n_legal) at its own plies (n_legal == 1 draws nothing) and plays the k-th empty cell
+ *                    in ascending index.
+ * At least one side has an engine (it gives the number of matches).  Refused with NZ_ERR_ARG (message in nz_last_error of
+ * every engine passed, and of NULL) before any launch: a missing engine or one passed for a random side, one engine on
+ * both sides unless both are policy sides, engines with different game counts or devices or with n_slots != n_games, a
+ * training engine, missing seeds for a random side, an MCTS or policy side without weights or table.
+ * The call resets the engines, enqueues exactly nine plies on `stream` -- per ply the search of every MCTS side, for a
+ * scripted mover its evaluation and the agents' kernel, then the apply of every MCTS side; finished matches are no-ops --
+ * then the tally, and synchronises `stream` once at the end: no host read-back between plies.
+ * `out` (may be NULL; every pointer in it may be NULL) receives, in DEVICE memory: actions int32 [n][9] (-1 past the
+ * end), lengths [n], outcomes [n] (the terminal value: +1 player 1 won, -1 player 2 won, 0 draw), per side
+ * agent_actions / agent_n_legal int32 [n][9] by ply (-1 / 0 where that side did not decide or is an MCTS side); and in
+ * HOST memory tally4_host int64 [4]: side-1 wins, side-2 wins, draws, unfinished.
+ * nz_engine_match_streams (test hook): the MT19937 state (key uint32 [n][624], pos int32 [n], host memory) in which the
+ * last match round left random side `side` (0 / 1); `e` is that round's first non-NULL engine. */
+typedef struct nz_ttt_match_result {
+  int32_t* actions;
+  int32_t* lengths;
+  int32_t* outcomes;
+  int32_t* agent_actions[2];
+  int32_t* agent_n_legal[2];
+  int64_t* tally4_host;
+} nz_ttt_match_result;
+nz_status nz_engine_match_play(nz_engine* side1, int32_t kind1, nz_engine* side2, int32_t kind2,
+                               const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
+                               const nz_ttt_match_result* out, void* stream);
+nz_status nz_engine_match_streams(nz_engine* e, int32_t side, uint32_t* keys_host, int32_t* pos_host);
+
 /* ---- host random streams (numpy legacy RandomState, MT19937) --------------
  * Replaces the reference's use of the global np.random stream
  * (Explorer.py:77-78,89,199,208). */

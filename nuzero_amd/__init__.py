@@ -12,7 +12,7 @@ __version__ = "0.1"
 
 def __getattr__(name):
     # the evaluation-match front end, imported on first use (it loads the shared library)
-    if name in ("ScsMatch", "ScsAgentMatch", "ScsTester"):
+    if name in ("ScsMatch", "ScsAgentMatch", "ScsTester", "TttMatch", "TttAgentMatch", "TttTester"):
         from . import tester
         return getattr(tester, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -76,6 +76,11 @@ class ScsAgent(Structure):
     _fields_ = [("kind", c_int32), ("net", c_void_p), ("seeds_host", c_void_p)]
 
 
+class TttMatchResult(Structure):
+    _fields_ = [("actions", c_void_p), ("lengths", c_void_p), ("outcomes", c_void_p), ("agent_actions", c_void_p * 2),
+                ("agent_n_legal", c_void_p * 2), ("tally4_host", POINTER(c_int64))]
+
+
 # name -> (restype, argtypes); every symbol include/nuzero_amd.h declares
 SIGNATURES = {
     "nz_version": (c_char_p, []),
@@ -174,6 +179,9 @@ SIGNATURES = {
     "nz_scs_agent_match_decisions": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_agent_record": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32]),
     "nz_scs_agent_record_read": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "nz_engine_match_play": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, POINTER(TttMatchResult),
+                                       c_void_p]),
+    "nz_engine_match_streams": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "nz_replay_create": (c_int32, [POINTER(c_void_p), c_int64, c_int32, c_int32, c_int32]),
     "nz_replay_destroy": (None, [c_void_p]),
     "nz_replay_last_error": (c_char_p, [c_void_p]),

@@ -13,6 +13,8 @@
 
 #include "engine.h"
 #include "hip_own.hpp"
+#include "scs_mt.hpp"
+#include "ttt_agents.hpp"
 
 using namespace nz;
 
@@ -36,6 +38,26 @@ struct EngineArrays {
   DevBuf<double> noise, uniforms, game_noise, game_uniforms;   // one move's randomness [G][A], [G][3]; a whole game's [G][T]...
   DevBuf<unsigned long long> stamps;          // [blocks][4], diagnostic build only
   DevBuf<NetProgram> prog;
+};
+
+// The state of the evaluation matches of nz_engine_match_play (ttt_agents.hpp), made at the first round and owned by
+// the round's first engine; TttMatchArgs borrows the pointers.
+struct MatchArrays {
+  DevBuf<uint32_t> board, mt_keys[2], seeds[2];
+  DevBuf<int32_t> alive, length, outcome, actions, forced, err, agent_actions[2], agent_n_legal[2], mt_pos[2];
+  DevBuf<float> states, logits, value, probs;
+  DevBuf<unsigned long long> tally;           // [8]
+  PinnedBuf<unsigned long long> h_tally;      // [8]
+  bool ensure(size_t n) {
+    const size_t nt = n * TTT_MAX_MOVES;
+    bool ok = board.ensure(n) && alive.ensure(n) && length.ensure(n) && outcome.ensure(n) && actions.ensure(nt) &&
+              forced.ensure(n) && err.ensure(n) && states.ensure(n * 18) && logits.ensure(n * TTT_ACTIONS) &&
+              value.ensure(n) && probs.ensure(n * TTT_ACTIONS) && tally.ensure(8) && h_tally.ensure(8);
+    for (int s = 0; s < 2; ++s)
+      ok = ok && agent_actions[s].ensure(nt) && agent_n_legal[s].ensure(nt) && mt_keys[s].ensure(n * MT_N) &&
+           mt_pos[s].ensure(n) && seeds[s].ensure(n);
+    return ok;
+  }
 };
 }  // namespace
 
@@ -76,6 +98,9 @@ struct nz_engine {
   bool profile = false;
   std::vector<ProfileSpan> spans;
   int64_t net_positions = 0;       // upper bound: positions offered to the network kernel
+  // evaluation matches (nz_engine_match_play)
+  MatchArrays match;
+  int match_kinds[2] = {-1, -1};   // the last round's sides, -1: none played
 };
 
 namespace {
@@ -1153,6 +1178,147 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
     for (int b = 0; b < blocks; ++b) sum += (double)h[(size_t)b * 4 + i];
     ticks4_host[i] = sum / blocks;
   }
+  return NZ_OK;
+}
+
+// ---- evaluation matches (Tester.Test_using_agents, Testing/Tester.py:46-121) ------------------------------------------
+// All matches of a round are at the same ply, so the mover's side and kind are known here: nine plies are enqueued
+// back to back, finished matches are no-ops in every kernel, and the only synchronisation is the one after the tally.
+nz_status nz_engine_match_play(nz_engine* side1, int32_t kind1, nz_engine* side2, int32_t kind2,
+                               const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
+                               const nz_ttt_match_result* out, void* stream) {
+  nz_engine* const eng[2] = {side1, side2};
+  const int32_t kind[2] = {kind1, kind2};
+  const uint32_t* const seeds[2] = {agent_seeds1_host, agent_seeds2_host};
+  auto refuse = [&](nz_status code, const std::string& msg) {       // the message on every engine passed, and on NULL
+    for (nz_engine* e : eng)
+      if (e) e->error = msg;
+    g_create_error = msg;
+    return code;
+  };
+  for (int i = 0; i < 2; ++i) {
+    const int k = kind[i];
+    if (k != NZ_AGENT_MCTS && k != NZ_AGENT_POLICY && k != NZ_AGENT_RANDOM)
+      return refuse(NZ_ERR_ARG, text("side %d: unknown agent kind %d", i + 1, k));
+    if (k == NZ_AGENT_RANDOM) {
+      if (eng[i]) return refuse(NZ_ERR_ARG, text("side %d: a random side takes no engine", i + 1));
+      if (!seeds[i]) return refuse(NZ_ERR_ARG, text("side %d: a random side needs agent seeds, one per match", i + 1));
+      continue;
+    }
+    const nz_engine* e = eng[i];
+    if (!e) return refuse(NZ_ERR_ARG, text("side %d: an MCTS or policy side needs an engine", i + 1));
+    if (e->cfg.training)
+      return refuse(NZ_ERR_ARG, text("side %d: a training engine (evaluation agents do not explore: create it with training = 0)", i + 1));
+    if (!e->cfg.keep_subtree) return refuse(NZ_ERR_ARG, text("side %d: keep_subtree = 0 is not supported", i + 1));
+    if (!e->have_net && !e->have_table)
+      return refuse(NZ_ERR_ARG, text("side %d: no network: call nz_engine_set_weights or nz_engine_set_table first", i + 1));
+    if (e->n_slots != e->n_games)
+      return refuse(NZ_ERR_ARG, text("side %d: a match engine needs n_slots == n_games (every match in flight)", i + 1));
+  }
+  if (!side1 && !side2) return refuse(NZ_ERR_ARG, "two random sides: one side must have an engine (it gives the number of matches)");
+  if (side1 && side1 == side2 && !(kind1 == NZ_AGENT_POLICY && kind2 == NZ_AGENT_POLICY))
+    return refuse(NZ_ERR_ARG, "both sides are the same engine: only two policy sides may share one (an MCTS side owns its trees)");
+  if (side1 && side2 && side1->n_games != side2->n_games)
+    return refuse(NZ_ERR_ARG, text("the engines hold %d and %d games: a match is one game on both", side1->n_games, side2->n_games));
+  if (side1 && side2 && side1->device != side2->device)
+    return refuse(NZ_ERR_ARG, text("the engines are on devices %d and %d", side1->device, side2->device));
+
+  nz_engine* const host = side1 ? side1 : side2;
+  const int n = host->n_games;
+  hipStream_t s = as_stream(stream);
+  NZ_HIP(host, hipSetDevice(host->device));
+  MatchArrays& m = host->match;
+  if (!m.ensure((size_t)n)) return fail(host, NZ_ERR_HIP, "device allocation failed (match state)");
+  host->match_kinds[0] = host->match_kinds[1] = -1;
+  TttMatchArgs a{};
+  a.n = n;
+  a.board = m.board.get(); a.alive = m.alive.get(); a.length = m.length.get(); a.outcome = m.outcome.get();
+  a.actions = m.actions.get(); a.forced = m.forced.get(); a.err = m.err.get();
+  a.states = m.states.get(); a.probs = m.probs.get();
+  for (int i = 0; i < 2; ++i) {
+    a.agent_actions[i] = m.agent_actions[i].get(); a.agent_n_legal[i] = m.agent_n_legal[i].get();
+    a.mt_keys[i] = m.mt_keys[i].get(); a.mt_pos[i] = m.mt_pos[i].get();
+  }
+
+  nz_engine* mcts[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; ++i)
+    if (kind[i] == NZ_AGENT_MCTS) mcts[i] = eng[i];
+  for (int i = 0; i < 2; ++i) {
+    if (eng[i] && !(i == 1 && eng[1] == eng[0])) {
+      const nz_status st = nz_engine_reset(eng[i], stream);
+      if (st != NZ_OK) return st;
+    }
+    if (kind[i] == NZ_AGENT_RANDOM) {
+      NZ_HIP(host, hipMemcpyAsync(m.seeds[i].get(), seeds[i], (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      NZ_HIP(host, agent_seed_launch(m.seeds[i].get(), a.mt_keys[i], a.mt_pos[i], n, s));
+    }
+  }
+  ttt_match_reset_launch(a, s);
+
+  for (int ply = 0; ply < TTT_MAX_MOVES; ++ply) {
+    const int mv = ply & 1;                                  // side 1 moves for player 1, the first mover
+    for (nz_engine* e : mcts)
+      if (e) search_lockstep(e, nullptr, s);                 // the mover's choose_action, the opponent's update_subtree
+    if (kind[mv] == NZ_AGENT_MCTS) {
+      launch_finish_move(mcts[mv]->tp, nullptr, nullptr, s);
+      launch_last_actions(mcts[mv]->tp, a.forced, s);
+      if (mcts[mv ^ 1]) launch_finish_move(mcts[mv ^ 1]->tp, nullptr, a.forced, s);
+    } else {
+      const float* table = nullptr;
+      if (kind[mv] == NZ_AGENT_POLICY) {
+        const nz_engine* pe = eng[mv];
+        table = pe->tp.table;
+        if (!table) {                                        // the stand-alone network route (nz_net_forward)
+          ttt_state_image_launch(a, s);
+          launch_net(pe->dev.prog.get(), 0, net_weights(pe), nullptr, a.states, nullptr, n, m.logits.get(), m.value.get(),
+                     m.probs.get(), nullptr, s);
+        }
+      }
+      ttt_agent_move_launch(a, mv, kind[mv], table, s);
+      for (nz_engine* e : mcts)
+        if (e) launch_finish_move(e->tp, nullptr, a.forced, s);
+    }
+    ttt_match_step_launch(a, s);
+  }
+
+  NZ_HIP(host, hipMemsetAsync(m.tally.get(), 0, 8 * sizeof(unsigned long long), s));
+  ttt_match_tally_launch(a, mcts[0] ? mcts[0]->tp.error_flag : nullptr, mcts[1] ? mcts[1]->tp.error_flag : nullptr,
+                         m.tally.get(), s);
+  NZ_HIP(host, hipGetLastError());
+  NZ_HIP(host, hipMemcpyAsync(m.h_tally.get(), m.tally.get(), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  if (out) {
+    const size_t nt = (size_t)n * TTT_MAX_MOVES * sizeof(int32_t);
+    if (out->actions) NZ_HIP(host, hipMemcpyAsync(out->actions, a.actions, nt, hipMemcpyDeviceToDevice, s));
+    if (out->lengths) NZ_HIP(host, hipMemcpyAsync(out->lengths, a.length, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (out->outcomes) NZ_HIP(host, hipMemcpyAsync(out->outcomes, a.outcome, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    for (int i = 0; i < 2; ++i) {
+      if (out->agent_actions[i]) NZ_HIP(host, hipMemcpyAsync(out->agent_actions[i], a.agent_actions[i], nt, hipMemcpyDeviceToDevice, s));
+      if (out->agent_n_legal[i]) NZ_HIP(host, hipMemcpyAsync(out->agent_n_legal[i], a.agent_n_legal[i], nt, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  NZ_HIP(host, hipStreamSynchronize(s));
+  const unsigned long long* t = m.h_tally.get();
+  if (t[5] || t[6])
+    return fail(host, NZ_ERR_OVERFLOW, "device check failed (side-1 flag %llu, side-2 flag %llu: 1 = tree arena full, 2 = visit table "
+                                       "too short, 4 = move finished before its search, 8 = forced action is not legal)", t[5], t[6]);
+  if (t[4])
+    return fail(host, NZ_ERR_STATE, "internal: a match's error word is set (%llu: 1 = randint rejection cap, 2 = no empty cell, "
+                                    "4 = the mover's action is not an empty cell)", t[4]);
+  if (out && out->tally4_host)
+    for (int i = 0; i < 4; ++i) out->tally4_host[i] = (int64_t)t[i];
+  host->match_kinds[0] = kind1;
+  host->match_kinds[1] = kind2;
+  return NZ_OK;
+}
+
+nz_status nz_engine_match_streams(nz_engine* e, int32_t side, uint32_t* keys_host, int32_t* pos_host) {
+  if (!e || side < 0 || side > 1 || !keys_host || !pos_host) return fail(e, NZ_ERR_ARG, "bad argument");
+  if (e->match_kinds[side] != NZ_AGENT_RANDOM)
+    return fail(e, NZ_ERR_STATE, "side %d of this engine's last match round was no random side", side + 1);
+  NZ_HIP(e, hipSetDevice(e->device));
+  NZ_HIP(e, hipDeviceSynchronize());
+  NZ_HIP(e, hipMemcpy(keys_host, e->match.mt_keys[side].get(), (size_t)e->n_games * MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  NZ_HIP(e, hipMemcpy(pos_host, e->match.mt_pos[side].get(), (size_t)e->n_games * sizeof(int32_t), hipMemcpyDeviceToHost));
   return NZ_OK;
 }
 

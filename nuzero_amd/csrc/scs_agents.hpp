@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "scs_dev.hpp"
+#include "scs_mt.hpp"
 
 namespace nz {
 
@@ -54,8 +55,7 @@ struct AgentArgs {
   int32_t* err;                  // [G] AGENT_ERR_*
 };
 
-// streams of the random agents: keys/pos of match g = RandomState(seeds[g])
-hipError_t agent_seed_launch(const uint32_t* seeds, uint32_t* mt_keys, int32_t* mt_pos, int n, hipStream_t stream);
+// (streams of the random agents: scs_mt.hpp's agent_seed_launch)
 // out3 (zeroed by the host): live matches, the handle's error flag, the OR of the matches' error words
 hipError_t agent_live_launch(const ScsState* real, int n, const int32_t* error_flag, const int32_t* err, int32_t* out3,
                              hipStream_t stream);

@@ -83,4 +83,8 @@ __device__ inline int mt_randint(Mt& m, int n) {
   return -1;
 }
 
+// Streams kept in HBM between a random agent's decisions (scs_agents.hip, ttt_agents.hip): keys [n][624] / pos [n] of
+// match g = RandomState(seeds[g]) (pos = 624: the first draw twists).  Defined in scs_agents.hip.
+hipError_t agent_seed_launch(const uint32_t* seeds, uint32_t* mt_keys, int32_t* mt_pos, int n, hipStream_t stream);
+
 }  // namespace nz

@@ -20,12 +20,16 @@ action of largest softmax probability (lowest index on a tie, no search); the ra
 `RandomState(agent_seeds[i]).randint(n_legal)` at each of its own decisions and plays that legal action in ascending
 index.  `ScsTester.test_using_agents` takes these specs in place of a search config.
 
-Out of scope: SCS's scripted agents (the reference's hand-written SCS players), and Tic-Tac-Toe (two deterministic
-agents play ONE game there: the two-engine loop of INTEGRATION.md section 5 covers it, and there is no per-match
-variety to batch).
+Tic-Tac-Toe (C ABI nz_engine_match_play): `TttMatch` (two MCTS agents), `TttAgentMatch` (any pairing of MCTS, policy
+and random sides, same specs and rules) and `TttTester`.  A game lasts at most nine plies and every match of a round is
+at the same ply, so one call enqueues the whole round with no host round trip.  Two MCTS sides, or MCTS against the bare
+policy, are deterministic from the empty board: N such matches are N copies of one game; only matches with a random
+side differ from each other.
+
+Out of scope: SCS's scripted agents (the reference's hand-written SCS players).
 """
 from collections.abc import Mapping
-from ctypes import byref, c_int32, c_void_p
+from ctypes import byref, c_int32, c_int64, c_void_p
 
 import numpy as np
 
@@ -273,6 +277,188 @@ class ScsTester:
             r = self._match[1].play(net1, net2, seeds=seeds, agent_seeds=agent_seeds, max_moves=max_moves)
         else:
             r = self._match[1].play(net1, net2, seeds=seeds, max_moves=max_moves)
+        return r["p1_wins"], r["p2_wins"], r["draws"]
+
+    Test_using_agents = test_using_agents
+
+
+# ---- Tic-Tac-Toe -------------------------------------------------------------------------------------------------------
+TTT_TABLE_ROWS = 3 ** 9
+
+
+def _is_table(net):
+    """A table evaluator: [3^9, 10] numbers (9 post-softmax probabilities + value), what SelfPlayEngine.set_table takes."""
+    return not isinstance(net, (Mapping, tuple, list)) and hasattr(net, "shape") and len(net.shape) == 2
+
+
+def _check_ttt_net(i, kind, net):
+    """What a Tic-Tac-Toe side's `net` may be: None (random side), a state_dict (any mapping), a pair (state_dict,
+    set_weights keyword arguments), or a table."""
+    if kind == "random":
+        return
+    if net is None:
+        raise ValueError(f"agent {i + 1}: a {kind} agent needs a network (a state_dict) or a table")
+    if _is_table(net):
+        if tuple(net.shape) != (TTT_TABLE_ROWS, 10):
+            raise ValueError(f"agent {i + 1}: a table has shape ({TTT_TABLE_ROWS}, 10), not {tuple(net.shape)}")
+        return
+    if isinstance(net, (tuple, list)):
+        if len(net) != 2 or not isinstance(net[0], Mapping) or not isinstance(net[1], Mapping):
+            raise ValueError(f"agent {i + 1}: a network with its own arguments is (state_dict, set_weights kwargs)")
+        return
+    if not isinstance(net, Mapping):
+        raise ValueError(f"agent {i + 1}: net must be a state_dict, (state_dict, kwargs) or a ({TTT_TABLE_ROWS}, 10) table")
+
+
+class TttAgentMatch:
+    """n_matches Tic-Tac-Toe matches between agent1 (player 1, the first mover) and agent2: specs ("mcts", search_cfg),
+    ("policy",), ("random",) as ScsAgentMatch takes them, in any pairing but two random sides.  `engines`: per side the
+    SelfPlayEngine(training=False) of an MCTS or policy side, None for a random side; after play() an MCTS side's
+    engine holds its search records (export()).  `share_policy_engine`: two policy sides that play with the SAME
+    network use one engine instead of one each."""
+
+    def __init__(self, agent1, agent2, n_matches, device=0, share_policy_engine=False):
+        self.kinds, self.search_cfgs = zip(*(_agent_spec(a) for a in (agent1, agent2)))
+        if self.kinds == ("random", "random"):
+            raise ValueError("two random agents: one side must be an MCTS or policy agent (its engine holds the matches)")
+        for i, sc in enumerate(self.search_cfgs):
+            if sc is not None and not sc["Simulation"]["keep_subtree"]:
+                raise ValueError(f"agent {i + 1}: keep_subtree = False is not supported (an MctsAgent that drops its "
+                                 "tree never re-roots, MctsAgent.py:28-39; every shipped search config keeps it)")
+        if int(n_matches) <= 0:
+            raise ValueError("n_matches must be positive")
+        if share_policy_engine and self.kinds != ("policy", "policy"):
+            raise ValueError("share_policy_engine: only two policy agents may share one engine (an MCTS agent owns its trees)")
+        self.n_matches, self.device = int(n_matches), device
+        from .engine import SelfPlayEngine            # (needs the GPU from here on)
+        engines = []
+        for kind, sc in zip(self.kinds, self.search_cfgs):
+            if kind == "random":
+                engines.append(None)
+            elif share_policy_engine and engines:
+                engines.append(engines[0])            # one engine, one network
+            else:
+                engines.append(SelfPlayEngine(sc or _NO_SEARCH, self.n_matches, training=False, device=device))
+        self.engines = tuple(engines)
+
+    def close(self):
+        for e in set(e for e in self.engines if e is not None):
+            e.close()
+
+    def _check_play(self, nets, agent_seeds):
+        """What play() refuses before any GPU call; returns the per-side uint32 seed arrays (None: not a random side)."""
+        for i, (kind, net) in enumerate(zip(self.kinds, nets)):
+            _check_ttt_net(i, kind, net)
+        per_side = [None, None]
+        if "random" in self.kinds:
+            if agent_seeds is None:
+                raise ValueError("a random agent draws from RandomState(agent_seeds[i]) in match i: pass agent_seeds")
+            given = list(agent_seeds)
+            i = self.kinds.index("random")
+            if len(given) != self.n_matches:
+                raise ValueError(f"agent {i + 1}: {len(given)} agent_seeds for {self.n_matches} matches")
+            from .scs import _seed_array
+            per_side[i] = _seed_array(given)
+        return per_side
+
+    def _load(self, engine, net, net_kwargs):
+        if _is_table(net):
+            import torch
+            engine.set_table(net.cpu().numpy() if isinstance(net, torch.Tensor) else net)
+        elif isinstance(net, Mapping):
+            engine.set_weights(net, **net_kwargs)
+        else:
+            engine.set_weights(net[0], **dict(net_kwargs, **net[1]))
+
+    def play(self, net1, net2, agent_seeds=None, **net_kwargs):
+        """One round: every match from the empty board to its end.  net1 / net2: an MCTS or policy side's network -- a
+        state_dict (with `net_kwargs`, SelfPlayEngine.set_weights' keyword arguments, or as a pair (state_dict,
+        kwargs) of its own) or a (3^9, 10) table (set_table) -- None for a random side; with share_policy_engine the
+        same net for both.  `agent_seeds` (a random side: required, one per
+        match): match i's random agent is RandomState(agent_seeds[i]), rebuilt every round.  Returns ScsMatch.play's
+        keys: "p1_wins", "p2_wins", "draws", "unfinished", "actions" int32 [N, 9] (-1 past a match's end), "lengths",
+        "outcomes" [N] (terminal value: +1 player 1 won), and per side "agent_actions" / "agent_n_legal" int32 [N, 9]
+        by ply (-1 / 0 where the side did not decide; None for an MCTS side)."""
+        import torch
+        from . import _lib
+        nets = (net1, net2)
+        side_seeds = self._check_play(nets, agent_seeds)
+        if self.engines[0] is not None and self.engines[0] is self.engines[1] and net1 is not net2:
+            raise ValueError("two policy agents share one engine and one network: pass the same net for both")
+        loaded = set()
+        for e, net in zip(self.engines, nets):
+            if e is not None and id(e) not in loaded:
+                self._load(e, net, net_kwargs)
+                loaded.add(id(e))
+        host = next(e for e in self.engines if e is not None)
+        N, dev = self.n_matches, host.device
+        new = lambda: torch.empty((N, 9), dtype=torch.int32, device=dev)
+        actions, lengths, outcomes = new(), torch.empty((N,), dtype=torch.int32, device=dev), torch.empty((N,), dtype=torch.int32, device=dev)
+        ag_a, ag_n = [new(), new()], [new(), new()]
+        tally = (c_int64 * 4)()
+        res = _lib.TttMatchResult(actions=actions.data_ptr(), lengths=lengths.data_ptr(), outcomes=outcomes.data_ptr(),
+                                  agent_actions=(c_void_p * 2)(*[t.data_ptr() for t in ag_a]),
+                                  agent_n_legal=(c_void_p * 2)(*[t.data_ptr() for t in ag_n]), tally4_host=tally)
+        code = {"mcts": _lib.NZ_AGENT_MCTS, "policy": _lib.NZ_AGENT_POLICY, "random": _lib.NZ_AGENT_RANDOM}
+        h = [e._h if e is not None else None for e in self.engines]
+        sp = [c_void_p(s.ctypes.data) if s is not None else None for s in side_seeds]
+        with torch.cuda.device(dev):
+            stream = c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib.nz_engine_match_play(h[0], code[self.kinds[0]], h[1], code[self.kinds[1]], sp[0], sp[1],
+                                                     byref(res), stream), host._h)
+        out = {"p1_wins": int(tally[0]), "p2_wins": int(tally[1]), "draws": int(tally[2]), "unfinished": int(tally[3]),
+               "actions": actions.cpu().numpy(), "lengths": lengths.cpu().numpy(), "outcomes": outcomes.cpu().numpy(),
+               "agent_actions": [None, None], "agent_n_legal": [None, None]}
+        for i, kind in enumerate(self.kinds):
+            if kind != "mcts":
+                out["agent_actions"][i], out["agent_n_legal"][i] = ag_a[i].cpu().numpy(), ag_n[i].cpu().numpy()
+        return out
+
+    def random_streams(self, side):
+        """Test hook: the MT19937 states (key uint32 [N, 624], pos int32 [N]) the last round left random side `side` in."""
+        from . import _lib
+        host = next(e for e in self.engines if e is not None)
+        keys, pos = np.empty((self.n_matches, 624), np.uint32), np.empty((self.n_matches,), np.int32)
+        _lib.check(_lib.lib.nz_engine_match_streams(host._h, int(side), c_void_p(keys.ctypes.data), c_void_p(pos.ctypes.data)),
+                   host._h)
+        return keys, pos
+
+
+class TttMatch(TttAgentMatch):
+    """n_matches matches between two MCTS agents on Tic-Tac-Toe (search_cfg_1 plays player 1), one engine each.  Both are
+    deterministic, so the matches of a round are copies of one game."""
+
+    def __init__(self, search_cfg_1, search_cfg_2, n_matches, device=0):
+        for i, sc in enumerate((search_cfg_1, search_cfg_2)):
+            if not isinstance(sc, Mapping):
+                raise ValueError(f"agent {i + 1}: TttMatch takes two search configs (scripted sides: TttAgentMatch)")
+        super().__init__(("mcts", search_cfg_1), ("mcts", search_cfg_2), n_matches, device=device)
+
+    def play(self, weights1, weights2, **net_kwargs):
+        return super().play(weights1, weights2, **net_kwargs)
+
+
+class TttTester:
+    """The shape of the reference's Tester on Tic-Tac-Toe, as ScsTester: `test_using_agents` plays n matches between
+    two agents -- a search config (an MCTS agent) or a spec ("mcts", search_cfg) / ("policy",) / ("random",) -- and
+    returns (p1_wins, p2_wins, draws), as Test_using_agents counts them over n games (Tester.py:46-121)."""
+
+    def __init__(self, device=0):
+        self.device = device
+        self._match = None
+
+    def close(self):
+        if self._match is not None:
+            self._match[1].close()
+            self._match = None
+
+    def test_using_agents(self, agent1, net1, agent2, net2, n, agent_seeds=None, **net_kwargs):
+        (k1, c1), (k2, c2) = _agent_spec(agent1), _agent_spec(agent2)
+        key = (repr((k1, c1)), repr((k2, c2)), int(n))
+        if self._match is None or self._match[0] != key:
+            self.close()
+            self._match = (key, TttAgentMatch((k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device))
+        r = self._match[1].play(net1, net2, agent_seeds=agent_seeds, **net_kwargs)
         return r["p1_wins"], r["p2_wins"], r["draws"]
 
     Test_using_agents = test_using_agents
