@@ -138,6 +138,18 @@ nz_status nz_engine_set_table(nz_engine* e, const float* table, int32_t n_rows);
  * unexpanded root (Gamer.py:52-59). */
 nz_status nz_engine_reset(nz_engine* e, void* stream);
 
+/* nz_engine_reset, then every game's position becomes boards_host[g] (uint32 [n_games], host memory; copied before the
+ * call returns): the engine's own bitboard word, player-one stones in bits 0-8, player-two stones in bits 16-24.
+ * A position is playable when no other bit is set, the two stone sets are disjoint, stones(p1) - stones(p2) is 0 or
+ * 1, neither side has a line and at least one cell is empty; how it arose is not checked.  The search starts from a
+ * fresh root (MctsAgent.new_game, then choose_action on a game stepped to the position), the player to move is the
+ * one the stone count gives, and the engine's records count from the position: record 0 is the first decision made
+ * there, lengths the plies played since.  Evaluation engines on the lock-step route only.  Refused before any launch,
+ * the engine untouched: NZ_ERR_ARG for a NULL argument, a training engine, or a board that is not playable (the
+ * message names the index of the first one and the condition); NZ_ERR_STATE for n_slots != n_games.
+ * nz_engine_reset afterwards returns the engine to the empty board: nothing of the positions survives. */
+nz_status nz_engine_reset_to(nz_engine* e, const uint32_t* boards_host, void* stream);
+
 /* Children of each game's current root, 0 for an unexpanded root or a finished
  * game: the number of gamma draws add_exploration_noise will take
  * (Explorer.py:201-210).  dev int32[G]. */
@@ -650,6 +662,26 @@ nz_status nz_engine_match_play(nz_engine* side1, int32_t kind1, nz_engine* side2
                                const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
                                const nz_ttt_match_result* out, void* stream);
 nz_status nz_engine_match_streams(nz_engine* e, int32_t side, uint32_t* keys_host, int32_t* pos_host);
+
+/* nz_engine_match_play from given positions: match i starts at start_boards_host[i] (uint32 [n_games], host memory;
+ * the playable positions of nz_engine_reset_to), every MCTS side from a fresh root there.  NULL is nz_engine_match_play,
+ * which is this call.  All of nz_engine_match_play's refusals stand and come first; then NZ_ERR_ARG for a board that
+ * is not playable (index and condition named) and for start boards that do not all hold the same number of stones k
+ * (both counts named): every match of a round is at the same ply, which is what lets the host enqueue the round
+ * without a read-back.  Plies k .. 8 are enqueued; side 1 still moves for player 1, the even plies, so with odd k
+ * side 2 moves first.  The match's record stays by absolute ply: actions[i][p] is -1 for p < k and past the end,
+ * lengths[i] the stone count of the final position, agent_actions / agent_n_legal by ply as before.  An MCTS side's
+ * engine counts from the position (nz_engine_reset_to): its record is the match's shifted by k.
+ * nz_engine_policy_actions: the bare-policy agent's decision on each of n <= n_games playable positions (boards_host
+ * uint32 [n], host memory) into actions_dev (int32 [n], device memory; enqueued on `stream`, no synchronisation): the
+ * legal cell of largest softmax probability from the engine's network or table, the lowest index on a tie -- the
+ * policy mover of the matches, run on the engine's match state (a later nz_engine_match_streams is refused).  Refused
+ * with NZ_ERR_ARG: a NULL argument, n outside 1 .. n_games, no network or table, a board that is not playable. */
+nz_status nz_engine_match_play_from(nz_engine* side1, int32_t kind1, nz_engine* side2, int32_t kind2,
+                                    const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
+                                    const uint32_t* start_boards_host, const nz_ttt_match_result* out, void* stream);
+nz_status nz_engine_policy_actions(nz_engine* e, const uint32_t* boards_host, int32_t n, int32_t* actions_dev,
+                                   void* stream);
 
 /* ---- host random streams (numpy legacy RandomState, MT19937) --------------
  * Replaces the reference's use of the global np.random stream

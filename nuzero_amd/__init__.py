@@ -15,4 +15,7 @@ def __getattr__(name):
     if name in ("ScsMatch", "ScsAgentMatch", "ScsTester", "TttMatch", "TttAgentMatch", "TttTester"):
         from . import tester
         return getattr(tester, name)
+    if name == "ttt_positions":                # start positions of the Tic-Tac-Toe matches (plain numpy)
+        import importlib
+        return importlib.import_module(".ttt_positions", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

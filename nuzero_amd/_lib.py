@@ -93,6 +93,7 @@ SIGNATURES = {
     "nz_engine_set_weights": (c_int32, [c_void_p, POINTER(NetDesc), POINTER(c_void_p), c_int32, c_int32]),
     "nz_engine_set_table": (c_int32, [c_void_p, c_void_p, c_int32]),
     "nz_engine_reset": (c_int32, [c_void_p, c_void_p]),
+    "nz_engine_reset_to": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nz_engine_root_children": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nz_engine_search": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nz_engine_apply": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -182,6 +183,9 @@ SIGNATURES = {
     "nz_engine_match_play": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, POINTER(TttMatchResult),
                                        c_void_p]),
     "nz_engine_match_streams": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "nz_engine_match_play_from": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                            POINTER(TttMatchResult), c_void_p]),
+    "nz_engine_policy_actions": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "nz_replay_create": (c_int32, [POINTER(c_void_p), c_int64, c_int32, c_int32, c_int32]),
     "nz_replay_destroy": (None, [c_void_p]),
     "nz_replay_last_error": (c_char_p, [c_void_p]),

@@ -98,7 +98,8 @@ struct TreeParams {
   double* hist_root_value_sum;
 };
 
-void launch_reset(const TreeParams& p, hipStream_t s);
+// boards: [n_games] start positions (needs n_slots == n_games), or nullptr for the empty board
+void launch_reset(const TreeParams& p, const uint32_t* boards, hipStream_t s);
 void launch_noise(const TreeParams& p, const double* noise, hipStream_t s);
 void launch_advance(const TreeParams& p, int iteration, hipStream_t s);
 void launch_finish_move(const TreeParams& p, const double* uniforms, const int32_t* forced, hipStream_t s);

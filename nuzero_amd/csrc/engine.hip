@@ -30,6 +30,7 @@ struct ProfileSpan {
 struct EngineArrays {
   DevBuf<TNode> nodes;
   DevBuf<uint32_t> board, leaf_board, leaf_boards, hist_board;
+  DevBuf<uint32_t> start_board;                 // [G] nz_engine_reset_to's positions, made at its first call
   DevBuf<int32_t> next_game, length, alive, outcome, root, node_count, sims_left, pending, path, path_len, sim_count, exp_count,
       sel_nodes, sel_children, new_nodes, n_root_children, desync, leaf_count, error_flag, hist_action, hist_visits,
       hist_tree_size, hist_children;
@@ -43,14 +44,14 @@ struct EngineArrays {
 // The state of the evaluation matches of nz_engine_match_play (ttt_agents.hpp), made at the first round and owned by
 // the round's first engine; TttMatchArgs borrows the pointers.
 struct MatchArrays {
-  DevBuf<uint32_t> board, mt_keys[2], seeds[2];
+  DevBuf<uint32_t> board, start, mt_keys[2], seeds[2];
   DevBuf<int32_t> alive, length, outcome, actions, forced, err, agent_actions[2], agent_n_legal[2], mt_pos[2];
   DevBuf<float> states, logits, value, probs;
   DevBuf<unsigned long long> tally;           // [8]
   PinnedBuf<unsigned long long> h_tally;      // [8]
   bool ensure(size_t n) {
     const size_t nt = n * TTT_MAX_MOVES;
-    bool ok = board.ensure(n) && alive.ensure(n) && length.ensure(n) && outcome.ensure(n) && actions.ensure(nt) &&
+    bool ok = board.ensure(n) && start.ensure(n) && alive.ensure(n) && length.ensure(n) && outcome.ensure(n) && actions.ensure(nt) &&
               forced.ensure(n) && err.ensure(n) && states.ensure(n * 18) && logits.ensure(n * TTT_ACTIONS) &&
               value.ensure(n) && probs.ensure(n * TTT_ACTIONS) && tally.ensure(8) && h_tally.ensure(8);
     for (int s = 0; s < 2; ++s)
@@ -447,6 +448,57 @@ nz_status check_device_flag(nz_engine* e, hipStream_t s) {
   return NZ_OK;
 }
 
+// ---- start positions (nz_engine_reset_to, nz_engine_match_play_from, nz_engine_policy_actions) ------------------------
+// The one check of a position a caller names: nullptr when it is playable, else the condition it
+// fails.  How the position arose is not checked.
+const char* ttt_unplayable(uint32_t b) {
+  auto line = [](uint32_t m) {
+    return (m & 0007u) == 0007u || (m & 0070u) == 0070u || (m & 0700u) == 0700u || (m & 0111u) == 0111u ||
+           (m & 0222u) == 0222u || (m & 0444u) == 0444u || (m & 0421u) == 0421u || (m & 0124u) == 0124u;
+  };
+  if (b & ~0x01ff01ffu) return "a bit outside the stone sets (bits 0-8 and 16-24) is set";
+  const uint32_t p1 = b & 0x1ffu, p2 = (b >> 16) & 0x1ffu;
+  if (p1 & p2) return "a cell holds a stone of both players";
+  const int diff = __builtin_popcount(p1) - __builtin_popcount(p2);
+  if (diff != 0 && diff != 1) return "stones(p1) - stones(p2) is neither 0 nor 1";
+  if (line(p1) || line(p2)) return "a side has a line: the game is over";
+  if ((p1 | p2) == 0x1ffu) return "no cell is empty";
+  return nullptr;
+}
+// what the kernels of ttt_agents.hip borrow of the first n matches' state
+TttMatchArgs match_args(MatchArrays& m, int n) {
+  TttMatchArgs a{};
+  a.n = n;
+  a.board = m.board.get(); a.alive = m.alive.get(); a.length = m.length.get(); a.outcome = m.outcome.get();
+  a.actions = m.actions.get(); a.forced = m.forced.get(); a.err = m.err.get();
+  a.states = m.states.get(); a.probs = m.probs.get();
+  for (int i = 0; i < 2; ++i) {
+    a.agent_actions[i] = m.agent_actions[i].get(); a.agent_n_legal[i] = m.agent_n_legal[i].get();
+    a.mt_keys[i] = m.mt_keys[i].get(); a.mt_pos[i] = m.mt_pos[i].get();
+  }
+  return a;
+}
+// Every board playable, and with `same_ply` all at one stone count (returned in *stones); else the refusal's words.
+bool check_start_boards(const uint32_t* boards, int n, bool same_ply, int* stones, std::string& msg) {
+  for (int i = 0; i < n; ++i) {
+    const char* why = ttt_unplayable(boards[i]);
+    if (why) {
+      msg = text("start board %d (0x%08x) is not playable: %s", i, boards[i], why);
+      return false;
+    }
+  }
+  const int k0 = __builtin_popcount(boards[0]);
+  for (int i = 1; same_ply && i < n; ++i) {
+    const int k = __builtin_popcount(boards[i]);
+    if (k != k0) {
+      msg = text("start boards 0 and %d hold %d and %d stones: every match of a round starts at the same ply", i, k0, k);
+      return false;
+    }
+  }
+  if (stones) *stones = k0;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -569,7 +621,7 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   for (PinnedBuf<double>* b : {&e->h_noise, &e->h_uniforms, &e->h_game_noise, &e->h_game_uniforms, &e->h_next_noise, &e->h_next_uniforms})
     memset(b->get(), 0, b->size() * sizeof(double));
 
-  launch_reset(p, nullptr);
+  launch_reset(p, nullptr, nullptr);
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, NZ_ERR_HIP, "reset kernel failed"));
   *out = e;
   return NZ_OK;
@@ -717,7 +769,26 @@ nz_status nz_engine_reset(nz_engine* e, void* stream) {
   if (!e) return NZ_ERR_ARG;
   NZ_HIP(e, hipSetDevice(e->device));
   Span sp(e, as_stream(stream), 2);
-  launch_reset(e->tp, as_stream(stream));
+  launch_reset(e->tp, nullptr, as_stream(stream));
+  NZ_HIP(e, hipGetLastError());
+  return NZ_OK;
+}
+
+nz_status nz_engine_reset_to(nz_engine* e, const uint32_t* boards_host, void* stream) {
+  if (!e || !boards_host) return fail(e, NZ_ERR_ARG, "nz_engine_reset_to: NULL %s", e ? "boards" : "engine");
+  if (e->cfg.training)
+    return fail(e, NZ_ERR_ARG, "a training engine starts every game at the empty board (start positions are for "
+                               "evaluation engines: create it with training = 0)");
+  if (e->n_slots != e->n_games)
+    return fail(e, NZ_ERR_STATE, "start positions need the lock-step route: n_slots == n_games (every game of the round in flight)");
+  std::string msg;
+  if (!check_start_boards(boards_host, e->n_games, false, nullptr, msg)) return fail(e, NZ_ERR_ARG, "%s", msg.c_str());
+  NZ_HIP(e, hipSetDevice(e->device));
+  if (!e->dev.start_board.ensure((size_t)e->n_games)) return fail(e, NZ_ERR_HIP, "device allocation failed (start boards)");
+  hipStream_t s = as_stream(stream);
+  NZ_HIP(e, hipMemcpyAsync(e->dev.start_board.get(), boards_host, (size_t)e->n_games * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  Span sp(e, s, 2);
+  launch_reset(e->tp, e->dev.start_board.get(), s);
   NZ_HIP(e, hipGetLastError());
   return NZ_OK;
 }
@@ -1187,6 +1258,13 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
 nz_status nz_engine_match_play(nz_engine* side1, int32_t kind1, nz_engine* side2, int32_t kind2,
                                const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
                                const nz_ttt_match_result* out, void* stream) {
+  return nz_engine_match_play_from(side1, kind1, side2, kind2, agent_seeds1_host, agent_seeds2_host, nullptr, out, stream);
+}
+
+// From start positions (all at one ply k, so the mover's side is still known here): plies k .. 8 are enqueued.
+nz_status nz_engine_match_play_from(nz_engine* side1, int32_t kind1, nz_engine* side2, int32_t kind2,
+                                    const uint32_t* agent_seeds1_host, const uint32_t* agent_seeds2_host,
+                                    const uint32_t* start_boards_host, const nz_ttt_match_result* out, void* stream) {
   nz_engine* const eng[2] = {side1, side2};
   const int32_t kind[2] = {kind1, kind2};
   const uint32_t* const seeds[2] = {agent_seeds1_host, agent_seeds2_host};
@@ -1225,37 +1303,41 @@ nz_status nz_engine_match_play(nz_engine* side1, int32_t kind1, nz_engine* side2
 
   nz_engine* const host = side1 ? side1 : side2;
   const int n = host->n_games;
+  int first_ply = 0;
+  if (start_boards_host) {
+    std::string msg;
+    if (!check_start_boards(start_boards_host, n, true, &first_ply, msg)) return refuse(NZ_ERR_ARG, msg);
+  }
   hipStream_t s = as_stream(stream);
   NZ_HIP(host, hipSetDevice(host->device));
   MatchArrays& m = host->match;
   if (!m.ensure((size_t)n)) return fail(host, NZ_ERR_HIP, "device allocation failed (match state)");
   host->match_kinds[0] = host->match_kinds[1] = -1;
-  TttMatchArgs a{};
-  a.n = n;
-  a.board = m.board.get(); a.alive = m.alive.get(); a.length = m.length.get(); a.outcome = m.outcome.get();
-  a.actions = m.actions.get(); a.forced = m.forced.get(); a.err = m.err.get();
-  a.states = m.states.get(); a.probs = m.probs.get();
-  for (int i = 0; i < 2; ++i) {
-    a.agent_actions[i] = m.agent_actions[i].get(); a.agent_n_legal[i] = m.agent_n_legal[i].get();
-    a.mt_keys[i] = m.mt_keys[i].get(); a.mt_pos[i] = m.mt_pos[i].get();
-  }
+  TttMatchArgs a = match_args(m, n);
 
+  const uint32_t* start = nullptr;                           // the device copy every reset below reads
+  if (start_boards_host) {
+    NZ_HIP(host, hipMemcpyAsync(m.start.get(), start_boards_host, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    start = m.start.get();
+  }
   nz_engine* mcts[2] = {nullptr, nullptr};
   for (int i = 0; i < 2; ++i)
     if (kind[i] == NZ_AGENT_MCTS) mcts[i] = eng[i];
   for (int i = 0; i < 2; ++i) {
     if (eng[i] && !(i == 1 && eng[1] == eng[0])) {
-      const nz_status st = nz_engine_reset(eng[i], stream);
-      if (st != NZ_OK) return st;
+      // nz_engine_reset's launch with the start boards.  No hipSetDevice and no status of its own: an engine on
+      // another device than the host engine's was refused above, and hipGetLastError is checked after the tally.
+      Span sp(eng[i], s, 2);
+      launch_reset(eng[i]->tp, start, s);
     }
     if (kind[i] == NZ_AGENT_RANDOM) {
       NZ_HIP(host, hipMemcpyAsync(m.seeds[i].get(), seeds[i], (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
       NZ_HIP(host, agent_seed_launch(m.seeds[i].get(), a.mt_keys[i], a.mt_pos[i], n, s));
     }
   }
-  ttt_match_reset_launch(a, s);
+  ttt_match_reset_launch(a, start, s);
 
-  for (int ply = 0; ply < TTT_MAX_MOVES; ++ply) {
+  for (int ply = first_ply; ply < TTT_MAX_MOVES; ++ply) {
     const int mv = ply & 1;                                  // side 1 moves for player 1, the first mover
     for (nz_engine* e : mcts)
       if (e) search_lockstep(e, nullptr, s);                 // the mover's choose_action, the opponent's update_subtree
@@ -1319,6 +1401,37 @@ nz_status nz_engine_match_streams(nz_engine* e, int32_t side, uint32_t* keys_hos
   NZ_HIP(e, hipDeviceSynchronize());
   NZ_HIP(e, hipMemcpy(keys_host, e->match.mt_keys[side].get(), (size_t)e->n_games * MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
   NZ_HIP(e, hipMemcpy(pos_host, e->match.mt_pos[side].get(), (size_t)e->n_games * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return NZ_OK;
+}
+
+nz_status nz_engine_policy_actions(nz_engine* e, const uint32_t* boards_host, int32_t n, int32_t* actions_dev, void* stream) {
+  if (!e || !boards_host || !actions_dev)
+    return fail(e, NZ_ERR_ARG, "nz_engine_policy_actions: NULL %s", !e ? "engine" : !boards_host ? "boards" : "actions");
+  if (n <= 0 || n > e->n_games) return fail(e, NZ_ERR_ARG, "%d positions: an engine of %d games takes 1 .. %d", n, e->n_games, e->n_games);
+  if (!e->have_net && !e->have_table)
+    return fail(e, NZ_ERR_ARG, "no network: call nz_engine_set_weights or nz_engine_set_table first");
+  std::string msg;
+  if (!check_start_boards(boards_host, n, false, nullptr, msg)) return fail(e, NZ_ERR_ARG, "%s", msg.c_str());
+  hipStream_t s = as_stream(stream);
+  NZ_HIP(e, hipSetDevice(e->device));
+  MatchArrays& m = e->match;
+  if (!m.ensure((size_t)e->n_games)) return fail(e, NZ_ERR_HIP, "device allocation failed (match state)");
+  e->match_kinds[0] = e->match_kinds[1] = -1;                // the match state is overwritten
+  TttMatchArgs a = match_args(m, n);
+  NZ_HIP(e, hipMemcpyAsync(m.start.get(), boards_host, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  ttt_match_reset_launch(a, m.start.get(), s);
+  const float* table = e->tp.table;
+  if (!table) {
+    ttt_state_image_launch(a, s);
+    launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, a.states, nullptr, n, m.logits.get(), m.value.get(), m.probs.get(),
+               nullptr, s);
+  }
+  // The mover runs as side 0 whoever is to move: only a.forced is read here.  Its by-ply rows (agent_actions[0] /
+  // agent_n_legal[0]) are written too, into a match state declared overwritten above.  A playable position has an
+  // empty cell, so forced is set for every one.
+  ttt_agent_move_launch(a, 0, NZ_AGENT_POLICY, table, s);
+  NZ_HIP(e, hipGetLastError());
+  NZ_HIP(e, hipMemcpyAsync(actions_dev, a.forced, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   return NZ_OK;
 }
 

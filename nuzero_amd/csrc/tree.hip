@@ -11,7 +11,8 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int GAMES_PER_BLOCK = BLOCK / LANES_PER_GAME;
 
-__global__ void reset_kernel(TreeParams p) {
+// `boards` (nz_engine_reset_to; nullptr: the empty board): each game's start position, checked playable by the host
+__global__ void reset_kernel(TreeParams p, const uint32_t* __restrict__ boards) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g == 0) {
     p.leaf_count[0] = 0;
@@ -22,7 +23,7 @@ __global__ void reset_kernel(TreeParams p) {
   if (g < p.n_games) p.alive[g] = g < p.n_slots ? 1 : 0;
   if (g < p.n_slots) {          // per-slot state
     arena_reset(arena_of(p, g));
-    p.board[g] = 0u;
+    p.board[g] = boards ? boards[g] : 0u;
     p.root[g] = 0;
     p.node_count[g] = 1;
     p.sims_left[g] = p.sims;
@@ -219,9 +220,9 @@ __global__ void export_moves_kernel(TreeParams p, int32_t* visits, int32_t* acti
 
 }  // namespace
 
-void launch_reset(const TreeParams& p, hipStream_t s) {
+void launch_reset(const TreeParams& p, const uint32_t* boards, hipStream_t s) {
   const int n = p.n_games > p.n_slots ? p.n_games : p.n_slots;
-  hipLaunchKernelGGL(reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, boards);
 }
 void launch_noise(const TreeParams& p, const double* noise, hipStream_t s) {
   const int blocks = (p.n_games + GAMES_PER_BLOCK - 1) / GAMES_PER_BLOCK;

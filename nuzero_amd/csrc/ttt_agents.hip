@@ -21,7 +21,7 @@ namespace {
 
 static_assert(MT_N % 4 == 0, "keys are copied in 16-byte words");
 
-__global__ void ttt_match_reset_kernel(TttMatchArgs a) {
+__global__ void ttt_match_reset_kernel(TttMatchArgs a, const uint32_t* __restrict__ start) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;          // over n * 9
   if (idx >= a.n * TTT_MAX_MOVES) return;
   a.actions[idx] = -1;
@@ -31,9 +31,10 @@ __global__ void ttt_match_reset_kernel(TttMatchArgs a) {
     a.agent_n_legal[s][idx] = 0;
   }
   if (idx < a.n) {
-    a.board[idx] = 0u;
+    const uint32_t board = start ? start[idx] : 0u;
+    a.board[idx] = board;
     a.alive[idx] = 1;
-    a.length[idx] = 0;
+    a.length[idx] = ttt_length(board);                            // the record is by absolute ply
     a.outcome[idx] = 0;
     a.forced[idx] = -1;
     a.err[idx] = 0;
@@ -160,9 +161,9 @@ __global__ void ttt_match_tally_kernel(TttMatchArgs a, const int32_t* __restrict
 
 }  // namespace
 
-void ttt_match_reset_launch(const TttMatchArgs& a, hipStream_t s) {
+void ttt_match_reset_launch(const TttMatchArgs& a, const uint32_t* start, hipStream_t s) {
   const int total = a.n * TTT_MAX_MOVES;
-  hipLaunchKernelGGL(ttt_match_reset_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ttt_match_reset_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a, start);
 }
 void ttt_state_image_launch(const TttMatchArgs& a, hipStream_t s) {
   const int total = a.n * 18;

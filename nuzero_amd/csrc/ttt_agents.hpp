@@ -28,7 +28,9 @@ struct TttMatchArgs {
   const float* probs;            // [n][9] its post-softmax output
 };
 
-void ttt_match_reset_launch(const TttMatchArgs& a, hipStream_t s);
+// start: [n] the matches' start positions (playable, checked by the host; lengths begin at their stone counts), or
+// nullptr for the empty board
+void ttt_match_reset_launch(const TttMatchArgs& a, const uint32_t* start, hipStream_t s);
 // the policy mover's network input: every live match's position as two planes (finished matches: zeros)
 void ttt_state_image_launch(const TttMatchArgs& a, hipStream_t s);
 // the scripted mover's decision for every live match: side 0 / 1, kind NZ_AGENT_POLICY (probabilities from `table`'s row

@@ -138,9 +138,28 @@ class SelfPlayEngine:
         return dict(zip(("k_loops", "input_planes", "epilogues", "barriers"), list(out)))
 
     # ---- stepping --------------------------------------------------------------
-    def reset(self):
+    def reset(self, boards=None):
+        """Every game back to the empty board with an unexpanded root; with `boards` (uint32 [n_games], playable
+        positions: nuzero_amd.ttt_positions) game g starts at boards[g] instead and the engine's records count from
+        there (evaluation engines on the lock-step route only; nz_engine_reset_to)."""
         with torch.cuda.device(self.device):
-            check(lib.nz_engine_reset(self._h, _stream()), self._h)
+            if boards is None:
+                check(lib.nz_engine_reset(self._h, _stream()), self._h)
+                return
+            b = np.ascontiguousarray(np.asarray(boards, dtype=np.uint32).reshape(-1))
+            if len(b) != self.n_games:
+                raise ValueError(f"{len(b)} boards for {self.n_games} games")
+            check(lib.nz_engine_reset_to(self._h, c_void_p(b.ctypes.data), _stream()), self._h)
+
+    def policy_actions(self, boards):
+        """The bare-policy agent's decision on each of up to n_games playable positions (uint32 [n]): the legal cell
+        of largest softmax probability from the engine's network or table, lowest index on a tie
+        (nz_engine_policy_actions).  int32 [n] on the device."""
+        b = np.ascontiguousarray(np.asarray(boards, dtype=np.uint32).reshape(-1))
+        out = torch.empty((len(b),), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.nz_engine_policy_actions(self._h, c_void_p(b.ctypes.data), len(b), _ptr(out), _stream()), self._h)
+        return out
 
     def root_children(self):
         out = torch.empty((self.n_games,), dtype=torch.int32, device=self.device)

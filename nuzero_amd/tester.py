@@ -24,7 +24,11 @@ Tic-Tac-Toe (C ABI nz_engine_match_play): `TttMatch` (two MCTS agents), `TttAgen
 and random sides, same specs and rules) and `TttTester`.  A game lasts at most nine plies and every match of a round is
 at the same ply, so one call enqueues the whole round with no host round trip.  Two MCTS sides, or MCTS against the bare
 policy, are deterministic from the empty board: N such matches are N copies of one game; only matches with a random
-side differ from each other.
+side differ from each other.  The remedy is to start the matches elsewhere: `play(..., start_boards=...)` starts match i
+at a position of the caller's (nuzero_amd.ttt_positions; all of one round at the same ply), every MCTS side from a fresh
+root there; `TttTester.test_from_openings` plays every opening of k plies with both colour assignments, and
+`TttTester.score_against_perfect_play` asks one agent for its move in each of the 4,520 reachable positions of the solved
+game (C ABI nz_engine_match_play_from, nz_engine_reset_to, nz_engine_policy_actions).
 
 Out of scope: SCS's scripted agents (the reference's hand-written SCS players).
 """
@@ -310,6 +314,16 @@ def _check_ttt_net(i, kind, net):
         raise ValueError(f"agent {i + 1}: net must be a state_dict, (state_dict, kwargs) or a ({TTT_TABLE_ROWS}, 10) table")
 
 
+def _load_ttt_net(engine, net, net_kwargs):
+    if _is_table(net):
+        import torch
+        engine.set_table(net.cpu().numpy() if isinstance(net, torch.Tensor) else net)
+    elif isinstance(net, Mapping):
+        engine.set_weights(net, **net_kwargs)
+    else:
+        engine.set_weights(net[0], **dict(net_kwargs, **net[1]))
+
+
 class TttAgentMatch:
     """n_matches Tic-Tac-Toe matches between agent1 (player 1, the first mover) and agent2: specs ("mcts", search_cfg),
     ("policy",), ("random",) as ScsAgentMatch takes them, in any pairing but two random sides.  `engines`: per side the
@@ -345,10 +359,16 @@ class TttAgentMatch:
         for e in set(e for e in self.engines if e is not None):
             e.close()
 
-    def _check_play(self, nets, agent_seeds):
-        """What play() refuses before any GPU call; returns the per-side uint32 seed arrays (None: not a random side)."""
+    def _check_play(self, nets, agent_seeds, start_boards=None):
+        """What play() refuses before any GPU call; returns the per-side uint32 seed arrays (None: not a random side)
+        and the start boards as a uint32 array (None: the empty board)."""
         for i, (kind, net) in enumerate(zip(self.kinds, nets)):
             _check_ttt_net(i, kind, net)
+        if start_boards is not None:
+            from .ttt_positions import check_start_boards
+            if len(start_boards) != self.n_matches:
+                raise ValueError(f"{len(start_boards)} start_boards for {self.n_matches} matches")
+            start_boards = check_start_boards(start_boards, same_ply=True)
         per_side = [None, None]
         if "random" in self.kinds:
             if agent_seeds is None:
@@ -359,19 +379,15 @@ class TttAgentMatch:
                 raise ValueError(f"agent {i + 1}: {len(given)} agent_seeds for {self.n_matches} matches")
             from .scs import _seed_array
             per_side[i] = _seed_array(given)
-        return per_side
+        return per_side, start_boards
 
-    def _load(self, engine, net, net_kwargs):
-        if _is_table(net):
-            import torch
-            engine.set_table(net.cpu().numpy() if isinstance(net, torch.Tensor) else net)
-        elif isinstance(net, Mapping):
-            engine.set_weights(net, **net_kwargs)
-        else:
-            engine.set_weights(net[0], **dict(net_kwargs, **net[1]))
-
-    def play(self, net1, net2, agent_seeds=None, **net_kwargs):
-        """One round: every match from the empty board to its end.  net1 / net2: an MCTS or policy side's network -- a
+    def play(self, net1, net2, agent_seeds=None, start_boards=None, **net_kwargs):
+        """One round: every match from the empty board -- or, with `start_boards` (uint32 [n_matches], playable
+        positions that all hold the same number of stones k: nuzero_amd.ttt_positions), match i from start_boards[i],
+        every MCTS side from a fresh root there -- to its end.  The record stays by absolute ply: "actions"[i][p] is -1
+        for p < k, "lengths" the stone count of the final position, side 1 moves the even plies (with odd k side 2
+        moves first); an MCTS side's engine counts from the position, so its export() is the record shifted by k.
+        The result then holds "start_boards" (None without them).  net1 / net2: an MCTS or policy side's network -- a
         state_dict (with `net_kwargs`, SelfPlayEngine.set_weights' keyword arguments, or as a pair (state_dict,
         kwargs) of its own) or a (3^9, 10) table (set_table) -- None for a random side; with share_policy_engine the
         same net for both.  `agent_seeds` (a random side: required, one per
@@ -382,13 +398,13 @@ class TttAgentMatch:
         import torch
         from . import _lib
         nets = (net1, net2)
-        side_seeds = self._check_play(nets, agent_seeds)
+        side_seeds, start = self._check_play(nets, agent_seeds, start_boards)
         if self.engines[0] is not None and self.engines[0] is self.engines[1] and net1 is not net2:
             raise ValueError("two policy agents share one engine and one network: pass the same net for both")
         loaded = set()
         for e, net in zip(self.engines, nets):
             if e is not None and id(e) not in loaded:
-                self._load(e, net, net_kwargs)
+                _load_ttt_net(e, net, net_kwargs)
                 loaded.add(id(e))
         host = next(e for e in self.engines if e is not None)
         N, dev = self.n_matches, host.device
@@ -404,11 +420,12 @@ class TttAgentMatch:
         sp = [c_void_p(s.ctypes.data) if s is not None else None for s in side_seeds]
         with torch.cuda.device(dev):
             stream = c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(_lib.lib.nz_engine_match_play(h[0], code[self.kinds[0]], h[1], code[self.kinds[1]], sp[0], sp[1],
-                                                     byref(res), stream), host._h)
+            _lib.check(_lib.lib.nz_engine_match_play_from(h[0], code[self.kinds[0]], h[1], code[self.kinds[1]], sp[0], sp[1],
+                                                          c_void_p(start.ctypes.data) if start is not None else None,
+                                                          byref(res), stream), host._h)
         out = {"p1_wins": int(tally[0]), "p2_wins": int(tally[1]), "draws": int(tally[2]), "unfinished": int(tally[3]),
                "actions": actions.cpu().numpy(), "lengths": lengths.cpu().numpy(), "outcomes": outcomes.cpu().numpy(),
-               "agent_actions": [None, None], "agent_n_legal": [None, None]}
+               "agent_actions": [None, None], "agent_n_legal": [None, None], "start_boards": start}
         for i, kind in enumerate(self.kinds):
             if kind != "mcts":
                 out["agent_actions"][i], out["agent_n_legal"][i] = ag_a[i].cpu().numpy(), ag_n[i].cpu().numpy()
@@ -426,7 +443,8 @@ class TttAgentMatch:
 
 class TttMatch(TttAgentMatch):
     """n_matches matches between two MCTS agents on Tic-Tac-Toe (search_cfg_1 plays player 1), one engine each.  Both are
-    deterministic, so the matches of a round are copies of one game."""
+    deterministic, so from the empty board the matches of a round are copies of one game: pass `start_boards` (one
+    position per match, e.g. ttt_positions.openings(2)) for matches that differ."""
 
     def __init__(self, search_cfg_1, search_cfg_2, n_matches, device=0):
         for i, sc in enumerate((search_cfg_1, search_cfg_2)):
@@ -434,8 +452,8 @@ class TttMatch(TttAgentMatch):
                 raise ValueError(f"agent {i + 1}: TttMatch takes two search configs (scripted sides: TttAgentMatch)")
         super().__init__(("mcts", search_cfg_1), ("mcts", search_cfg_2), n_matches, device=device)
 
-    def play(self, weights1, weights2, **net_kwargs):
-        return super().play(weights1, weights2, **net_kwargs)
+    def play(self, weights1, weights2, start_boards=None, **net_kwargs):
+        return super().play(weights1, weights2, start_boards=start_boards, **net_kwargs)
 
 
 class TttTester:
@@ -445,20 +463,88 @@ class TttTester:
 
     def __init__(self, device=0):
         self.device = device
-        self._match = None
+        self._match = None           # (key, TttAgentMatch) of the last call
+        self._exchanged = None       # the same pairing with the sides exchanged, while test_from_openings plays both
+        self.opening_rounds = None   # the two play() results of the last test_from_openings
 
     def close(self):
-        if self._match is not None:
-            self._match[1].close()
-            self._match = None
+        for m in (self._match, self._exchanged):
+            if m is not None:
+                m[1].close()
+        self._match = self._exchanged = None
 
-    def test_using_agents(self, agent1, net1, agent2, net2, n, agent_seeds=None, **net_kwargs):
+    def _match_of(self, agent1, agent2, n):
+        """The match of this pairing and size.  The last one is kept, and beside it the one with the sides exchanged,
+        so repeated test_from_openings calls between two different agents build their engines once; any other
+        pairing closes both."""
         (k1, c1), (k2, c2) = _agent_spec(agent1), _agent_spec(agent2)
         key = (repr((k1, c1)), repr((k2, c2)), int(n))
-        if self._match is None or self._match[0] != key:
+        if self._match is not None and self._match[0] == key:
+            return self._match[1]
+        if self._exchanged is not None and self._exchanged[0] == key:
+            self._match, self._exchanged = self._exchanged, self._match
+            return self._match[1]
+        if self._match is not None and self._match[0] == (key[1], key[0], key[2]):
+            if self._exchanged is not None:
+                self._exchanged[1].close()
+            self._exchanged, self._match = self._match, None
+        else:
             self.close()
-            self._match = (key, TttAgentMatch((k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device))
-        r = self._match[1].play(net1, net2, agent_seeds=agent_seeds, **net_kwargs)
+        self._match = (key, TttAgentMatch((k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device))
+        return self._match[1]
+
+    def test_using_agents(self, agent1, net1, agent2, net2, n, agent_seeds=None, **net_kwargs):
+        r = self._match_of(agent1, agent2, n).play(net1, net2, agent_seeds=agent_seeds, **net_kwargs)
         return r["p1_wins"], r["p2_wins"], r["draws"]
 
     Test_using_agents = test_using_agents
+
+    def test_from_openings(self, agent1, net1, agent2, net2, plies=2, agent_seeds=None, **net_kwargs):
+        """Every opening of `plies` plies (ttt_positions.openings: 72 for two plies) played twice, the second time with
+        the agents exchanging sides: matches that differ from each other even between two deterministic agents.
+        Returns (agent1_wins, agent2_wins, draws) over both rounds, counted per agent, not per side.  `agent_seeds` (a
+        random agent): one per opening, used in both rounds.  The two rounds' play() results are kept in
+        `opening_rounds` (in the second, side 1 is agent2)."""
+        from .ttt_positions import openings
+        boards = openings(plies)
+        rounds = []
+        for (a, na), (b, nb) in (((agent1, net1), (agent2, net2)), ((agent2, net2), (agent1, net1))):
+            rounds.append(self._match_of(a, b, len(boards)).play(na, nb, agent_seeds=agent_seeds, start_boards=boards,
+                                                                 **net_kwargs))
+        self.opening_rounds = tuple(rounds)
+        r1, r2 = rounds
+        return r1["p1_wins"] + r2["p2_wins"], r1["p2_wins"] + r2["p1_wins"], r1["draws"] + r2["draws"]
+
+    def score_against_perfect_play(self, agent, net, **net_kwargs):
+        """An absolute strength measure that needs no opponent: the agent's move in every one of the 4,520 reachable
+        non-terminal positions (each searched from a fresh root), scored against perfect play of the solved game.
+        `agent`: a search config / ("mcts", cfg), or ("policy",).  Returns a dict: "positions" (4520), "optimal" (the
+        decisions inside the perfect-play mask), "by_ply" int [9, 2] (positions, optimal, by stone count), "boards"
+        uint32 [4520] (ttt_positions.reachable_nonterminal), "actions" int32 [4520], "is_optimal" bool [4520]."""
+        from .ttt_positions import perfect_play, reachable_nonterminal, ttt_code
+        kind, cfg = _agent_spec(agent)
+        if kind == "random":
+            raise ValueError("a random agent has no move to score: its choice is its seed's (score an MCTS or policy agent)")
+        if cfg is not None and not cfg["Simulation"]["keep_subtree"]:
+            raise ValueError("keep_subtree = False is not supported (every shipped search config keeps it)")
+        _check_ttt_net(0, kind, net)
+        boards = reachable_nonterminal()
+        from .engine import SelfPlayEngine            # (needs the GPU from here on)
+        e = SelfPlayEngine(cfg or _NO_SEARCH, len(boards), training=False, device=self.device)
+        try:
+            _load_ttt_net(e, net, net_kwargs)
+            if kind == "mcts":
+                e.reset(boards)
+                e.search()
+                e.apply()
+                actions = e.last_actions().cpu().numpy()
+            else:
+                actions = e.policy_actions(boards).cpu().numpy()
+        finally:
+            e.close()
+        masks = perfect_play()[1][[ttt_code(b) for b in boards]]
+        ok = ((masks >> np.clip(actions, 0, 8)) & 1).astype(bool) & (actions >= 0)
+        stones = np.array([bin(int(b)).count("1") for b in boards])
+        by_ply = np.stack([np.bincount(stones, minlength=9), np.bincount(stones[ok], minlength=9)], 1)
+        return {"positions": len(boards), "optimal": int(ok.sum()), "by_ply": by_ply, "boards": boards,
+                "actions": actions, "is_optimal": ok}
