@@ -733,7 +733,15 @@ nz_status nz_replay_check(nz_replay* h, void* stream);
  * policy_loss: cross entropy with label smoothing 0.02 (AlphaZero.py:327), KL divergence, masked MSE
  * (Utils/Functions/loss_functions.py:7-26); value_loss: squared / absolute error (loss_functions.py:28-33);
  * normalize_policy: divide the policy loss by log(batch) as the reference does (AlphaZero.py:912-915).
- * workspace_dev: 2 * batch floats.  float32 arithmetic; results agree with the reference's to ~1e-6 relative.
+ * workspace_dev: 2 * batch floats.  Sums in a fixed order: the same inputs give the same bits.  float32 per element, the
+ * sums behind the three losses carried in double (a small KL divergence is the difference of two sums of size log A);
+ * log_softmax as (x - max) - log(sum exp(x - max)), so a common offset of the logits costs nothing.  Held to the
+ * reference's loop in float64 (tests/test_gpu_loss_edges.py: 1 <= A <= 2100, batches up to 2048, logits 2 N, 30 N,
+ * 2 N + 1e4, all equal, one entry +80; sparse, one-hot and dense targets): the losses within 2e-6 relative, which is
+ * where the reference's own float32 loop sits; the gradients within 2e-6 of their largest entry, EXCEPT where float32
+ * softmax itself has no more to give -- rows saturated by |logits| of 30 and more, whose whole gradient is ~1e-10 of
+ * 1 / batch (there: within 2e-6 / batch absolute, or 4 x the error of the reference's float32 loop on the same row).  These are
+ * the bounds the test asserts; DESIGN.md section 2 statement 12 says what has been measured on a device.
  * Masked MSE with a target row of zeros only (the reference raises ZeroDivisionError there): losses3[1] and [2] come out
  * NaN, that sample's dlogits row is zeros. */
 enum { NZ_LOSS_CE = 0, NZ_LOSS_KLD = 1, NZ_LOSS_MSE = 2 };

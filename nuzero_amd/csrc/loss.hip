@@ -15,7 +15,8 @@
 // One workgroup per sample: log-sum-exp of the logits (wave shuffles + one LDS exchange), the sample's loss terms and
 // d(combined) / d(logits), d(combined) / d(value) in the same pass over the A actions; per-sample losses are summed
 // on the host side of the ABI by a second tiny kernel in a fixed order (so the result does not depend on scheduling).
-// float32 throughout, like the reference (which accumulates float32 tensors); HBM-bound: 12 bytes per action.
+// float32 per element, like the reference (which works on float32 tensors); the sums behind the three losses are
+// carried in double (see loss_kernel); HBM-bound: 12 bytes per action.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -55,49 +56,66 @@ __device__ __forceinline__ float block_reduce(float v, float* scratch, bool is_m
   return r;
 }
 
+__device__ __forceinline__ double block_sum(double v, double* scratch) {   // the same tree in double
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) scratch[wave] = v;
+  __syncthreads();
+  return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+}
+
 __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
   __shared__ float scratch[4];
+  __shared__ double scratch_d[4];
   const int b = blockIdx.x, tid = threadIdx.x, A = a.actions;
   const float* x = a.logits + (size_t)b * A;
   const float* t = a.target_policies + (size_t)b * A;
   float mx = -INFINITY;
   for (int i = tid; i < A; i += 256) mx = fmaxf(mx, x[i]);
   mx = block_reduce(mx, scratch, true);
-  float se = 0.f;
-  for (int i = tid; i < A; i += 256) se += expf(x[i] - mx);
-  se = block_reduce(se, scratch, false);
-  const float lse = mx + logf(se);
+  // The sums that make up the LOSS are carried in double: a KL divergence between a near-uniform target and near-equal
+  // logits is the small difference of two sums of size log(A), and one float32 rounding of log(sum) -- the same for
+  // every action, so it does not average out -- is 3e-6 of such a loss at A = 255.  Elementwise work stays float32.
+  double se = 0.0;
+  for (int i = tid; i < A; i += 256) se += (double)expf(x[i] - mx);
+  se = block_sum(se, scratch_d);
+  // log_softmax(x)_i = (x_i - mx) - log(se), the maximum subtracted FIRST (torch's order): mx + log(se) is rounded at the
+  // spacing of mx, 1e-3 for logits near 1e4, and x_i - lse would carry that into every log-probability and gradient
+  const double lzd = log(se);
+  const float lz = (float)lzd;
 
-  float loss_part = 0.f, aux = 0.f, cnt = 0.f;
+  double loss_part = 0.0;
+  float aux = 0.f, cnt = 0.f;
   if (a.policy_loss == NZ_LOSS_CE) {
     const float eps = a.smoothing, uni = eps / (float)A;
     for (int i = tid; i < A; i += 256) {
       const float tp = t[i] * (1.0f - eps) + uni;
-      loss_part -= tp * (x[i] - lse);
+      loss_part -= (double)tp * ((double)(x[i] - mx) - lzd);
     }
   } else if (a.policy_loss == NZ_LOSS_KLD) {
     for (int i = tid; i < A; i += 256) {
       const float ti = t[i];
-      if (ti > 0.f) loss_part += ti * (logf(ti) - (x[i] - lse));
+      if (ti > 0.f) loss_part += (double)ti * ((double)logf(ti) - ((double)(x[i] - mx) - lzd));
       aux += ti;                                   // sum of the targets (gradient of the log-softmax term)
     }
   } else {                                         // masked MSE on softmax(x)
     for (int i = tid; i < A; i += 256) {
       const float ti = t[i];
       if (ti != 0.f) {
-        const float p = expf(x[i] - lse), d = ti - p;
-        loss_part += d * d;
+        const float p = expf((x[i] - mx) - lz), d = ti - p;
+        loss_part += (double)(d * d);
         aux += d * p;                              // sum_j [t_j != 0] (t_j - p_j) p_j
         cnt += 1.f;
       }
     }
   }
-  loss_part = block_reduce(loss_part, scratch, false);
+  loss_part = block_sum(loss_part, scratch_d);
   if (a.policy_loss != NZ_LOSS_CE) aux = block_reduce(aux, scratch, false);
   if (a.policy_loss == NZ_LOSS_MSE) cnt = block_reduce(cnt, scratch, false);
-  float policy_term = loss_part;
-  if (a.policy_loss == NZ_LOSS_KLD) policy_term = loss_part / (float)A;
-  if (a.policy_loss == NZ_LOSS_MSE) policy_term = loss_part / cnt;
+  float policy_term = (float)loss_part;
+  if (a.policy_loss == NZ_LOSS_KLD) policy_term = (float)(loss_part / (double)A);
+  if (a.policy_loss == NZ_LOSS_MSE) policy_term = (float)(loss_part / (double)cnt);   // cnt == 0: NaN, as before
 
   if (a.dlogits) {
     float* g = a.dlogits + (size_t)b * A;
@@ -109,18 +127,18 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
       st = block_reduce(st, scratch, false);
       for (int i = tid; i < A; i += 256) {
         const float tp = t[i] * (1.0f - eps) + uni;
-        g[i] = s * (expf(x[i] - lse) * st - tp);
+        g[i] = s * (expf((x[i] - mx) - lz) * st - tp);
       }
     } else if (a.policy_loss == NZ_LOSS_KLD) {
       const float k = s / (float)A;
-      for (int i = tid; i < A; i += 256) g[i] = k * (expf(x[i] - lse) * aux - t[i]);
+      for (int i = tid; i < A; i += 256) g[i] = k * (expf((x[i] - mx) - lz) * aux - t[i]);
     } else {
       // (no target entry at all: the loss is 0 / 0 -- the reference raises ZeroDivisionError, loss_functions.py:7-26; the
       // sample's policy term is NaN, so the batch's loss says so, but its gradient row is zeros: one bad sample does
       // not poison the other samples' gradients)
       const float k = cnt > 0.f ? 2.0f * s / cnt : 0.f;
       for (int i = tid; i < A; i += 256) {         // d/dx_i sum_j m_j (t_j - p_j)^2 = 2 p_i (sum_j m_j (t_j - p_j) p_j - m_i (t_i - p_i))
-        const float p = expf(x[i] - lse);
+        const float p = expf((x[i] - mx) - lz);
         const float mi = t[i] != 0.f ? (t[i] - p) : 0.f;
         g[i] = k * p * (aux - mi);
       }
@@ -137,15 +155,16 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
   }
 }
 
-// sums of the per-sample terms in sample order (what the reference's `+=` loop does), one thread: B is a batch size
-__global__ void loss_sum_kernel(const float* __restrict__ per_sample, int batch, float policy_scale, float value_scale,
-                                float* __restrict__ out3) {
-  float p = 0.f, v = 0.f;
+// sums of the per-sample terms in sample order (the order of the reference's `+=` loop), one thread: B is a batch size.
+// Accumulated in double: a float32 running sum of 2048 terms alone wanders 1e-6 from the sum of its terms.
+__global__ void loss_sum_kernel(const float* __restrict__ per_sample, int batch, double policy_scale,
+                                double value_scale, float* __restrict__ out3) {
+  double p = 0.0, v = 0.0;
   for (int i = 0; i < batch; ++i) {
-    p += per_sample[2 * i];
-    v += per_sample[2 * i + 1];
+    p += (double)per_sample[2 * i];
+    v += (double)per_sample[2 * i + 1];
   }
-  const float vl = v * value_scale, pl = p * policy_scale;
+  const float vl = (float)(v * value_scale), pl = (float)(p * policy_scale);
   out3[0] = vl;
   out3[1] = pl;
   out3[2] = pl + vl;
@@ -179,7 +198,9 @@ nz_status nz_loss_forward_backward(const float* logits_dev, const float* values_
              normalize_policy ? (1.0f / logf((float)batch)) * inv_b : inv_b, inv_b, 0.02f};
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(loss_kernel, dim3(batch), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1), 0, s, workspace_dev, batch, a.policy_scale, a.value_scale,
+  const double value_scale = 1.0 / (double)batch;
+  const double policy_scale = normalize_policy ? value_scale / log((double)batch) : value_scale;
+  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1), 0, s, workspace_dev, batch, policy_scale, value_scale,
                      losses3_dev);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
