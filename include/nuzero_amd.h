@@ -716,15 +716,34 @@ nz_status nz_replay_create(nz_replay** out, int64_t capacity_positions, int32_t 
 void nz_replay_destroy(nz_replay* h);
 const char* nz_replay_last_error(const nz_replay* h);
 nz_status nz_replay_dims(const nz_replay* h, int64_t* capacity, int32_t* state_floats, int32_t* num_actions);
-/* exactly one of visits_dev [N, A] int32 / policies_dev [N, A] float32 / (child_action_dev, child_visit_dev
- * [N, max_children] int32 + n_children_dev [N]) */
+/* nz_replay_create: NZ_ERR_ARG for a NULL `out` or a size <= 0, NZ_ERR_HIP where `device` is no HIP device or the
+ * allocation fails (*out stays NULL; the message is read with nz_replay_last_error(NULL)).
+ *
+ * nz_replay_append: exactly one of visits_dev [N, A] int32 / policies_dev [N, A] float32 / (child_action_dev,
+ * child_visit_dev [N, max_children] int32 + n_children_dev [N]); game_value_dev holds one int32 per rows_per_game rows
+ * (the last game may have fewer).  NZ_ERR_ARG, with a message and nothing enqueued, for a NULL handle, states, values or
+ * slots, for none or more than one of the three forms, for child lists without visits, counts or max_children > 0, and for
+ * rows_per_game <= 0; n_rows <= 0 (and batch <= 0 in nz_replay_gather) is NZ_OK and does nothing.  Per row:
+ *   dst_slot = -1 (any negative slot) leaves the buffer alone;
+ *   dst_slot >= capacity raises flag 1, the row is not stored;
+ *   dense and sparse form: an action with 0 visits gets policy 0, also where the row's visits sum to 0 (never 0 / 0);
+ *   sparse form: only the first n_children[r] entries of row r's lists are read.  A child whose action is outside
+ *   0 .. A-1 raises flag 2 and is skipped (its visits still count in the row's sum); a count n_children[r] outside
+ *   0 .. max_children raises flag 2 and counts as 0 -- the row's state, value and game index are still stored, its policy
+ *   is zeros.  The rows of one call must name distinct slots, a row's children distinct actions.
+ * nz_replay_gather: each of the four outputs may be NULL; a slot outside 0 .. capacity-1 raises flag 4 and leaves that
+ * row of the outputs as it was; slots may repeat.
+ * The flags are one device word, OR-ed by the kernels.  nz_replay_check synchronises `stream` and returns
+ * NZ_ERR_OVERFLOW, with the word in the message, while any flag is set: 1 slot at or beyond capacity, 2 action or child
+ * count out of range, 4 batch slot out of range.  The word is sticky: checking does not clear it, a handle that has raised
+ * a flag reports it from every later check until it is destroyed. */
 nz_status nz_replay_append(nz_replay* h, const float* states_dev, const int32_t* visits_dev, const float* policies_dev,
                            const int32_t* child_action_dev, const int32_t* child_visit_dev, const int32_t* n_children_dev,
                            int32_t max_children, const int32_t* game_value_dev, int32_t rows_per_game,
                            const int64_t* dst_slot_dev, int64_t n_rows, int32_t game_index, void* stream);
 nz_status nz_replay_gather(nz_replay* h, const int64_t* slots_dev, int64_t batch, float* states_out, float* policies_out,
                            float* values_out, int32_t* game_index_out, void* stream);
-/* synchronises; NZ_ERR_OVERFLOW if a kernel saw a slot or an action out of range */
+/* synchronises; NZ_ERR_OVERFLOW if a kernel has seen a slot, an action or a child count out of range (sticky, see above) */
 nz_status nz_replay_check(nz_replay* h, void* stream);
 
 /* ---- batched loss ---------------------------------------------------------------

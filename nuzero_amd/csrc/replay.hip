@@ -87,10 +87,15 @@ __global__ __launch_bounds__(256) void append_kernel(AppendArgs a) {
     if (tid == 0) s_total = 0;
     __syncthreads();
     long long part = 0;
+    int k = 0;                   // sparse: the row's child count; one outside 0 .. max_children counts as 0 (flag 2)
     if (a.visits != nullptr) {
       for (int i = tid; i < A; i += 256) part += a.visits[r * A + i];
     } else {
-      const int k = a.n_children[r];
+      k = a.n_children[r];
+      if (k < 0 || k > a.max_children) {
+        if (tid == 0) atomicOr(a.error_flag, 2);
+        k = 0;
+      }
       for (int i = tid; i < k; i += 256) part += a.child_visit[r * a.max_children + i];
     }
     if (part) atomicAdd((unsigned long long*)&s_total, (unsigned long long)part);
@@ -104,11 +109,11 @@ __global__ __launch_bounds__(256) void append_kernel(AppendArgs a) {
     } else {
       for (int i = tid; i < A; i += 256) pol[i] = 0.0f;
       __syncthreads();
-      const int k = a.n_children[r];
       for (int i = tid; i < k; i += 256) {
         const int act = a.child_action[r * a.max_children + i];
         if (act < 0 || act >= A) { atomicOr(a.error_flag, 2); continue; }
-        pol[act] = (float)((double)a.child_visit[r * a.max_children + i] / total);
+        const int v = a.child_visit[r * a.max_children + i];
+        pol[act] = v ? (float)((double)v / total) : 0.0f;      // as the dense form: never 0 / 0
       }
     }
   }
@@ -188,7 +193,7 @@ nz_status nz_replay_append(nz_replay* h, const float* states_dev, const int32_t*
                            const int32_t* child_action_dev, const int32_t* child_visit_dev, const int32_t* n_children_dev,
                            int32_t max_children, const int32_t* game_value_dev, int32_t rows_per_game,
                            const int64_t* dst_slot_dev, int64_t n_rows, int32_t game_index, void* stream) {
-  if (!h || !states_dev || !game_value_dev || !dst_slot_dev) return NZ_ERR_ARG;
+  if (!h || !states_dev || !game_value_dev || !dst_slot_dev) return rfail(h, NZ_ERR_ARG, "null argument");
   const int modes = (visits_dev != nullptr) + (policies_dev != nullptr) + (child_action_dev != nullptr);
   if (modes != 1) return rfail(h, NZ_ERR_ARG, "exactly one of visits / policies / child lists must be given");
   if (child_action_dev && (!child_visit_dev || !n_children_dev || max_children <= 0))
@@ -206,7 +211,7 @@ nz_status nz_replay_append(nz_replay* h, const float* states_dev, const int32_t*
 
 nz_status nz_replay_gather(nz_replay* h, const int64_t* slots_dev, int64_t batch, float* states_out, float* policies_out,
                            float* values_out, int32_t* game_index_out, void* stream) {
-  if (!h || !slots_dev) return NZ_ERR_ARG;
+  if (!h || !slots_dev) return rfail(h, NZ_ERR_ARG, "null argument");
   if (batch <= 0) return NZ_OK;
   R_HIP(h, hipSetDevice(h->device));
   GatherArgs a{h->states.get(), h->policies.get(), h->values.get(), h->game_index.get(), slots_dev, states_out, policies_out, values_out,
@@ -217,13 +222,13 @@ nz_status nz_replay_gather(nz_replay* h, const int64_t* slots_dev, int64_t batch
 }
 
 nz_status nz_replay_check(nz_replay* h, void* stream) {
-  if (!h) return NZ_ERR_ARG;
+  if (!h) return rfail(nullptr, NZ_ERR_ARG, "null argument");
   R_HIP(h, hipSetDevice(h->device));
   int32_t f = 0;
   R_HIP(h, hipMemcpyAsync(&f, h->game_index.get() + h->capacity, sizeof(f), hipMemcpyDeviceToHost, (hipStream_t)stream));
   R_HIP(h, hipStreamSynchronize((hipStream_t)stream));
-  if (f) return rfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: 1 slot beyond capacity, 2 action out of range, "
-                                          "4 batch slot out of range)", f);
+  if (f) return rfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: 1 slot beyond capacity, 2 action or child count "
+                                          "out of range, 4 batch slot out of range)", f);
   return NZ_OK;
 }
 
