@@ -385,7 +385,15 @@ nz_status nz_scs_search_export(nz_scs_search* h, int32_t* actions, int32_t* tree
  *   probs_dev   float[n][policy_channels*rows*cols] softmax over ALL logits, may be NULL
  *   value_dev   float[n]
  *   n_dev       optional device int32: the live batch size (<= n) when the host does not
- *               know it yet (the leaf count of a simulation wave); NULL = n. */
+ *               know it yet (the leaf count of a simulation wave); NULL = n.  Outputs of the
+ *               positions from *n_dev on are not written; *n_dev == 0 writes nothing at all
+ *               and returns NZ_OK (as n == 0 does, without a launch).
+ * Shapes (pinned by tests/test_gpu_boardnet_edges.py against a float64 reference): any positive
+ * rows and cols (a board may be one cell wide or high), any positive width, in_channels and
+ * policy_channels (none has to be a multiple of 16), num_blocks >= 0, kernel_size 1 or 3
+ * (ConvNet trunk; the heads are 3x3), 0 <= n <= max_batch, RecurrentNet iterations >= 1.
+ * Anything else is refused with NZ_ERR_ARG and a message in nz_boardnet_last_error (of the
+ * handle, or of NULL where there is no handle). */
 typedef struct nz_boardnet nz_boardnet;
 nz_status nz_boardnet_create(nz_boardnet** out, const nz_net_desc* net, int32_t rows, int32_t cols,
                              int32_t max_batch, int32_t device);
@@ -397,9 +405,14 @@ nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, i
 nz_status nz_boardnet_forward(nz_boardnet* h, const float* images_dev, int32_t n, const int32_t* n_dev,
                               float* logits_dev, float* probs_dev, float* value_dev, void* stream);
 /* The same without the layout conversion: the network's own input buffer is rows of `row_stride` floats, channels
- * contiguous (zero beyond in_channels: never write there), row = ((position / 16) * rows*cols + cell) * 16 +
- * position % 16.  A producer (the SCS search kernel) writes the positions' planes there directly, then calls
- * nz_boardnet_forward_rows. */
+ * contiguous, row = ((position / 16) * rows*cols + cell) * 16 + position % 16.  A producer (the SCS search kernel)
+ * writes the positions' planes there directly, then calls nz_boardnet_forward_rows.  What the caller owes: channels
+ * 0 .. in_channels - 1 of every cell of the n (or *n_dev) live positions, written on `stream` or ordered before it.
+ * The channels from in_channels to row_stride are zero after nz_boardnet_create and after every nz_boardnet_forward
+ * and are best left alone; they meet zero weights, so any FINITE value there leaves the outputs unchanged, a NaN or
+ * an infinity does not.  Rows of positions past the live ones (up to max_batch rounded up to 16) may hold any finite
+ * values, stale planes of an earlier, larger batch included: no live position's output depends on them.  The buffer belongs
+ * to the handle (max_batch rounded up to 16 positions) and is overwritten by nz_boardnet_forward. */
 nz_status nz_boardnet_input_rows(nz_boardnet* h, float** rows_dev, int32_t* row_stride);
 nz_status nz_boardnet_forward_rows(nz_boardnet* h, int32_t n, const int32_t* n_dev, float* logits_dev, float* probs_dev,
                                    float* value_dev, void* stream);

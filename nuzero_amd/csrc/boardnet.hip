@@ -941,6 +941,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   // K groups reach past a narrow layer's channels and row tiles past the last row (zero weights, discarded rows): what
   // they read must be numbers, so everything starts as zeros
   for (int i = HDR(clear_from) + tid * 4, end = HDR(lds_floats); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = HDR(clear2_from) + tid * 4, end = HDR(clear2_to); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int i = tid; i < 3 * h_in_cs; i += FUSED_THREADS)     // the input's row of zeros
     lds[h_in_off + (i / h_in_cs) * h_in_ps + zrow_index * h_in_cs + i % h_in_cs] = 0.f;
   // (no barrier here: the input rows written next are none of the floats cleared above; the barrier after them covers both)
@@ -950,13 +951,19 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   {   // this workgroup's input rows, split into pieces (global row of (position n, cell c): ((n >> 4) * hw + c) * 16 + (n & 15))
     const int cs = h_in_cs, ps = h_in_ps;
     const int chunks = in_channels >> 3;                    // eight channels = one 16-byte chunk of a piece
-    for (int i = tid; i < rows * chunks; i += FUSED_THREADS) {
-      const int r = i / chunks, c8 = i - r * chunks;
+    // Every float of the input pieces is written here, not only the live channels of the live rows: a row holds whole
+    // 32-channel K groups (with 16 (mod 32) input channels its last two chunks are read against zero weights), and a
+    // ResNet's trunk buffers 2 and 3 take this space over, rows of a workgroup with fewer positions than the program
+    // was built for included, and read their own rows' padded channels before anyone wrote them.  What is read must
+    // be numbers: zeros.  (zrow_index = the program's row count; the row of zeros itself is made above.)
+    const int row_chunks = cs >> 2;
+    for (int i = tid; i < zrow_index * row_chunks; i += FUSED_THREADS) {
+      const int r = i / row_chunks, c8 = i - r * row_chunks;
       const int pl = r / hw, cell = r - pl * hw, n = p0 + pl;
       const size_t grow = ((size_t)(n >> 4) * hw + cell) * 16 + (n & 15);
       const float* src = in_rows + grow * in_channels + c8 * 8;
-      u32x4 q0, q1, q2;
-      wide_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
+      u32x4 q0 = u32x4{0u, 0u, 0u, 0u}, q1 = q0, q2 = q0;
+      if (r < rows && c8 < chunks) wide_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
       float* d = lds + h_in_off + r * cs + ((c8 ^ ((r >> 2) & 3)) << 2);
       *reinterpret_cast<u32x4*>(d) = q0;
       *reinterpret_cast<u32x4*>(d + ps) = q1;
@@ -1717,6 +1724,11 @@ bool build_fused16_resnet(nz_boardnet* h, int p_max) {
   if (off > budget) return false;
   pg.lds_floats = (int32_t)off;
   pg.clear_from = off_a;
+  // trunk buffers 2 and 3 lie over the input pieces (every float of which the kernel's input loop writes) and reach past
+  // them when the input is narrower than two trunk buffers: that part of LDS is zeroed, so that a layer reading its
+  // source rows' padded channels (coutp = 16 mod 32: the K group's upper half is never stored) reads numbers
+  pg.clear2_from = off_i + (int)std::min(pieces_floats(h->inp), region_i);
+  pg.clear2_to = off_i + (int)region_i;
   pg.n_ops = n_ops;
   pg.hw = h->hw; pg.h = h->rows; pg.wd = h->cols;
   pg.planes = nd.policy_channels; pg.hex = nd.hex ? 1 : 0;
@@ -1949,7 +1961,8 @@ nz_status nz_boardnet_create(nz_boardnet** out, const nz_net_desc* net, int32_t 
 // weights: the reference's state_dict tensors in order (device or host pointers), float32.
 nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, int32_t n_weights,
                                   int32_t recurrent_iterations) {
-  if (!h || !weights) return NZ_ERR_ARG;
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_set_weights: null handle");
+  if (!weights) return bfail(h, NZ_ERR_ARG, "nz_boardnet_set_weights: null weights");
   B_HIP(h, hipSetDevice(h->device));
   B_HIP(h, hipDeviceSynchronize());
   for (auto& c : h->convs) { (void)hipFree(c.dev); if (c.dev_split) (void)hipFree(c.dev_split); if (c.dev16) (void)hipFree(c.dev16); }
@@ -2047,7 +2060,7 @@ nz_status nz_boardnet_wide_stamps(uint64_t* out8) {
 }
 
 nz_status nz_boardnet_fused(nz_boardnet* h, int32_t enable, int32_t* available) {
-  if (!h) return NZ_ERR_ARG;
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_fused: null handle");
   if (enable >= 0) h->use_fused = enable != 0;
   if (available) *available = h->fused_dev != nullptr || h->fused16_dev != nullptr ? 1 : 0;
   return NZ_OK;
@@ -2055,7 +2068,7 @@ nz_status nz_boardnet_fused(nz_boardnet* h, int32_t enable, int32_t* available) 
 
 nz_status nz_boardnet_dims(const nz_boardnet* h, int32_t* in_channels, int32_t* policy_channels, int32_t* rows,
                            int32_t* cols, int32_t* max_batch) {
-  if (!h) return NZ_ERR_ARG;
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_dims: null handle");
   if (in_channels) *in_channels = h->net.in_channels;
   if (policy_channels) *policy_channels = h->net.policy_channels;
   if (rows) *rows = h->rows;
@@ -2066,7 +2079,8 @@ nz_status nz_boardnet_dims(const nz_boardnet* h, int32_t* in_channels, int32_t* 
 
 static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n, const int32_t* n_dev,
                                float* logits_dev, float* probs_dev, float* value_dev, void* stream) {
-  if (!h || !value_dev) return NZ_ERR_ARG;
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_forward: null handle");
+  if (!value_dev) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward: value_dev is NULL");
   if (!h->ready) return bfail(h, NZ_ERR_STATE, "no weights set");
   if (n < 0 || n > h->max_batch) return bfail(h, NZ_ERR_ARG, "batch %d exceeds max_batch %d", n, h->max_batch);
   if (n == 0) return NZ_OK;
@@ -2125,12 +2139,13 @@ static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n
 
 nz_status nz_boardnet_forward(nz_boardnet* h, const float* images_dev, int32_t n, const int32_t* n_dev,
                               float* logits_dev, float* probs_dev, float* value_dev, void* stream) {
-  if (!images_dev) return NZ_ERR_ARG;
+  if (!images_dev) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward: images_dev is NULL");
   return forward_impl(h, images_dev, n, n_dev, logits_dev, probs_dev, value_dev, stream);
 }
 
 nz_status nz_boardnet_input_rows(nz_boardnet* h, float** rows_dev, int32_t* row_stride) {
-  if (!h || !rows_dev || !row_stride) return NZ_ERR_ARG;
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_input_rows: null handle");
+  if (!rows_dev || !row_stride) return bfail(h, NZ_ERR_ARG, "nz_boardnet_input_rows: null argument");
   *rows_dev = h->buffers[0];
   *row_stride = h->inp;
   return NZ_OK;

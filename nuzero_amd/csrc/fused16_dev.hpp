@@ -52,9 +52,10 @@ struct Fused16Op {
 struct Fused16Program {
   int32_t n_ops, hw, h, wd, planes, hex;
   int32_t zrow_index, lds_floats;           // every pieces buffer has a row of zeros at this index (never written)
-  int32_t clear_from, pad2;                 // LDS floats [clear_from, lds_floats) start as zeros: the activation buffers
+  int32_t clear_from, clear2_from;          // LDS floats [clear_from, lds_floats) and [clear2_from, clear2_to) start as zeros:
+                                            // the activation buffers (a K group of 32 channels reaches past a layer's last 16)
   int32_t wbuf_off[2];
-  int32_t in_off, in_cs, in_ps, pol_off, pol_cs, val_off, val_cs, pad;
+  int32_t in_off, in_cs, in_ps, pol_off, pol_cs, val_off, val_cs, clear2_to;
   int32_t zero_at_op, n_zero, zero_off[6], zero_len;   // rows of zeros to (re)make before that layer: buffers that take over a weight buffer's space
   // the per-wavefront-pair program (boardnet_wave_program) only: the layers from solo_at on are two independent chains
   // (the policy head's solo_pol layers, then the value head's) that the pair's two wavefronts run side by side; the first

@@ -9,6 +9,11 @@ inference wrapper of Neural_Networks/Network_Manager.py:46-64.
 All convolutions are 3x3, stride 1, zero 'same' padding, bias-free.  Weights are
 a dict keyed by the reference's ``state_dict`` names, so a reference checkpoint
 (``model_state_dict``) loads unchanged.
+
+Every net takes ``dtype`` (default float32: the reference's own arithmetic, bit for
+bit what the golden vectors pin).  With ``dtype=torch.float64`` the weights, the input
+and every intermediate are float64: the high-precision reference the device kernels
+are held to (tests/test_gpu_boardnet_edges.py).
 """
 import numpy as np
 import torch
@@ -48,8 +53,9 @@ def param_shapes(in_channels, policy_channels, width, num_blocks, recall=True):
 
 class RecurrentNetRef:
     def __init__(self, weights, in_channels, policy_channels, width=64, num_blocks=2,
-                 recall=True, value_activation="tanh"):
-        self.w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in weights.items()}
+                 recall=True, value_activation="tanh", dtype=torch.float32):
+        self.dtype = dtype
+        self.w = {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in weights.items()}
         self.in_channels = in_channels
         self.policy_channels = policy_channels
         self.width = width
@@ -63,7 +69,7 @@ class RecurrentNetRef:
 
     def forward(self, x, iters):
         """RecurrentNet.py:82-99."""
-        x = torch.as_tensor(x, dtype=torch.float32)
+        x = torch.as_tensor(x, dtype=self.dtype)
         thought = F.relu(self._conv(x, "projection.0.weight"))
         base = 1 if self.recall else 0
         for _ in range(iters):
@@ -120,13 +126,14 @@ def _heads(w, trunk, value_activation):
 class FeedForwardRef:
     """ResNet / ConvNet with hex=False (Architectures/ResNet.py:64-70, ConvNet.py:52-57)."""
 
-    def __init__(self, weights, arch, num_blocks, value_activation="tanh"):
-        self.w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in weights.items()}
+    def __init__(self, weights, arch, num_blocks, value_activation="tanh", dtype=torch.float32):
+        self.dtype = dtype
+        self.w = {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in weights.items()}
         self.arch, self.num_blocks, self.value_activation = arch, num_blocks, value_activation
         self.recurrent = False
 
     def forward(self, x):
-        x = torch.as_tensor(x, dtype=torch.float32)
+        x = torch.as_tensor(x, dtype=self.dtype)
         conv = lambda t, name: F.conv2d(t, self.w[name], None, 1, "same")
         if self.arch == "resnet":
             t = F.relu(conv(x, "input_block.0.weight"))
@@ -158,10 +165,10 @@ class FeedForwardRef:
 # adjacency SCS_Game uses (Games/SCS/SCS_Game.py:1199-1243; tests/test_hex_oracle.py checks that much) --
 # with kernel0 [out, in, 3, 1] = (N, centre, S) of the cell's own column and kernel1 [out, in, 2, 2] =
 # [upper, lower] x [left column, right column].
-def hex_conv2d(x, kernel0, kernel1):
-    x = torch.as_tensor(x, dtype=torch.float32)
-    k0 = torch.as_tensor(np.asarray(kernel0), dtype=torch.float32)
-    k1 = torch.as_tensor(np.asarray(kernel1), dtype=torch.float32)
+def hex_conv2d(x, kernel0, kernel1, dtype=torch.float32):
+    x = torch.as_tensor(x, dtype=dtype)
+    k0 = torch.as_tensor(np.asarray(kernel0), dtype=dtype)
+    k1 = torch.as_tensor(np.asarray(kernel1), dtype=dtype)
     n, _, rows, cols = x.shape
     out = F.conv2d(x, k0, None, 1, (1, 0))                           # own column: rows r-1, r, r+1
     xp = F.pad(x, (1, 1, 1, 1))                                      # zero border: xp[r + 1, c + 1] = x[r, c]
@@ -181,16 +188,17 @@ class HexNetRef:
     """RecurrentNet / ResNet / ConvNet with hex=True (every conv a hexagdly.Conv2d(kernel_size=1)); weights keyed
     `<layer>.kernel0` / `<layer>.kernel1` in state_dict order.  Parity unpinned (see above)."""
 
-    def __init__(self, weights, arch, num_blocks, recall=True, value_activation="tanh"):
-        self.w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in weights.items()}
+    def __init__(self, weights, arch, num_blocks, recall=True, value_activation="tanh", dtype=torch.float32):
+        self.dtype = dtype
+        self.w = {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in weights.items()}
         self.arch, self.num_blocks, self.recall, self.value_activation = arch, num_blocks, recall, value_activation
         self.recurrent = arch == "recurrent"
 
     def _conv(self, x, layer):
-        return hex_conv2d(x, self.w[layer + ".kernel0"], self.w[layer + ".kernel1"])
+        return hex_conv2d(x, self.w[layer + ".kernel0"], self.w[layer + ".kernel1"], self.dtype)
 
     def forward(self, x, iters=1):
-        x = torch.as_tensor(x, dtype=torch.float32)
+        x = torch.as_tensor(x, dtype=self.dtype)
         c = self._conv
         if self.arch == "recurrent":
             t = F.relu(c(x, "projection.0"))
