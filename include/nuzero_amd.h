@@ -260,6 +260,15 @@ nz_status nz_engine_net_matrix_flops(const nz_engine* e, double* bf16_flops_host
 #define NZ_NET_JOB_FIELDS 13
 nz_status nz_net_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t* jobs, int32_t max_jobs,
                          int32_t* n_jobs);
+/* The order in which wave `wave` runs jobs in a pass it steals (it runs, stage by stage, its own jobs and then those of
+ * wave `wave` ^ 4, which sits the pass out; host only): one row of NZ_NET_STEAL_FIELDS int32 per job, barrier-only jobs
+ * included -- the list's wave, index in that list, stage, output-cell group (7: no work), K groups, dword offset of
+ * the job's weights, that of the weights the job streams in behind its own (-1: none), destination, destination tile,
+ * 1 if a stage of that list ends with the job, the stage's simulation budget.  *first_w: the weights in the ring when
+ * the pass starts (-1: none). */
+#define NZ_NET_STEAL_FIELDS 11
+nz_status nz_net_steal_order(const nz_net_desc* net, int32_t recurrent_iterations, int32_t wave, int32_t* rows,
+                             int32_t max_rows, int32_t* n_rows, int32_t* first_w);
 /* last conv tap (0..8, row-major over (dy, dx) in -1..1) that reaches output cell `cell` of the 3x3 board; -1: no such cell */
 int32_t nz_net_final_tap(int32_t cell);
 
@@ -292,9 +301,11 @@ nz_status nz_engine_profile_read(nz_engine* e, double* ms_host /*[3]*/, int64_t*
  * [2] share in the network phase, [3] mean / max workgroup lifetime (how evenly
  * the workgroups finish), [4] shader-clock ticks per network phase, [5] per tree
  * phase, [6] ticks of the longest-lived workgroup, [7] workgroups, [8] wave 0's
- * ticks per cycle in end-of-move bookkeeping, [9] in the pending expansion.  Run
- * times of the stamped build are not quoted. */
-nz_status nz_engine_phase_stamps(nz_engine* e, int32_t enable, double* out10_host);
+ * ticks per cycle in end-of-move bookkeeping, [9] simulations of the slowest row per
+ * cycle, [10] network passes per workgroup during which a wave sat out, [11]
+ * simulations per workgroup run under network passes.  Run times of the stamped
+ * build are not quoted. */
+nz_status nz_engine_phase_stamps(nz_engine* e, int32_t enable, double* out12_host);
 
 /* ---- SCS rules as batch operators ------------------------------------------
  * Device-side state transition, legal-move mask and state image of the SCS hex

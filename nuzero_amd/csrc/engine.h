@@ -83,6 +83,9 @@ struct TreeParams {
   int32_t sims_per_cycle;  // persistent kernel: simulations a game may run between two network passes
   int32_t slots_per_wg;    // persistent kernel: game slots a workgroup plays (1..16 of its 16 network rows): fewer slots
                            // than 16 x CUs are spread over all CUs rather than packed into a quarter of them
+  int32_t burst_under_net; // persistent kernel: 1 = a wavefront whose row hit the per-cycle cap sits out the network pass and
+                           // keeps simulating under it while its SIMD partner runs both halves of the tile (selfplay.hip);
+                           // 2 = waves 0-3 sit out every pass (test hook for the partner's merged job order); 0 = off
   int32_t max_cycles;      // persistent kernel: tree/network cycles a workgroup may run before it gives up
                            // (error flag 64) -- a bound every wave reaches, whatever goes wrong
   int32_t* error_flag;
@@ -167,6 +170,14 @@ struct NetProgram {
   int32_t n_jobs[NET_WAVES_HOST];
   int32_t first_w_off[NET_WAVES_HOST];   // w_off of each wave's first weight-reading job, or -1
   NetJob jobs[NET_WAVES_HOST][NET_MAX_JOBS];
+  // A stealing pass (net_dev.hpp net_tile, `steal`): wave w runs, stage by stage, its own jobs and then those of wave
+  // w ^ 4, which sits the pass out.  The weight stream follows that merged order: steal_w_after[l][j][0] is the w_off
+  // of the weight-reading job after job j of list l when l's own wave steals, [1] when l is the stolen list (-1: none);
+  // steal_first_w[w]: the first weight-reading job of w's merged order.
+  int32_t steal_w_after[NET_WAVES_HOST][NET_MAX_JOBS][2];
+  int32_t steal_first_w[NET_WAVES_HOST];
+  int32_t n_stages;
+  int32_t stage_budget[NET_MAX_JOBS];    // simulations a sitting-out wave's row may run before the stage's barrier
 };
 
 void launch_net(const NetProgram* prog_dev, int n_layers, const float* packed_weights,

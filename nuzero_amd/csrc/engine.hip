@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -222,6 +223,7 @@ struct StageConv {
   int dtile = 0;   // destination tile of output tile 0 (dst a buffer): tiles past the fourth go to the strip
 };
 const int og_taps[7] = {49, 13, 12, 12, 12, 26, 23};   // (input cell, tap) pairs per output-cell group (net_dev.hpp og_mask)
+const int BURST_LONG_STAGE = 160;   // add_stage cost units from which a stage counts as long for the burst budget
 const int JOB_OVERHEAD = 12;   // a job's epilogue and start-up beyond its MFMAs, in the cost units of add_stage (32 cycles)
 bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::vector<StageConv>& stage) {
   struct Unit { NetJob job; int cost; };
@@ -328,6 +330,11 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
     }
     pg.jobs[w][pg.n_jobs[w] - 1].flags |= NET_JOB_STAGE_END;
   }
+  // the stage's length in the cost model above (compile_net turns it into the stage's simulation budget)
+  if (pg.n_stages >= NET_MAX_JOBS) return false;
+  int longest = 0;
+  for (int w = 0; w < NET_WAVES_HOST; ++w) longest = std::max(longest, load[w]);
+  pg.stage_budget[pg.n_stages++] = longest;
   return true;
 }
 
@@ -431,6 +438,38 @@ std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::v
       if (pg.jobs[w][j].og != OG_NONE && pg.jobs[w][j].kgroups > 0) next = pg.jobs[w][j].w_off;
     }
     pg.first_w_off[w] = next;
+  }
+  // Simulations a row of a wave that sits the pass out may run under each stage (selfplay.hip burst_under_pass), from
+  // the stage's length in add_stage's cost model: a four-tile stage of two K groups (26 x 6 + 12 = 168 units on its
+  // longest wave) covers two, anything shorter one.
+  {
+    int budget[2] = {2, 1};
+    if (const char* v = getenv("NZ_BURST_BUDGET")) {          // tuning experiments: "long,short"
+      int a = 0, b = 0;
+      if (sscanf(v, "%d,%d", &a, &b) == 2) { budget[0] = std::max(0, a); budget[1] = std::max(0, b); }
+    }
+    for (int s = 0; s < pg.n_stages; ++s) pg.stage_budget[s] = budget[pg.stage_budget[s] >= BURST_LONG_STAGE ? 0 : 1];
+  }
+  // The same chain for a stealing pass: wave p runs, stage by stage, its own jobs and then wave p ^ 4's.
+  for (int p = 0; p < NET_WAVES_HOST; ++p) {
+    const int lists[2] = {p, p ^ (NET_WAVES_HOST / 2)};
+    std::vector<std::pair<int, int>> order;      // (0 own / 1 stolen, job)
+    int at[2] = {0, 0}, stages[2] = {0, 0};
+    while (at[0] < pg.n_jobs[lists[0]] || at[1] < pg.n_jobs[lists[1]])
+      for (int k = 0; k < 2; ++k)
+        while (at[k] < pg.n_jobs[lists[k]]) {
+          order.push_back({k, at[k]});
+          if (pg.jobs[lists[k]][at[k]++].flags & NET_JOB_STAGE_END) { ++stages[k]; break; }
+        }
+    if (stages[0] != pg.n_stages || stages[1] != pg.n_stages) return "job lists disagree on the number of stages";
+    int32_t next = -1;
+    for (size_t i = order.size(); i-- > 0;) {
+      const int k = order[i].first, j = order[i].second;
+      const NetJob& job = pg.jobs[lists[k]][j];
+      pg.steal_w_after[lists[k]][j][k] = next;
+      if (job.og != OG_NONE && job.kgroups > 0) next = job.w_off;
+    }
+    pg.steal_first_w[p] = next;
   }
   return "";
 }
@@ -566,7 +605,7 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
 #undef P
   EngineArrays& d = e->dev;
   if (!d.noise.ensure(G * TTT_ACTIONS) || !d.uniforms.ensure(G * 3) || !d.game_noise.ensure(GTA) ||
-      !d.game_uniforms.ensure(GT * 3) || !d.stamps.ensure((size_t)n_slots * 6) ||      // (one workgroup per slot at most)
+      !d.game_uniforms.ensure(GT * 3) || !d.stamps.ensure((size_t)n_slots * 8) ||      // (one workgroup per slot at most)
       !d.prog.ensure(1))
     return bail(fail(e, NZ_ERR_HIP, "device allocation failed"));
   p.cap = e->cap;
@@ -596,6 +635,14 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   // a workgroup more helps at 100 simulations a move (1024 slots, one box: 6 / 10 / 16 / 32 -> 28.8 / 30.1 / 30.8 / 31.4 k
   // games/s) and hurts at configs[2]'s 400 (12 / 16 / 24 / 32 -> 8.76 / 8.68 / 8.52 / 8.52 k): 16 everywhere
   p.sims_per_cycle = 16;
+  // A wave whose row hit that cap sits out the network pass and goes on simulating under it, while the other wave of its
+  // SIMD runs both waves' jobs (selfplay.hip burst_under_pass; results do not depend on it).  A capped row then no longer
+  // holds the tree phase for all its simulations, so full workgroups take a lower cap: 4096 slots, one box, switch on,
+  // cap 4 / 6 / 8 / 12 / 16 -> 122.7 / 124.3 / 123.7 / 121.8 / 121.3 k games/s beside 120.6-121.0 k without the switch
+  // (profiles/r06_burst_under_net.txt).
+  p.burst_under_net = 1;
+  if (const char* v = getenv("NZ_BURST_UNDER_NET")) p.burst_under_net = std::min(2, std::max(0, atoi(v)));   // tuning experiments
+  if (p.burst_under_net == 1 && p.slots_per_wg == 16) p.sims_per_cycle = 6;
   if (const char* v = getenv("NZ_SIMS_PER_CYCLE")) p.sims_per_cycle = std::max(1, atoi(v));   // tuning experiments
   {   // every cycle finishes at least one simulation or one move of every live row of the workgroup
     const double games_per_slot = std::ceil((double)p.n_games / (double)p.n_slots) + 2.0;
@@ -749,6 +796,52 @@ nz_status nz_net_program(const nz_net_desc* net, int32_t recurrent_iterations, i
   }
   delete pg;
   *n_jobs = n;
+  return NZ_OK;
+}
+
+nz_status nz_net_steal_order(const nz_net_desc* net, int32_t recurrent_iterations, int32_t wave, int32_t* rows,
+                             int32_t max_rows, int32_t* n_rows, int32_t* first_w) {
+  if (!net || !n_rows || !first_w || (!rows && max_rows > 0) || wave < 0 || wave >= NET_WAVES_HOST) return NZ_ERR_ARG;
+  NetLayout L;
+  std::string bad = net_layout(net, recurrent_iterations, L);
+  std::vector<float> packed;
+  std::vector<PackedConv> convs(L.shapes.size());
+  std::unique_ptr<NetProgram> pg(new NetProgram);
+  if (bad.empty()) {
+    for (size_t i = 0; i < L.shapes.size(); ++i) {   // the layout only: zero weights
+      const std::vector<float> zeros((size_t)L.shapes[i].cout * L.shapes[i].cin * 9, 0.f);
+      convs[i] = pack_conv(zeros.data(), L.shapes[i].cout, L.shapes[i].cin, L.cin_main((int)i, net->in_channels), packed);
+    }
+    double flops = 0.0;
+    bad = compile_net(net, L, convs, *pg, flops);
+  }
+  if (!bad.empty()) {
+    g_create_error = bad;
+    return NZ_ERR_ARG;
+  }
+  // the walk of net_tile's job loop with `steal` set: the other list takes over at every stage end of the running one
+  const int lists[2] = {wave, wave ^ (NET_WAVES_HOST / 2)};
+  int at[2] = {0, 0}, side = 0, stage = 0;
+  const int total = pg->n_jobs[lists[0]] + pg->n_jobs[lists[1]];
+  int32_t n = 0;
+  for (int it = 0; it < total && at[side] < pg->n_jobs[lists[side]]; ++it) {
+    const int j = at[side]++;
+    const NetJob& job = pg->jobs[lists[side]][j];
+    const bool end = (job.flags & NET_JOB_STAGE_END) != 0;
+    if (n < max_rows) {
+      const int32_t row[NZ_NET_STEAL_FIELDS] = {lists[side], j, stage, job.og, job.kgroups, job.w_off,
+                                                pg->steal_w_after[lists[side]][j][side], job.dst, job.dtile, end ? 1 : 0,
+                                                pg->stage_budget[stage]};
+      memcpy(rows + (size_t)n * NZ_NET_STEAL_FIELDS, row, sizeof(row));
+    }
+    ++n;
+    if (end) {
+      if (side == 1) ++stage;
+      side ^= 1;
+    }
+  }
+  *n_rows = n;
+  *first_w = pg->steal_first_w[wave];
   return NZ_OK;
 }
 
@@ -1103,7 +1196,7 @@ nz_status nz_engine_phase_stamps(nz_engine* e, int32_t enable, double* out4_host
   if (!e) return NZ_ERR_ARG;
   if (out4_host) {
     const int blocks = selfplay_blocks(e->n_slots, e->tp.slots_per_wg);
-    std::vector<unsigned long long> h((size_t)blocks * 6);
+    std::vector<unsigned long long> h((size_t)blocks * 8);
     NZ_HIP(e, hipSetDevice(e->device));
     NZ_HIP(e, hipDeviceSynchronize());
     NZ_HIP(e, hipMemcpy(h.data(), e->dev.stamps.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1127,7 +1220,14 @@ nz_status nz_engine_phase_stamps(nz_engine* e, int32_t enable, double* out4_host
       exp += (double)h[(size_t)blocks * 4 + b * 2 + 1];
     }
     out4_host[8] = fin / std::max(sum[0], 1.0);      // wave 0: ticks per cycle in end-of-move bookkeeping
-    out4_host[9] = exp / std::max(sum[0], 1.0);      // wave 0: ticks per cycle in the pending expansion
+    out4_host[9] = exp / std::max(sum[0], 1.0);      // simulations of the slowest row per cycle
+    double passes = 0, sims = 0;
+    for (int b = 0; b < blocks; ++b) {
+      passes += (double)h[(size_t)blocks * 6 + b * 2];
+      sims += (double)h[(size_t)blocks * 6 + b * 2 + 1];
+    }
+    out4_host[10] = passes / blocks;                 // network passes with a wave sitting out, per workgroup
+    out4_host[11] = sims / blocks;                   // simulations run under network passes, per workgroup
   }
   e->stamps = enable != 0;
   return NZ_OK;

@@ -728,6 +728,18 @@ __device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float
   run_job_plain<OMASK>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, value, stamp, fetch_next);
 }
 
+// value = tanh(mean over (C=1,H,W)) (blocks.py:82-84); the last stage's jobs left channel 0 of each cell in `vcells`
+// (the program's last stage ends with a barrier).  Cells are added in index order, whichever wave produced them.
+__device__ __forceinline__ void net_value_mean(const float* lds_f, int tid, int n_valid, float* value) {
+  const float* const vcells = lds_f + NET_BUFFERS * ACT_FLOATS + INP_FLOATS;
+  if (tid < POS && tid < n_valid) {
+    float sum = 0.0f;
+#pragma unroll
+    for (int o = 0; o < CELLS; ++o) sum += vcells[o * POS + tid];
+    value[tid] = tanh_fast(sum / 9.0f);
+  }
+}
+
 // Run the compiled network on the 16 positions whose input planes are in `inp`
 // ([cell][pos][4 planes]); `lds_f` holds the activation buffers (NET_BUFFERS * ACT_FLOATS floats,
 // no NaN bit patterns: the callers zero it once), then `inp`'s INP_FLOATS, then VAL_FLOATS of staging, then the
@@ -737,11 +749,16 @@ __device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float
 // (any address space).
 // STAMPS (diagnostic build only): wave 0 adds up the shader-clock ticks it spends in the K
 // loops, the input-plane step, the epilogues and at the stage barriers into stamps[0..3].
+// `steal` (uniform per wave; the persistent kernel only): wave w ^ 4, the other wave of this SIMD, sits the pass out
+// (selfplay.hip burst_under_pass) and this wave runs its jobs too -- stage by stage its own, then the other list's, then the
+// barrier.  The jobs of a stage are independent of each other, and the progressive-epilogue hazard rule holds for the
+// stage as a whole, so which wave runs a job changes nothing it computes.  The weight ring follows the merged order
+// (NetProgram::steal_w_after).
 template <bool STAMPS = false>
 __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, const float* __restrict__ W,
                                          float* __restrict__ lds_f, const float* __restrict__ inp,
                                          int policy_channels, int n_valid, float* logits, float* value,
-                                         unsigned long long* stamps = nullptr) {
+                                         unsigned long long* stamps = nullptr, int steal = 0) {
   unsigned char* __restrict__ lds = reinterpret_cast<unsigned char*>(lds_f);
   float* const vcells = lds_f + NET_BUFFERS * ACT_FLOATS + INP_FLOATS;
   unsigned char* const strip = reinterpret_cast<unsigned char*>(vcells + VAL_FLOATS);
@@ -749,10 +766,10 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
   asm volatile("" : "+v"(tid));                     // per-lane addresses are derived here, not hoisted out of the caller's loop
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const NetJob* __restrict__ jobs = prog->jobs[wave];
+  const NetJob* __restrict__ jobs = prog->jobs[0];
   // (uniform by construction; said explicitly for callers that pass `prog` as a generic pointer)
-  const int n_jobs = __builtin_amdgcn_readfirstlane(prog->n_jobs[wave]);
-  const int first_w = __builtin_amdgcn_readfirstlane(prog->first_w_off[wave]);
+  const int n_jobs = __builtin_amdgcn_readfirstlane(prog->n_jobs[wave] + (steal ? prog->n_jobs[wave ^ (NET_WAVES / 2)] : 0));
+  const int first_w = __builtin_amdgcn_readfirstlane(steal ? prog->steal_first_w[wave] : prog->first_w_off[wave]);
 
   FragS f;
   zero_b(f);
@@ -780,9 +797,15 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
   asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));                  // a zero the compiler must keep in a vector register
   const __attribute__((address_space(1))) uint32_t* jw =
       (const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(jobs) + vzero;   // global, not FLAT
-  uint32_t nw[6];
+  // the merged chain of a stealing pass, read beside the descriptor (one more word, only then)
+  const __attribute__((address_space(1))) uint32_t* sw =
+      (const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(&prog->steal_w_after[0][0][0]) + vzero;
+  // ja: the running job, as an index into jobs[0]; jb: where the other list goes on (steal); side: 1 while it runs
+  int ja = wave * NET_MAX_JOBS, jb = (wave ^ (NET_WAVES / 2)) * NET_MAX_JOBS, side = 0;
+  uint32_t nw[6], nwa = 0u;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) nw[i] = jw[i];
+  for (int i = 0; i < 6; ++i) nw[i] = jw[ja * 6 + i];
+  if (steal) nwa = sw[ja * 2];
   for (int j = 0; j < n_jobs; ++j) {
     NetJob job;
     {
@@ -791,6 +814,19 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       for (int i = 0; i < 6; ++i) cw[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)nw[i]);
       __builtin_memcpy(&job, cw, sizeof(job));
     }
+    int next_w_off = job.next_w_off;
+    bool barrier = (job.flags & NET_JOB_STAGE_END) != 0;
+    if (steal) {
+      next_w_off = __builtin_amdgcn_readfirstlane((int)nwa);
+      if (barrier) {                 // the stage's other list takes over; the barrier comes after the stolen jobs
+        const int t = jb;
+        jb = ja + 1;
+        ja = t - 1;
+        barrier = side != 0;
+        side ^= 1;
+      }
+    }
+    ++ja;
     // Every vector load still in flight here was issued a whole epilogue ago (this job's first three taps): an explicit
     // wait costs nothing and gives the K loop exact counts.  Left to itself the compiler, which cannot count loads across
     // the loop's back edges, makes the first wait inside the job a vmcnt(0) -- behind the taps issued just before it.
@@ -798,12 +834,13 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
     auto fetch_next = [&]() {
       if (j + 1 < n_jobs) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) nw[i] = jw[(j + 1) * 6 + i];
+        for (int i = 0; i < 6; ++i) nw[i] = jw[ja * 6 + i];
+        if (steal) nwa = sw[ja * 2 + side];
       }
     };
     if (job.og == OG_NONE) fetch_next();
     if (job.og != OG_NONE) {
-      const float* w_after = W + (job.next_w_off >= 0 ? job.next_w_off : 0);   // never null: straight-line K loops
+      const float* w_after = W + (next_w_off >= 0 ? next_w_off : 0);   // never null: straight-line K loops
       switch (job.og) {
         // (group 0, all nine cells in one job, is never scheduled: layers are at most four tiles wide and eight waves
         // want a unit each -- engine.hip add_stage)
@@ -816,7 +853,7 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       }
     }
     stamp(2);
-    if (job.flags & NET_JOB_STAGE_END) __syncthreads();
+    if (barrier) __syncthreads();
     stamp(3);
 #ifdef NZ_STAGE_STAMPS   // diagnostic build: per-stage ticks of waves 0 and 4 of workgroup 0 (K loops + planes, epilogue, barrier)
     if constexpr (STAMPS) {
@@ -828,14 +865,7 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
     }
 #endif
   }
-  // value = tanh(mean over (C=1,H,W)) (blocks.py:82-84); the last stage's jobs left channel 0 of each cell in `vcells`
-  // (the program's last stage ends with a barrier).  Cells are added in index order, whichever wave produced them.
-  if (tid < POS && tid < n_valid) {
-    float sum = 0.0f;
-#pragma unroll
-    for (int o = 0; o < CELLS; ++o) sum += vcells[o * POS + tid];
-    value[tid] = tanh_fast(sum / 9.0f);
-  }
+  net_value_mean(lds_f, tid, n_valid, value);
   __syncthreads();
   if constexpr (STAMPS) {
     if (tid == 0)

@@ -19,7 +19,9 @@
 //
 // A game runs at most sims_per_cycle simulations between two network passes: late in a game
 // most simulations end in terminal positions, and one such row would otherwise hold the other
-// fifteen (and the matrix pipes) for dozens of simulations; it simply skips a pass instead.
+// fifteen (and the matrix pipes) for dozens of simulations; it simply skips a pass instead -- and the wave that holds it
+// sits that pass out and goes on simulating under it, while the other wave of its SIMD runs both waves' network jobs
+// (burst_under_pass below; TreeParams.burst_under_net).
 //
 // Randomness.  The reference's draws per move (gamma x n_root_children, two
 // uniforms, at most one more inside np.random.choice; SURVEY.md appendix A rule
@@ -60,6 +62,7 @@ __device__ __forceinline__ int tree_index(int tid) { return tree_slot(tid) * LAN
 // Tree-phase state of one row (game slot); see `park` below.
 struct RowState {
   bool alive = false, pending = false;
+  bool fresh = false;             // pending since a simulation under the last network pass: that pass did not evaluate the leaf
   int g = 0, root = 0, node_count = 1, sims_left = 0, move = 0;
   uint32_t board = 0u;
   int n_sim = 0, n_exp = 0, n_lvl = 0, n_kid = 0;
@@ -73,7 +76,7 @@ constexpr int PARK_ROW_WORDS = 23, PARK_LANE_WORDS = 13;
 __device__ __forceinline__ void park(const RowState& s, const RootCache& rc, int32_t (*row)[POS],
                                      int32_t (*lane)[TREE_THREADS], int slot, int sub, int tid) {
   if (sub == 0) {
-    row[0][slot] = (s.alive ? 1 : 0) | (s.pending ? 2 : 0);
+    row[0][slot] = (s.alive ? 1 : 0) | (s.pending ? 2 : 0) | (s.fresh ? 4 : 0);
     row[1][slot] = s.g; row[2][slot] = s.root; row[3][slot] = s.node_count; row[4][slot] = s.sims_left;
     row[5][slot] = s.move; row[6][slot] = (int32_t)s.board; row[7][slot] = s.n_sim; row[8][slot] = s.n_exp;
     row[9][slot] = s.n_lvl; row[10][slot] = s.n_kid; row[11][slot] = s.path_len; row[12][slot] = s.leaf;
@@ -93,7 +96,7 @@ __device__ __forceinline__ void park(const RowState& s, const RootCache& rc, int
 __device__ __forceinline__ void unpark(RowState& s, RootCache& rc, int32_t (*row)[POS], int32_t (*lane)[TREE_THREADS],
                                        int slot, int sub, int tid) {
   const int f = row[0][slot];
-  s.alive = (f & 1) != 0; s.pending = (f & 2) != 0;
+  s.alive = (f & 1) != 0; s.pending = (f & 2) != 0; s.fresh = (f & 4) != 0;
   s.g = row[1][slot]; s.root = row[2][slot]; s.node_count = row[3][slot]; s.sims_left = row[4][slot];
   s.move = row[5][slot]; s.board = (uint32_t)row[6][slot]; s.n_sim = row[7][slot]; s.n_exp = row[8][slot];
   s.n_lvl = row[9][slot]; s.n_kid = row[10][slot]; s.path_len = row[11][slot]; s.leaf = row[12][slot];
@@ -138,7 +141,7 @@ __device__ __forceinline__ int opaque(int v) {
 // The network phase as a real call: its registers are allocated on their own, as in the stand-alone network kernel
 // (inlined into the persistent loop the allocator spills ~140 registers around the job loop).
 __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W, float* lds, const float* inp,
-                                                    float* out_logits, float* out_value) {
+                                                    float* out_logits, float* out_value, int steal) {
   // arguments of a device function arrive in vector registers; these two are uniform
   auto uniform = [](const void* q) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(q);
@@ -147,7 +150,78 @@ __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W
     return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
   };
   net_tile(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds, inp, 1, POS,
-           out_logits, out_value);
+           out_logits, out_value, nullptr, steal);
+}
+
+// A row that hit the per-cycle cap: it can go on simulating without the network
+__device__ __forceinline__ bool row_capped(const RowState& s) {
+  return s.alive && !s.pending && s.move >= 0 && s.sims_left > 0;
+}
+
+// What a wave that sits the network pass out does instead of net_tile (its SIMD partner, wave ^ 4, runs its jobs:
+// net_tile's `steal`).  It walks its own job list for the stage structure only: at every job that ends a stage its
+// capped rows run up to the stage's budget of simulations -- the tree phase's descent, terminal backup and, at a leaf
+// that needs the network, the hand-over (the row turns pending and stops; `fresh` keeps the next tree phase from
+// expanding it with this pass's outputs, which were computed for an empty column) -- and then the wave executes the
+// barrier net_tile would have executed there; after the last stage the value mean (wave 0's lanes hold it) and the
+// trailing barrier.  The barriers are counted off the same flags words net_tile reads, so the two paths agree by
+// construction.  Moves are finished in the tree phase only.  LDS: the parked state and `tab`; none of the network's areas
+// but out_value.  Returns the simulations this lane's row ran.
+__device__ __forceinline__ int burst_under_pass(int32_t (*park_row)[POS], int32_t (*park_lane)[TREE_THREADS],
+                                                const double2* tab, const float* lds, float* out_value) {
+  const int tid = opaque(threadIdx.x);
+  const int slot = tree_slot(tid), sub = tid & (LANES_PER_GAME - 1);
+  const SelfplayArgs& ka = kernel_args();
+  const TreeParams& p = ka.p;
+  const NetProgram* const prog = ka.prog;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_jobs = __builtin_amdgcn_readfirstlane(prog->n_jobs[wave]);
+  const int gslot = blockIdx.x * p.slots_per_wg + slot;
+  const int tab_n = p.tab_len < LDS_TAB ? p.tab_len : LDS_TAB;
+  const Arena t = arena_of(p, gslot < p.n_slots ? gslot : 0);
+  RowState st;
+  RootCache rc;
+  bool mine = false;
+  if (tree_lane(tid)) {
+    unpark(st, rc, park_row, park_lane, slot, sub, tree_index(tid));
+    mine = row_capped(st);
+  }
+  int done = 0, stage = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const int flags = __builtin_amdgcn_readfirstlane((int)prog->jobs[wave][j].flags);
+    if (!(flags & NET_JOB_STAGE_END)) continue;
+    int budget = __builtin_amdgcn_readfirstlane(prog->stage_budget[stage]);
+    ++stage;
+    while (mine && budget > 0) {
+      const Descent d = descend_cached(p, t, rc, st.root, st.board, sub, st.my_node, st.my_n, st.my_vs, st.win0, tab, tab_n);
+      st.n_lvl += d.levels;
+      st.n_kid += d.children;
+      const int term = ttt_terminal(d.sb);
+      if (term != 0) {
+        if (sub == 0)
+          t[d.node].meta = pack_meta(0u, meta_action(d.lk.y), (uint32_t)ttt_player(d.sb), (uint32_t)term);
+        backup_cached(t, rc, st.my_node, st.my_n, st.my_vs, d.path_len, (double)term_value(term), sub, st.win0);
+        row_memory_fence();
+        --st.sims_left;
+        ++st.n_sim;
+        ++done;
+        --budget;
+        mine = st.sims_left > 0;
+      } else {                    // leaf needs the network: the next pass evaluates it
+        st.pending = st.fresh = true;
+        st.leaf = d.node;
+        st.leaf_meta = d.lk.y;
+        st.leaf_sb = d.sb;
+        st.path_len = d.path_len;
+        mine = false;
+      }
+    }
+    __syncthreads();
+  }
+  net_value_mean(lds, tid, POS, out_value);
+  __syncthreads();
+  if (tree_lane(tid)) park(st, rc, park_row, park_lane, slot, sub, tree_index(tid));
+  return done;
 }
 
 template <bool STAMPS>
@@ -184,11 +258,20 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
       park(st0, rc0, park_row, park_lane, slot, sub, tree_index(tid));
     }
   }
-  unsigned long long t_tree = 0, t_net = 0, n_cycles = 0, t_begin = 0, t0 = 0, t_finish = 0;
+  unsigned long long t_tree = 0, t_net = 0, t_begin = 0, t0 = 0;
+  // (thread 0's other sums wait in LDS: as registers they are live across the network pass, which has none to spare)
+  __shared__ unsigned long long s_diag[3];   // cycles with a pass, ticks in end-of-move bookkeeping, critical simulations
+  if constexpr (STAMPS) {
+    if (threadIdx.x == 0) s_diag[0] = s_diag[1] = s_diag[2] = 0;
+  }
   if constexpr (STAMPS) t_begin = t0 = __builtin_amdgcn_s_memtime();
 
   __shared__ int s_max_sims;
-  unsigned long long crit_sims = 0;
+  __shared__ int s_capped[NET_WAVES];      // per wave: one of its rows hit the per-cycle cap (posted in the tree phase)
+  __shared__ int s_burst_sims, s_burst_passes;   // diagnostic build: simulations run under network passes; passes a wave sat out
+  if constexpr (STAMPS) {
+    if (threadIdx.x == 0) s_burst_sims = s_burst_passes = 0;
+  }
   int cycle = 0;
   for (;;) {
     // ------------------------------ tree phase ---------------------------------
@@ -208,7 +291,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
       if (tid == 0) s_max_sims = 0;
       __syncthreads();
     }
-    bool row_alive = false, row_pending = false;
+    bool row_alive = false, row_pending = false, row_cap = false;
     if (tree_lane(tid)) {                                // lanes 32-63 of every wave only work in the network phase
     RowState st;
     RootCache rc;
@@ -224,7 +307,9 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     uint32_t &leaf_sb = st.leaf_sb, &leaf_meta = st.leaf_meta;
     int& outcome = st.outcome;
     if (alive) {
-      if (pending) {
+      if (pending && st.fresh) {
+        st.fresh = false;            // found under the last pass (burst_under_pass): the coming pass evaluates it
+      } else if (pending) {
         const float logit = sub < 9 ? out_logits[slot * TTT_ACTIONS + sub] : 0.0f;
         const float prob = row_softmax9(logit, sub);
         const double value = (double)out_value[slot];
@@ -280,7 +365,9 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
           term = row_geti(term, 0);
           new_children = row_geti(new_children, 0);
           new_board = (uint32_t)row_geti((int)new_board, 0);
-          if constexpr (STAMPS) t_finish += __builtin_amdgcn_s_memtime() - tf0;
+          if constexpr (STAMPS) {
+            if (tid == 0) s_diag[1] += __builtin_amdgcn_s_memtime() - tf0;
+          }
           if (chosen < 0) { alive = false; break; }        // error flag already raised (whole round fails)
           board = new_board;
           root = new_root;
@@ -355,6 +442,11 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     park(st, rc, park_row, park_lane, slot, sub, tree_index(tid));
     row_alive = alive;
     row_pending = pending;
+    row_cap = row_capped(st);
+    }
+    if (p.burst_under_net != 0) {
+      const int wave_cap = __builtin_amdgcn_ballot_w64(row_cap) != 0ull ? 1 : 0;
+      if ((tid & 63) == 0) s_capped[tid >> 6] = wave_cap;
     }
     const int any_alive = __syncthreads_or(row_alive ? 1 : 0);
     const int any_pending = __syncthreads_or(row_pending ? 1 : 0);
@@ -362,7 +454,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
       const unsigned long long t1 = __builtin_amdgcn_s_memtime();
       t_tree += t1 - t0;
       t0 = t1;
-      crit_sims += (unsigned long long)s_max_sims;
+      if (tid == 0) s_diag[2] += (unsigned long long)s_max_sims;
     }
     if (!any_alive) break;
     if (++cycle > p.max_cycles) {     // uniform over the workgroup: never spin forever
@@ -371,17 +463,41 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     }
     if (!any_pending) continue;       // every live row used up its simulations for this cycle
 
+    // Who sits this pass out: a wave with a capped row, of the two waves of a SIMD (w, w + 4) at most one -- the lower
+    // when both have one; the other runs both halves of the SIMD's tile.  (s_capped is written again only after the
+    // pass's barriers.)  Uniform per wave.
+    int absent = 0, steal = 0;
+    if (p.burst_under_net != 0) {
+      const int w = tid >> 6, lo = w & (NET_WAVES / 2 - 1);
+      const int cap_lo = s_capped[lo], cap_hi = s_capped[lo + NET_WAVES / 2];
+      const int out = p.burst_under_net == 2 ? lo : cap_lo ? lo : cap_hi ? lo + NET_WAVES / 2 : -1;   // 2: the test hook
+      absent = __builtin_amdgcn_readfirstlane(out == w ? 1 : 0);
+      steal = __builtin_amdgcn_readfirstlane(out == (w ^ (NET_WAVES / 2)) ? 1 : 0);
+      if constexpr (STAMPS) {
+        if (tid == 0) {
+          int any = p.burst_under_net == 2 ? 1 : 0;
+          for (int i = 0; i < NET_WAVES; ++i) any |= s_capped[i];
+          s_burst_passes += any;
+        }
+      }
+    }
+
     // ------------------------------ net phase ----------------------------------
-    {
+    if (absent) {
+      const int done = burst_under_pass(park_row, park_lane, tab, lds, out_value);
+      if constexpr (STAMPS) {
+        if (done > 0 && (tid & (LANES_PER_GAME - 1)) == 0) atomicAdd(&s_burst_sims, done);
+      }
+    } else {
       const SelfplayArgs& na = kernel_args();
-      net_phase(na.prog, na.W, lds, inp, out_logits, out_value);
+      net_phase(na.prog, na.W, lds, inp, out_logits, out_value, steal);
     }
     // net_tile ends with a barrier: outputs are visible to every row
     if constexpr (STAMPS) {
       const unsigned long long t1 = __builtin_amdgcn_s_memtime();
       t_net += t1 - t0;
       t0 = t1;
-      ++n_cycles;
+      if (tid == 0) ++s_diag[0];
     }
   }
   const SelfplayArgs& ea = kernel_args();
@@ -391,15 +507,17 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
   const int gslot = blockIdx.x * p.slots_per_wg + slot;
   if constexpr (STAMPS) {
     if (tid == 0) {
-      stamps[blockIdx.x * 4 + 0] = n_cycles;
+      stamps[blockIdx.x * 4 + 0] = s_diag[0];
       stamps[blockIdx.x * 4 + 1] = t_tree;
       stamps[blockIdx.x * 4 + 2] = t_net;
       stamps[blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memtime() - t_begin;
     }
     // wave 0's own time inside move bookkeeping and inside pending expansions (subset of tree ticks)
     if (tid == 0) {
-      stamps[gridDim.x * 4 + blockIdx.x * 2 + 0] = t_finish;
-      stamps[gridDim.x * 4 + blockIdx.x * 2 + 1] = crit_sims;   // sum over cycles of the slowest row's simulations
+      stamps[gridDim.x * 4 + blockIdx.x * 2 + 0] = s_diag[1];
+      stamps[gridDim.x * 4 + blockIdx.x * 2 + 1] = s_diag[2];   // sum over cycles of the slowest row's simulations
+      stamps[gridDim.x * 6 + blockIdx.x * 2 + 0] = (unsigned long long)s_burst_passes;
+      stamps[gridDim.x * 6 + blockIdx.x * 2 + 1] = (unsigned long long)s_burst_sims;
     }
   }
 
