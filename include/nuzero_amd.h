@@ -265,10 +265,22 @@ nz_status nz_net_program(const nz_net_desc* net, int32_t recurrent_iterations, i
  * included -- the list's wave, index in that list, stage, output-cell group (7: no work), K groups, dword offset of
  * the job's weights, that of the weights the job streams in behind its own (-1: none), destination, destination tile,
  * 1 if a stage of that list ends with the job, the stage's simulation budget.  *first_w: the weights in the ring when
- * the pass starts (-1: none). */
+ * the pass starts (-1: none).
+ * This is the CONCATENATED order: what the kernel walks when NZ_BURST_WHOLE_TILE=0 is set, and what the whole-tile jobs
+ * of nz_net_solo_program are made of; it does not depend on that switch. */
 #define NZ_NET_STEAL_FIELDS 11
 nz_status nz_net_steal_order(const nz_net_desc* net, int32_t recurrent_iterations, int32_t wave, int32_t* rows,
                              int32_t max_rows, int32_t* n_rows, int32_t* first_w);
+/* The list wave `wave` actually walks in a pass it steals (host only): the concatenated order above, except that where
+ * the two waves' jobs of a stage are the two cell halves (groups 5 and 6) of one tile of one conv into an activation
+ * buffer -- same weights, K groups, source, first slot, destination, tile, residual, activation and input-plane step
+ * -- ONE job of group 0 (all nine cells) stands for both, unless NZ_BURST_WHOLE_TILE=0 is set in the environment.  One
+ * row of NZ_NET_SOLO_FIELDS int32 per job, barrier-only jobs (group 7) included: the NZ_NET_JOB_FIELDS fields of
+ * nz_net_program (`wave` is the walking wave), then the dword offset of the job's weights, that of the weights it
+ * streams in behind its own (-1: none), and 1 if the workgroup barrier of a stage follows the job.  *first_w as above. */
+#define NZ_NET_SOLO_FIELDS (NZ_NET_JOB_FIELDS + 3)
+nz_status nz_net_solo_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t wave, int32_t* jobs,
+                              int32_t max_jobs, int32_t* n_jobs, int32_t* first_w);
 /* last conv tap (0..8, row-major over (dy, dx) in -1..1) that reaches output cell `cell` of the 3x3 board; -1: no such cell */
 int32_t nz_net_final_tap(int32_t cell);
 

@@ -25,6 +25,7 @@ NZ_LOSS_CE, NZ_LOSS_KLD, NZ_LOSS_MSE = 0, 1, 2
 NZ_LOSS_SE, NZ_LOSS_AE = 0, 1
 NZ_NET_JOB_FIELDS = 13
 NZ_NET_STEAL_FIELDS = 11
+NZ_NET_SOLO_FIELDS = NZ_NET_JOB_FIELDS + 3
 
 
 class SearchCfg(Structure):
@@ -116,6 +117,8 @@ SIGNATURES = {
     "nz_net_program": (c_int32, [POINTER(NetDesc), c_int32, c_void_p, c_int32, POINTER(c_int32)]),
     "nz_net_steal_order": (c_int32, [POINTER(NetDesc), c_int32, c_int32, c_void_p, c_int32, POINTER(c_int32),
                                      POINTER(c_int32)]),
+    "nz_net_solo_program": (c_int32, [POINTER(NetDesc), c_int32, c_int32, c_void_p, c_int32, POINTER(c_int32),
+                                      POINTER(c_int32)]),
     "nz_net_final_tap": (c_int32, [c_int32]),
     "nz_net_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_net_forward_stamps": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(c_double)]),

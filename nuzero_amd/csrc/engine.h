@@ -85,7 +85,7 @@ struct TreeParams {
                            // than 16 x CUs are spread over all CUs rather than packed into a quarter of them
   int32_t burst_under_net; // persistent kernel: 1 = a wavefront whose row hit the per-cycle cap sits out the network pass and
                            // keeps simulating under it while its SIMD partner runs both halves of the tile (selfplay.hip);
-                           // 2 = waves 0-3 sit out every pass (test hook for the partner's merged job order); 0 = off
+                           // 2 = waves 0-3 sit out every pass (test hook for the partner's solo list); 0 = off
   int32_t max_cycles;      // persistent kernel: tree/network cycles a workgroup may run before it gives up
                            // (error flag 64) -- a bound every wave reaches, whatever goes wrong
   int32_t* error_flag;
@@ -160,22 +160,27 @@ __host__ __device__ constexpr int net_final_tap(int o) {
   return 3 * ((o / 3 < 2 ? 1 : 0) + 1) + ((o % 3 < 2 ? 1 : 0) + 1);
 }
 // The groups the kernel has the progressive form for: the late half {4,6,7,8} and the quarters {5,7} {2,6,8}, whose
-// epilogues nothing else on their SIMD covers.  (The early half {0,1,2,3,5} has two early cells and three pairs after
-// them, and its epilogue already runs under the late half's MFMAs; the other quarters have no early cell.)
-__host__ __device__ constexpr bool net_og_progressive(int cells) { return cells == 0x1D0 || cells == 0x0A0 || cells == 0x144; }
+// epilogues nothing else on their SIMD covers, and the whole tile of a solo list, which runs alone on its SIMD.  (The
+// early half {0,1,2,3,5} has two early cells and three pairs after them, and its epilogue already runs under the late
+// half's MFMAs; the other quarters have no early cell.)
+__host__ __device__ constexpr bool net_og_progressive(int cells) {
+  return cells == 0x1D0 || cells == 0x0A0 || cells == 0x144 || cells == 0x1FF;
+}
 constexpr int NET_WAVES_HOST = 8;
 constexpr int NET_MAX_JOBS = 192;
 constexpr int OG_NONE = 7;
+constexpr int NET_MAX_SOLO_JOBS = 2 * NET_MAX_JOBS;   // a solo list: two waves' jobs
 struct NetProgram {
   int32_t n_jobs[NET_WAVES_HOST];
   int32_t first_w_off[NET_WAVES_HOST];   // w_off of each wave's first weight-reading job, or -1
   NetJob jobs[NET_WAVES_HOST][NET_MAX_JOBS];
-  // A stealing pass (net_dev.hpp net_tile, `steal`): wave w runs, stage by stage, its own jobs and then those of wave
-  // w ^ 4, which sits the pass out.  The weight stream follows that merged order: steal_w_after[l][j][0] is the w_off
-  // of the weight-reading job after job j of list l when l's own wave steals, [1] when l is the stolen list (-1: none);
-  // steal_first_w[w]: the first weight-reading job of w's merged order.
-  int32_t steal_w_after[NET_WAVES_HOST][NET_MAX_JOBS][2];
-  int32_t steal_first_w[NET_WAVES_HOST];
+  // A stealing pass (net_dev.hpp net_tile, `steal`): wave w ^ 4 sits the pass out and wave w walks solo_jobs[w] instead of
+  // its own list -- a plain job list in the same format, with its own next_w_off chain and one stage-end flag per stage.
+  // Stage by stage it holds w's jobs and then w ^ 4's; where those are the two cell halves of one tile of one conv into
+  // a buffer, one job of group 0 (all nine cells) replaces them (engine.hip compile_net; NZ_BURST_WHOLE_TILE=0: never).
+  int32_t solo_n_jobs[NET_WAVES_HOST];
+  int32_t solo_first_w[NET_WAVES_HOST];
+  NetJob solo_jobs[NET_WAVES_HOST][NET_MAX_SOLO_JOBS];
   int32_t n_stages;
   int32_t stage_budget[NET_MAX_JOBS];    // simulations a sitting-out wave's row may run before the stage's barrier
 };

@@ -338,6 +338,54 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
   return true;
 }
 
+// The list wave p walks in a pass that wave p ^ 4 sits out (NetProgram::solo_jobs): stage by stage p's jobs and then
+// p ^ 4's, one barrier after both.  Where the two lists' jobs of a stage are the two cell halves (groups 5 and 6) of
+// one tile of one conv into an activation buffer -- the same weights, K groups, source, destination, residual,
+// activation and input-plane step -- and `whole_tile` is set, ONE job of group 0 replaces them: one start-up, one weight
+// stream and one uncovered tail where the two jobs, alone on their SIMD, have two of each.  Per output cell the
+// accumulator sees the same MFMAs in the same order and the epilogue the same steps, so the bits are the same.  The fused
+// job is progressive where the late half was (the hazard rule is the stage's, add_stage).  `list`, `index`: where a job
+// comes from (a fused one: p's half).  false: the two lists do not have pg.n_stages stages each.
+struct SoloJob { NetJob job; int list, index; };
+bool solo_halves_pair(const NetJob& a, const NetJob& b) {
+  return ((a.og == 5 && b.og == 6) || (a.og == 6 && b.og == 5)) && a.w_off == b.w_off && a.wx_off == b.wx_off &&
+         a.kgroups == b.kgroups && a.src == b.src && a.dst == b.dst && a.dtile == b.dtile && a.res == b.res &&
+         a.act == b.act && a.extra == b.extra && a.sslot == b.sslot && a.nt == b.nt &&
+         a.dst >= 0 && a.dst < NET_ACT_BUFFERS && a.sslot != NET_SSLOT_SPLIT;
+}
+bool solo_list(const NetProgram& pg, int p, bool whole_tile, std::vector<SoloJob>& out, int32_t& first_w) {
+  const int lists[2] = {p, p ^ (NET_WAVES_HOST / 2)};
+  int at[2] = {0, 0};
+  out.clear();
+  for (int s = 0; s < pg.n_stages; ++s) {
+    const size_t begin = out.size();
+    for (int k = 0; k < 2; ++k) {
+      bool ended = false;
+      while (!ended && at[k] < pg.n_jobs[lists[k]]) {
+        out.push_back({pg.jobs[lists[k]][at[k]], lists[k], at[k]});
+        ended = (out.back().job.flags & NET_JOB_STAGE_END) != 0;
+        ++at[k];
+      }
+      if (!ended) return false;
+      if (k == 0) out.back().job.flags &= ~NET_JOB_STAGE_END;     // the barrier comes after the other list's jobs
+    }
+    if (whole_tile && out.size() == begin + 2 && solo_halves_pair(out[begin].job, out[begin + 1].job)) {
+      NetJob& j = out[begin].job;
+      j.og = 0;
+      j.flags = (int8_t)(NET_JOB_STAGE_END | ((j.flags | out[begin + 1].job.flags) & NET_JOB_PROGRESSIVE));
+      out.pop_back();
+    }
+  }
+  if (at[0] != pg.n_jobs[lists[0]] || at[1] != pg.n_jobs[lists[1]]) return false;
+  int32_t next = -1;
+  for (size_t i = out.size(); i-- > 0;) {        // prefetch chain, as for the waves' own lists
+    out[i].job.next_w_off = next;
+    if (out[i].job.og != OG_NONE && out[i].job.kgroups > 0) next = out[i].job.w_off;
+  }
+  first_w = next;
+  return true;
+}
+
 // What nz_engine_set_weights derives from the description alone: no device, no weight values.
 struct ConvShape { int cout, cin, k; };
 struct NetLayout {
@@ -450,26 +498,22 @@ std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::v
     }
     for (int s = 0; s < pg.n_stages; ++s) pg.stage_budget[s] = budget[pg.stage_budget[s] >= BURST_LONG_STAGE ? 0 : 1];
   }
-  // The same chain for a stealing pass: wave p runs, stage by stage, its own jobs and then wave p ^ 4's.
+  // The lists of a stealing pass (NetProgram::solo_jobs).  NZ_BURST_WHOLE_TILE=0 (tuning experiments): the pure
+  // concatenation, two half-tile jobs where one whole-tile job would do.
+  bool whole_tile = true;
+  if (const char* v = getenv("NZ_BURST_WHOLE_TILE")) whole_tile = atoi(v) != 0;
   for (int p = 0; p < NET_WAVES_HOST; ++p) {
-    const int lists[2] = {p, p ^ (NET_WAVES_HOST / 2)};
-    std::vector<std::pair<int, int>> order;      // (0 own / 1 stolen, job)
-    int at[2] = {0, 0}, stages[2] = {0, 0};
-    while (at[0] < pg.n_jobs[lists[0]] || at[1] < pg.n_jobs[lists[1]])
-      for (int k = 0; k < 2; ++k)
-        while (at[k] < pg.n_jobs[lists[k]]) {
-          order.push_back({k, at[k]});
-          if (pg.jobs[lists[k]][at[k]++].flags & NET_JOB_STAGE_END) { ++stages[k]; break; }
-        }
-    if (stages[0] != pg.n_stages || stages[1] != pg.n_stages) return "job lists disagree on the number of stages";
-    int32_t next = -1;
-    for (size_t i = order.size(); i-- > 0;) {
-      const int k = order[i].first, j = order[i].second;
-      const NetJob& job = pg.jobs[lists[k]][j];
-      pg.steal_w_after[lists[k]][j][k] = next;
-      if (job.og != OG_NONE && job.kgroups > 0) next = job.w_off;
+    std::vector<SoloJob> solo;
+    if (!solo_list(pg, p, whole_tile, solo, pg.solo_first_w[p]) || solo.size() > (size_t)NET_MAX_SOLO_JOBS)
+      return "job lists disagree on the number of stages";
+    int stage_ends = 0;
+    for (size_t i = 0; i < solo.size(); ++i) {
+      pg.solo_jobs[p][i] = solo[i].job;
+      stage_ends += (solo[i].job.flags & NET_JOB_STAGE_END) ? 1 : 0;
     }
-    pg.steal_first_w[p] = next;
+    // (the sitting-out wave counts the barriers off its own list: selfplay.hip burst_under_pass)
+    if (stage_ends != pg.n_stages) return "job lists disagree on the number of stages";
+    pg.solo_n_jobs[p] = (int32_t)solo.size();
   }
   return "";
 }
@@ -819,29 +863,65 @@ nz_status nz_net_steal_order(const nz_net_desc* net, int32_t recurrent_iteration
     g_create_error = bad;
     return NZ_ERR_ARG;
   }
-  // the walk of net_tile's job loop with `steal` set: the other list takes over at every stage end of the running one
-  const int lists[2] = {wave, wave ^ (NET_WAVES_HOST / 2)};
-  int at[2] = {0, 0}, side = 0, stage = 0;
-  const int total = pg->n_jobs[lists[0]] + pg->n_jobs[lists[1]];
+  // the concatenated order: the solo list without whole-tile jobs, whatever NZ_BURST_WHOLE_TILE says
+  std::vector<SoloJob> solo;
+  int32_t first = -1;
+  if (!solo_list(*pg, wave, false, solo, first)) {
+    g_create_error = "job lists disagree on the number of stages";
+    return NZ_ERR_ARG;
+  }
   int32_t n = 0;
-  for (int it = 0; it < total && at[side] < pg->n_jobs[lists[side]]; ++it) {
-    const int j = at[side]++;
-    const NetJob& job = pg->jobs[lists[side]][j];
-    const bool end = (job.flags & NET_JOB_STAGE_END) != 0;
+  int stage = 0;
+  for (const SoloJob& sj : solo) {
+    const NetJob& job = sj.job;
+    const bool end = (pg->jobs[sj.list][sj.index].flags & NET_JOB_STAGE_END) != 0;     // of the job's own list
     if (n < max_rows) {
-      const int32_t row[NZ_NET_STEAL_FIELDS] = {lists[side], j, stage, job.og, job.kgroups, job.w_off,
-                                                pg->steal_w_after[lists[side]][j][side], job.dst, job.dtile, end ? 1 : 0,
-                                                pg->stage_budget[stage]};
+      const int32_t row[NZ_NET_STEAL_FIELDS] = {sj.list, sj.index, stage, job.og, job.kgroups, job.w_off, job.next_w_off,
+                                                job.dst, job.dtile, end ? 1 : 0, pg->stage_budget[stage]};
       memcpy(rows + (size_t)n * NZ_NET_STEAL_FIELDS, row, sizeof(row));
     }
     ++n;
-    if (end) {
-      if (side == 1) ++stage;
-      side ^= 1;
-    }
+    if (job.flags & NET_JOB_STAGE_END) ++stage;
   }
   *n_rows = n;
-  *first_w = pg->steal_first_w[wave];
+  *first_w = first;
+  return NZ_OK;
+}
+
+nz_status nz_net_solo_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t wave, int32_t* jobs,
+                              int32_t max_jobs, int32_t* n_jobs, int32_t* first_w) {
+  if (!net || !n_jobs || !first_w || (!jobs && max_jobs > 0) || wave < 0 || wave >= NET_WAVES_HOST) return NZ_ERR_ARG;
+  NetLayout L;
+  std::string bad = net_layout(net, recurrent_iterations, L);
+  std::vector<float> packed;
+  std::vector<PackedConv> convs(L.shapes.size());
+  std::unique_ptr<NetProgram> pg(new NetProgram);
+  if (bad.empty()) {
+    for (size_t i = 0; i < L.shapes.size(); ++i) {   // the layout only: zero weights
+      const std::vector<float> zeros((size_t)L.shapes[i].cout * L.shapes[i].cin * 9, 0.f);
+      convs[i] = pack_conv(zeros.data(), L.shapes[i].cout, L.shapes[i].cin, L.cin_main((int)i, net->in_channels), packed);
+    }
+    double flops = 0.0;
+    bad = compile_net(net, L, convs, *pg, flops);
+  }
+  if (!bad.empty()) {
+    g_create_error = bad;
+    return NZ_ERR_ARG;
+  }
+  // the very list net_tile walks: pg->solo_jobs[wave]; barrier-only jobs included
+  int stage = 0;
+  const int32_t n = pg->solo_n_jobs[wave];
+  for (int32_t i = 0; i < n && i < max_jobs; ++i) {
+    const NetJob& job = pg->solo_jobs[wave][i];
+    const int end = (job.flags & NET_JOB_STAGE_END) ? 1 : 0;
+    const int32_t row[NZ_NET_SOLO_FIELDS] = {wave, stage, job.og, og_mask(job.og), job.kgroups, job.sslot, job.src, job.dst,
+                                             job.res, job.act, job.dtile, job.extra,
+                                             (job.flags & NET_JOB_PROGRESSIVE) ? 1 : 0, job.w_off, job.next_w_off, end};
+    memcpy(jobs + (size_t)i * NZ_NET_SOLO_FIELDS, row, sizeof(row));
+    stage += end;
+  }
+  *n_jobs = n;
+  *first_w = pg->solo_first_w[wave];
   return NZ_OK;
 }
 

@@ -179,6 +179,49 @@ struct FragS {            // the wavefront's weight stream, W_RING taps ahead of
   Pieces rb[W_RING];
 };
 
+// A job's activation operands of one K group.  Every group but the whole tile keeps the three pieces of each used input
+// cell in registers for the K group.  The whole-tile job (0x1FF; solo lists only) holds all nine cells and all nine
+// accumulators, and a third resident piece would not fit the register file beside the weight ring: piece 2, which
+// only one of a pair's six MFMAs reads, is fetched from LDS per (input cell, tap) pair instead, LATE_AHEAD pairs ahead
+// into a ring of as many registers -- the same bits from the same address, 49 reads a K group in place of nine.
+constexpr int resident_pieces(int omask) { return omask == 0x1FF ? 2 : 3; }
+constexpr int LATE_AHEAD = 2;
+// the n-th (input cell, tap) pair of the group in issue order, as 9 * tap + cell (-1: past the last)
+constexpr int nth_pair(int omask, int n) {
+  for (int t = 0; t < 9; ++t)
+    for (int c = 0; c < CELLS; ++c) {
+      const int oy = c / 3 - (t / 3 - 1), ox = c % 3 - (t % 3 - 1);
+      if (oy >= 0 && oy < 3 && ox >= 0 && ox < 3 && ((omask >> (oy * 3 + ox)) & 1) && n-- == 0) return 9 * t + c;
+    }
+  return -1;
+}
+template <int OMASK>
+struct Operands {
+  static constexpr int NP = resident_pieces(OMASK), PAIRS = pairs_before(OMASK, 9, 0);
+  Pieces x[CELLS];
+  // NP == 2 only: the ring of piece 2, the source buffer, the slot addresses of this K group and of the job's next
+  u32x4 late[LATE_AHEAD];
+  const unsigned char* src;
+  int cur, nxt;
+  // pairs are counted through the job: pair N of the second K group (PART 2) is PAIRS + N
+  template <int PART>
+  static constexpr int through(int n) { return n + (PART == 2 ? PAIRS : 0); }
+  template <int I, int N, int PART>
+  __device__ __forceinline__ const u32x4& third() const {
+    if constexpr (NP == 3) return x[I].p[2];
+    else return late[through<PART>(N) % LATE_AHEAD];
+  }
+  // piece 2 for pair N of this K group, or (N >= PAIRS, PART 1) for pair N - PAIRS of the next; nothing past the job's end
+  template <int N, int PART>
+  __device__ __forceinline__ void fetch_third() {
+    if constexpr (NP < 3 && (N < PAIRS || PART == 1)) {
+      constexpr int I = nth_pair(OMASK, N % PAIRS) % 9;
+      late[through<PART>(N) % LATE_AHEAD] =
+          *reinterpret_cast<const u32x4*>(src + 2 * PIECE_BYTES + I * (POS * 128) + (N < PAIRS ? cur : nxt));
+    }
+  }
+};
+
 // ---- exact three-way split of float32 into bf16 pieces -------------------------------------------
 __device__ __forceinline__ uint32_t trunc_bf16(float x) { return __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u; }
 // (x0, x1) -> the two upper halves in one register: bf16(x0) | bf16(x1) << 16 (truncating)
@@ -207,18 +250,20 @@ struct NoEpi {
   template <int G>
   __device__ __forceinline__ void slot(const f32x4 (&)[CELLS]) {}
 };
-template <int OMASK, int I, int TAP, typename E>
-__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w, E& e) {
+template <int OMASK, int I, int TAP, int PART, typename E>
+__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, const Pieces& w, E& e) {
   if constexpr (pair_used<OMASK, I, TAP>()) {
     constexpr int o = TapMap<I, TAP>::o;
-    constexpr int g = 6 * pairs_before(OMASK, TAP, I);
+    constexpr int n = pairs_before(OMASK, TAP, I), g = 6 * n;
+    const Pieces (&x)[CELLS] = xs.x;
     // small terms first; one accumulator chain issues at the full rate
     acc[o] = mfma_bf16(w.p[1], x[I].p[1], acc[o]); e.template slot<g + 0>(acc);
-    acc[o] = mfma_bf16(w.p[0], x[I].p[2], acc[o]); e.template slot<g + 1>(acc);
+    acc[o] = mfma_bf16(w.p[0], xs.template third<I, n, PART>(), acc[o]); e.template slot<g + 1>(acc);
     acc[o] = mfma_bf16(w.p[2], x[I].p[0], acc[o]); e.template slot<g + 2>(acc);
     acc[o] = mfma_bf16(w.p[0], x[I].p[1], acc[o]); e.template slot<g + 3>(acc);
     acc[o] = mfma_bf16(w.p[1], x[I].p[0], acc[o]); e.template slot<g + 4>(acc);
     acc[o] = mfma_bf16(w.p[0], x[I].p[0], acc[o]); e.template slot<g + 5>(acc);
+    xs.template fetch_third<n + LATE_AHEAD, PART>();      // (whole-tile job only) into the register this pair just read
     // keep the chain together: the scheduler would interleave it with the other pairs' chains, and
     // round-robin over accumulators issues at 21 cycles per MFMA instead of 16
     // (scripts/microbench/mfma_bf16_rate.hip)
@@ -226,11 +271,11 @@ __device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)
   }
 }
 // all (input cell, TAP) pairs of the job's output cells: independent accumulators
-template <int OMASK, int TAP, typename E>
-__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], const Pieces (&x)[CELLS], const Pieces& w, E& e) {
-  pair_mfma<OMASK, 0, TAP>(acc, x, w, e); pair_mfma<OMASK, 1, TAP>(acc, x, w, e); pair_mfma<OMASK, 2, TAP>(acc, x, w, e);
-  pair_mfma<OMASK, 3, TAP>(acc, x, w, e); pair_mfma<OMASK, 4, TAP>(acc, x, w, e); pair_mfma<OMASK, 5, TAP>(acc, x, w, e);
-  pair_mfma<OMASK, 6, TAP>(acc, x, w, e); pair_mfma<OMASK, 7, TAP>(acc, x, w, e); pair_mfma<OMASK, 8, TAP>(acc, x, w, e);
+template <int OMASK, int TAP, int PART, typename E>
+__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, const Pieces& w, E& e) {
+  pair_mfma<OMASK, 0, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 1, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 2, TAP, PART>(acc, xs, w, e);
+  pair_mfma<OMASK, 3, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 4, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 5, TAP, PART>(acc, xs, w, e);
+  pair_mfma<OMASK, 6, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 7, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 8, TAP, PART>(acc, xs, w, e);
 }
 
 template <int OMASK, int I>
@@ -240,7 +285,7 @@ __device__ __forceinline__ void load_cell(Pieces (&x)[CELLS], const unsigned cha
 #else
   if constexpr (input_used<OMASK, I>()) {
 #pragma unroll
-    for (int piece = 0; piece < 3; ++piece)
+    for (int piece = 0; piece < resident_pieces(OMASK); ++piece)
       x[I].p[piece] = *reinterpret_cast<const u32x4*>(src + piece * PIECE_BYTES + I * (POS * 128) + a0);
   }
 #endif
@@ -323,36 +368,37 @@ __device__ __forceinline__ void refill(Pieces (&x)[CELLS], const unsigned char* 
 // refill_step, some after a tap of the first group, the others before a tap of the second; PART 0: a one-group job.
 // `e`: the epilogue scheduler of the job's LAST K group (PART 0 / 2; NoEpi for PART 1).
 template <int OMASK, int PART, typename E>
-__device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Pieces (&x)[CELLS], FragS& f,
+__device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, FragS& f,
                                        const unsigned char* __restrict__ src, int a1,
                                        const float* __restrict__ wc, const float* __restrict__ wn, int lane, E& e) {
   constexpr bool A = PART == 1, B = PART == 2;
+  Pieces (&x)[CELLS] = xs.x;
   if constexpr (B) refill<OMASK, 9>(x, src, a1);
-  tap_mfma<OMASK, 0>(acc, x, f.rb[0], e); load_tap(f.rb[0], wc + 3 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 0, PART>(acc, xs, f.rb[0], e); load_tap(f.rb[0], wc + 3 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 0>(x, src, a1);
   if constexpr (B) refill<OMASK, 10>(x, src, a1);
-  tap_mfma<OMASK, 1>(acc, x, f.rb[1], e); load_tap(f.rb[1], wc + 4 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 1, PART>(acc, xs, f.rb[1], e); load_tap(f.rb[1], wc + 4 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 1>(x, src, a1);
   if constexpr (B) refill<OMASK, 11>(x, src, a1);
-  tap_mfma<OMASK, 2>(acc, x, f.rb[2], e); load_tap(f.rb[2], wc + 5 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 2, PART>(acc, xs, f.rb[2], e); load_tap(f.rb[2], wc + 5 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 2>(x, src, a1);
   if constexpr (B) refill<OMASK, 12>(x, src, a1);
-  tap_mfma<OMASK, 3>(acc, x, f.rb[0], e); load_tap(f.rb[0], wc + 6 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 3, PART>(acc, xs, f.rb[0], e); load_tap(f.rb[0], wc + 6 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 3>(x, src, a1);
   if constexpr (B) refill<OMASK, 13>(x, src, a1);
-  tap_mfma<OMASK, 4>(acc, x, f.rb[1], e); load_tap(f.rb[1], wc + 7 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 4, PART>(acc, xs, f.rb[1], e); load_tap(f.rb[1], wc + 7 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 4>(x, src, a1);
   if constexpr (B) refill<OMASK, 14>(x, src, a1);
-  tap_mfma<OMASK, 5>(acc, x, f.rb[2], e); load_tap(f.rb[2], wc + 8 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 5, PART>(acc, xs, f.rb[2], e); load_tap(f.rb[2], wc + 8 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 5>(x, src, a1);
   if constexpr (B) refill<OMASK, 15>(x, src, a1);
-  tap_mfma<OMASK, 6>(acc, x, f.rb[0], e); load_tap(f.rb[0], wn + 0 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 6, PART>(acc, xs, f.rb[0], e); load_tap(f.rb[0], wn + 0 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 6>(x, src, a1);
   if constexpr (B) refill<OMASK, 16>(x, src, a1);
-  tap_mfma<OMASK, 7>(acc, x, f.rb[1], e); load_tap(f.rb[1], wn + 1 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 7, PART>(acc, xs, f.rb[1], e); load_tap(f.rb[1], wn + 1 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 7>(x, src, a1);
   if constexpr (B) refill<OMASK, 17>(x, src, a1);
-  tap_mfma<OMASK, 8>(acc, x, f.rb[2], e); load_tap(f.rb[2], wn + 2 * TAP_DWORDS, lane);
+  tap_mfma<OMASK, 8, PART>(acc, xs, f.rb[2], e); load_tap(f.rb[2], wn + 2 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 8>(x, src, a1);
 }
 // All K groups of one job as straight-line code (KG = 1 or 2: layers are at most 64 channels wide;
@@ -365,16 +411,25 @@ __device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragS& f, const u
                                           const unsigned char* __restrict__ strip, int sslot,
                                           const float* __restrict__ w, const float* __restrict__ w_after, int lane, E& e) {
   const int pos = lane & 15, quad = lane >> 4;
-  Pieces x[CELLS];
-  if (KG == 1 && sslot == NET_SSLOT_SPLIT) load_cells_split<OMASK>(x, src, strip, pos, quad);
-  else load_cells<OMASK>(x, src, slot_addr(0, pos, sslot + quad));
+  Operands<OMASK> xs;
+  if (KG == 1 && OMASK != 0x1FF && sslot == NET_SSLOT_SPLIT) load_cells_split<OMASK>(xs.x, src, strip, pos, quad);   // (no whole-tile job reads the strip)
+  else load_cells<OMASK>(xs.x, src, slot_addr(0, pos, sslot + quad));
+  if constexpr (Operands<OMASK>::NP < 3) {                 // piece 2 of the first pairs
+    xs.src = src;
+    xs.cur = slot_addr(0, pos, sslot + quad);
+    xs.nxt = slot_addr(0, pos, sslot + 4 + quad);
+    xs.template fetch_third<0, KG == 2 ? 1 : 0>();
+    xs.template fetch_third<1, KG == 2 ? 1 : 0>();
+    static_assert(LATE_AHEAD == 2, "the pairs fetched before the K loop");
+  }
   if constexpr (KG == 2) {
     const int a1 = slot_addr(0, pos, sslot + 4 + quad);
     NoEpi none;
-    kgroup<OMASK, 1>(acc, x, f, src, a1, w, w + NET_KG_DWORDS, lane, none);
-    kgroup<OMASK, 2>(acc, x, f, src, a1, w + NET_KG_DWORDS, w_after, lane, e);
+    kgroup<OMASK, 1>(acc, xs, f, src, a1, w, w + NET_KG_DWORDS, lane, none);
+    if constexpr (Operands<OMASK>::NP < 3) xs.cur = a1;
+    kgroup<OMASK, 2>(acc, xs, f, src, a1, w + NET_KG_DWORDS, w_after, lane, e);
   } else {
-    kgroup<OMASK, 0>(acc, x, f, src, 0, w, w_after, lane, e);
+    kgroup<OMASK, 0>(acc, xs, f, src, 0, w, w_after, lane, e);
   }
 }
 
@@ -430,6 +485,20 @@ constexpr int early_begin(int omask, int ns, int qi) {
     end = b + ns;
   }
   return b;
+}
+// the whole queue of a group: its early cells and their first slots, worked out once per ProgEpi instantiation
+constexpr int EPI_QUEUE = 5;          // cells final before tap 8: 2, 5, 6, 7, 8
+struct EpiQueue {
+  int n, cell[EPI_QUEUE], begin[EPI_QUEUE];
+};
+constexpr EpiQueue epi_queue(int omask, int ns) {
+  EpiQueue q{};
+  q.n = early_cells(omask);
+  for (int i = 0; i < EPI_QUEUE; ++i) {
+    q.cell[i] = i < q.n ? early_cell(omask, i) : 0;
+    q.begin[i] = i < q.n ? early_begin(omask, ns, i) : 0;
+  }
+  return q;
 }
 // One cell's epilogue is a fixed sequence of steps of a few VALU instructions each, so that the K loop can issue it step
 // by step between its MFMAs (ProgEpi) and the end-of-job form runs the very same steps back to back (epilogue_cell):
@@ -562,13 +631,12 @@ struct ProgEpi {
   static constexpr int NS = epi_steps<ACT, RES>(), NQ = early_cells(OMASK), SLOTS = 6 * pairs_before(OMASK, 9, 0);
   static constexpr int READ_AHEAD = 6;
   static constexpr int LATE = OMASK & 0x01B;          // cells 0, 1, 3, 4: final at tap 8
-  static_assert(NQ >= 1 && NQ <= 3, "groups with early cells");
-  static constexpr int B0 = early_begin(OMASK, NS, 0), B1 = NQ > 1 ? early_begin(OMASK, NS, 1) : 0, B2 = NQ > 2 ? early_begin(OMASK, NS, 2) : 0;
-  static constexpr int C0 = early_cell(OMASK, 0), C1 = early_cell(OMASK, 1), C2 = early_cell(OMASK, 2);
-  static constexpr int FIRST = RES ? B0 - READ_AHEAD : B0;     // the first slot with work: `off` is derived there
+  static_assert(NQ >= 1 && NQ <= EPI_QUEUE, "groups with early cells");
+  static constexpr EpiQueue Q = epi_queue(OMASK, NS);
+  static constexpr int FIRST = RES ? Q.begin[0] - READ_AHEAD : Q.begin[0];     // the first slot with work: `off` is derived there
   static_assert(FIRST >= 0 && FIRST < SLOTS && (!RES || READ_AHEAD <= NS - 8), "reads land inside the K group, behind the residual steps");
-  static constexpr int cell(int qi) { return qi == 0 ? C0 : qi == 1 ? C1 : C2; }
-  static constexpr int begin(int qi) { return qi == 0 ? B0 : qi == 1 ? B1 : B2; }
+  static constexpr int cell(int qi) { return Q.cell[qi]; }
+  static constexpr int begin(int qi) { return Q.begin[qi]; }
   static constexpr int read_slot(int qi) { return begin(qi) - READ_AHEAD; }
 
   EpiRegs s;
@@ -590,10 +658,10 @@ struct ProgEpi {
   }
   template <int G>
   __device__ __forceinline__ void slot(const f32x4 (&acc)[CELLS]) {
-    if constexpr (busy<0, G>() || busy<1, G>() || busy<2, G>()) {
+    if constexpr (busy<0, G>() || busy<1, G>() || busy<2, G>() || busy<3, G>() || busy<4, G>()) {
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (G == FIRST) off = epi_off<false>(lane, nt);
-      slot_of<0, G>(acc); slot_of<1, G>(acc); slot_of<2, G>(acc);
+      slot_of<0, G>(acc); slot_of<1, G>(acc); slot_of<2, G>(acc); slot_of<3, G>(acc); slot_of<4, G>(acc);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -615,13 +683,15 @@ struct ProgEpi {
   }
 };
 
+// (whole-tile jobs, group 0, go to an activation buffer only: engine.hip solo_list)
 template <int OMASK>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob& job, unsigned char* __restrict__ lds,
                                          unsigned char* __restrict__ strip, int lane, int policy_channels, int n_valid,
                                          float* logits, float* vcells) {
-  if (job.dst == NET_DST_STRIP) {             // ReLU only: the host compiles nothing else into the strip
+  constexpr bool BUFFER_ONLY = OMASK == 0x1FF;
+  if (!BUFFER_ONLY && job.dst == NET_DST_STRIP) {             // ReLU only: the host compiles nothing else into the strip
     epilogue_lds<OMASK, 1, false, true>(acc, strip, nullptr, lane, 0);
-  } else if (job.dst < NET_BUFFERS) {
+  } else if (BUFFER_ONLY || job.dst < NET_BUFFERS) {
     unsigned char* dst = lds + job.dst * ACT_BYTES;
     if (job.res >= 0) {
       epilogue_lds<OMASK, 1, true>(acc, dst, lds + job.res * ACT_BYTES, lane, job.dtile);
@@ -750,11 +820,12 @@ __device__ __forceinline__ void net_value_mean(const float* lds_f, int tid, int 
 // STAMPS (diagnostic build only): wave 0 adds up the shader-clock ticks it spends in the K
 // loops, the input-plane step, the epilogues and at the stage barriers into stamps[0..3].
 // `steal` (uniform per wave; the persistent kernel only): wave w ^ 4, the other wave of this SIMD, sits the pass out
-// (selfplay.hip burst_under_pass) and this wave runs its jobs too -- stage by stage its own, then the other list's, then the
-// barrier.  The jobs of a stage are independent of each other, and the progressive-epilogue hazard rule holds for the
-// stage as a whole, so which wave runs a job changes nothing it computes.  The weight ring follows the merged order
-// (NetProgram::steal_w_after).
-template <bool STAMPS = false>
+// (selfplay.hip burst_under_pass) and this wave runs its jobs too: it walks its solo list (NetProgram::solo_jobs) instead
+// of its own -- stage by stage its own jobs, then the other list's, then the barrier, the two halves of a tile as one
+// whole-tile job.  The jobs of a stage are independent of each other, and the progressive-epilogue hazard rule holds for
+// the stage as a whole, so which wave runs a job changes nothing it computes.  The job loop is the same for both lists.
+// SOLO: the caller may steal, so the whole-tile job is compiled in (the stand-alone network kernel does without it).
+template <bool STAMPS = false, bool SOLO = false>
 __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, const float* __restrict__ W,
                                          float* __restrict__ lds_f, const float* __restrict__ inp,
                                          int policy_channels, int n_valid, float* logits, float* value,
@@ -766,10 +837,10 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
   asm volatile("" : "+v"(tid));                     // per-lane addresses are derived here, not hoisted out of the caller's loop
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const NetJob* __restrict__ jobs = prog->jobs[0];
+  const NetJob* __restrict__ jobs = steal ? prog->solo_jobs[wave] : prog->jobs[wave];
   // (uniform by construction; said explicitly for callers that pass `prog` as a generic pointer)
-  const int n_jobs = __builtin_amdgcn_readfirstlane(prog->n_jobs[wave] + (steal ? prog->n_jobs[wave ^ (NET_WAVES / 2)] : 0));
-  const int first_w = __builtin_amdgcn_readfirstlane(steal ? prog->steal_first_w[wave] : prog->first_w_off[wave]);
+  const int n_jobs = __builtin_amdgcn_readfirstlane(steal ? prog->solo_n_jobs[wave] : prog->n_jobs[wave]);
+  const int first_w = __builtin_amdgcn_readfirstlane(steal ? prog->solo_first_w[wave] : prog->first_w_off[wave]);
 
   FragS f;
   zero_b(f);
@@ -797,15 +868,9 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
   asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));                  // a zero the compiler must keep in a vector register
   const __attribute__((address_space(1))) uint32_t* jw =
       (const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(jobs) + vzero;   // global, not FLAT
-  // the merged chain of a stealing pass, read beside the descriptor (one more word, only then)
-  const __attribute__((address_space(1))) uint32_t* sw =
-      (const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(&prog->steal_w_after[0][0][0]) + vzero;
-  // ja: the running job, as an index into jobs[0]; jb: where the other list goes on (steal); side: 1 while it runs
-  int ja = wave * NET_MAX_JOBS, jb = (wave ^ (NET_WAVES / 2)) * NET_MAX_JOBS, side = 0;
-  uint32_t nw[6], nwa = 0u;
+  uint32_t nw[6];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) nw[i] = jw[ja * 6 + i];
-  if (steal) nwa = sw[ja * 2];
+  for (int i = 0; i < 6; ++i) nw[i] = jw[i];
   for (int j = 0; j < n_jobs; ++j) {
     NetJob job;
     {
@@ -814,19 +879,6 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       for (int i = 0; i < 6; ++i) cw[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)nw[i]);
       __builtin_memcpy(&job, cw, sizeof(job));
     }
-    int next_w_off = job.next_w_off;
-    bool barrier = (job.flags & NET_JOB_STAGE_END) != 0;
-    if (steal) {
-      next_w_off = __builtin_amdgcn_readfirstlane((int)nwa);
-      if (barrier) {                 // the stage's other list takes over; the barrier comes after the stolen jobs
-        const int t = jb;
-        jb = ja + 1;
-        ja = t - 1;
-        barrier = side != 0;
-        side ^= 1;
-      }
-    }
-    ++ja;
     // Every vector load still in flight here was issued a whole epilogue ago (this job's first three taps): an explicit
     // wait costs nothing and gives the K loop exact counts.  Left to itself the compiler, which cannot count loads across
     // the loop's back edges, makes the first wait inside the job a vmcnt(0) -- behind the taps issued just before it.
@@ -834,16 +886,16 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
     auto fetch_next = [&]() {
       if (j + 1 < n_jobs) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) nw[i] = jw[ja * 6 + i];
-        if (steal) nwa = sw[ja * 2 + side];
+        for (int i = 0; i < 6; ++i) nw[i] = jw[(j + 1) * 6 + i];
       }
     };
     if (job.og == OG_NONE) fetch_next();
     if (job.og != OG_NONE) {
-      const float* w_after = W + (next_w_off >= 0 ? next_w_off : 0);   // never null: straight-line K loops
+      const float* w_after = W + (job.next_w_off >= 0 ? job.next_w_off : 0);   // never null: straight-line K loops
       switch (job.og) {
-        // (group 0, all nine cells in one job, is never scheduled: layers are at most four tiles wide and eight waves
-        // want a unit each -- engine.hip add_stage)
+        // (group 0, all nine cells in one job, is never dealt to a wave: layers are at most four tiles wide and eight waves
+        // want a unit each -- engine.hip add_stage; a solo list has it where the SIMD's two waves hold a tile's halves)
+        case 0: if constexpr (SOLO) run_job<og_mask(0)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
         case 1: run_job<og_mask(1)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
         case 2: run_job<og_mask(2)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
         case 3: run_job<og_mask(3)>(job, f, W, w_after, lds, strip, inp, lane, policy_channels, n_valid, logits, vcells, stamp, fetch_next); break;
@@ -853,7 +905,7 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
       }
     }
     stamp(2);
-    if (barrier) __syncthreads();
+    if (job.flags & NET_JOB_STAGE_END) __syncthreads();
     stamp(3);
 #ifdef NZ_STAGE_STAMPS   // diagnostic build: per-stage ticks of waves 0 and 4 of workgroup 0 (K loops + planes, epilogue, barrier)
     if constexpr (STAMPS) {

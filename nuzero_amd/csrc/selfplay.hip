@@ -149,8 +149,8 @@ __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
     return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
   };
-  net_tile(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds, inp, 1, POS,
-           out_logits, out_value, nullptr, steal);
+  net_tile<false, true>(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds, inp, 1,
+                        POS, out_logits, out_value, nullptr, steal);       // (true: with the solo lists' whole-tile job)
 }
 
 // A row that hit the per-cycle cap: it can go on simulating without the network
