@@ -41,6 +41,8 @@
 #include "../../include/nuzero_amd.h"
 #include "fused16_dev.hpp"
 #include "boardnet_internal.h"
+#include "hip_own.hpp"
+#include "weight_pack.hpp"
 
 using namespace nz;
 
@@ -1203,12 +1205,60 @@ struct ConvOp {
   int act;
 };
 
-struct PackedConv {
-  float* dev = nullptr;
-  uint32_t* dev_split = nullptr;            // wide layers only (conv_wide_kernel)
-  uint32_t* dev16 = nullptr;                // fused16_net_kernel's stream [col tile][tap][32-ch group][piece][lane][4]
+struct PackedConv {                         // move-only: it owns its streams
+  DevBuf<float> dev;
+  DevBuf<uint32_t> dev_split;               // wide layers only (conv_wide_kernel)
+  DevBuf<uint32_t> dev16;                   // fused16_net_kernel's stream [col tile][tap][32-ch group][piece][lane][4]
   int kg0_32 = 0, kg1_32 = 0;
   int c0p = 0, c1p = 0, coutp = 0, cout = 0, cin = 0;
+};
+
+// the kernel of a <true> / <false> pair for the network's taps (hexagonal / square), by the program it runs
+template <typename Program>
+using net_fn_t = void (*)(const Program*, const float*, int, const int32_t*, int, float*, float*, float*);
+net_fn_t<FusedProgram> net_pick(bool hex, const FusedProgram&);      // (defined below the per-layer launches)
+net_fn_t<Fused16Program> net_pick(bool hex, const Fused16Program&);
+
+// `n` elements of host memory in a device block of their own; false, and empty, when that fails
+template <typename T>
+bool upload(DevBuf<T>* dev, const T* host, size_t n) {
+  if (dev->ensure(n) && hipMemcpy(dev->get(), host, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess) return true;
+  dev->reset();
+  return false;
+}
+
+// A one-launch form: the program in device memory, the kernel that runs it, its grid and its LDS.
+template <typename Program>
+struct OneLaunch {
+  DevBuf<Program> prog;
+  net_fn_t<Program> fn = nullptr;
+  int grid = 0;
+  size_t lds_bytes = 0;
+  bool built() const { return prog.get() != nullptr; }
+  bool set(const Program& pg, bool hex, int grid_, size_t bytes) {
+    fn = net_pick(hex, pg);
+    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (!upload(&prog, &pg, 1)) return false;
+    grid = grid_; lds_bytes = bytes;
+    return true;
+  }
+};
+
+// What set_weights makes, one lifecycle group: emptied as a whole, refilled, and never run on while half there
+// (nz_boardnet::ready is set once it is whole).
+struct Weights {
+  std::vector<PackedConv> convs;
+  std::vector<ConvOp> ops;
+  int64_t flops = 0;
+  OneLaunch<FusedProgram> fused;            // fused_net_kernel, when the activations of a workgroup's share fit in LDS
+  OneLaunch<Fused16Program> fused16;        // the same on the BF16 matrix cores (ConvNet, ResNet), preferred when built
+  DevBuf<Fused16Program> wave_prog;         // one position per wavefront (boardnet_wave_program), built on first request
+  nz::WaveNet wave{};
+  int wave_state = 0;                       // 0 not tried, 1 built, -1 not possible (wave_why)
+  std::string wave_why;
 };
 
 }  // namespace
@@ -1219,25 +1269,12 @@ struct nz_boardnet {
   int rows = 0, cols = 0, hw = 0, max_batch = 0;
   int inp = 0;                              // padded input channels
   int widthp = 0;
-  std::vector<float*> buffers;              // 0: input rows, 1..3: trunk, 4: policy hidden, 5: policy logits, 6,7: value chain
+  std::vector<DevBuf<float>> buffers;       // 0: input rows, 1..3: trunk, 4: policy hidden, 5: policy logits, 6,7: value chain
   std::vector<int> buffer_channels;
-  std::vector<PackedConv> convs;
-  std::vector<ConvOp> ops;
+  Weights w;
   int policy_buf = -1, value_buf = -1;
   bool ready = false;
-  int64_t flops = 0;
-  // one-launch form (fused_net_kernel), built by set_weights when the activations of a workgroup's share fit in LDS
-  FusedProgram* fused_dev = nullptr;
   bool use_fused = true;
-  int fused_grid = 0;
-  size_t fused_lds_bytes = 0;
-  Fused16Program* fused16_dev = nullptr;    // the same on the BF16 matrix cores (ConvNet), preferred when built
-  Fused16Program* wave_dev = nullptr;       // one position per wavefront (boardnet_wave_program), built on first request
-  nz::WaveNet wave{};
-  int wave_state = 0;                       // 0 not tried, 1 built, -1 not possible (wave_why)
-  std::string wave_why;
-  int fused16_grid = 0;
-  size_t fused16_lds_bytes = 0;
   std::string error;
 };
 
@@ -1260,29 +1297,42 @@ nz_status bfail(nz_boardnet* h, nz_status st, const char* fmt, ...) {
 
 int pad16(int c) { return (c + 15) / 16 * 16; }
 
-std::vector<int> head_channels(int width, int out, int layers) {   // blocks.py:56-66,144-153
-  std::vector<int> ch{width};
-  const double step = (double)(out - width) / layers;
-  double prev = width;
-  for (int i = 0; i < layers; ++i) { prev += step; ch.push_back((int)prev); }
-  return ch;
+// algorithmic taps per position of one conv (k = 1 or 3; hexagonal: centre + 6 neighbours): those inside the board only
+int64_t taps_inside(const nz_boardnet* h, int k) {
+  if (!h->net.hex) return k == 1 ? (int64_t)h->hw : (int64_t)(3 * h->rows - 2) * (3 * h->cols - 2);
+  int64_t taps = 0;
+  for (int r = 0; r < h->rows; ++r)
+    for (int c = 0; c < h->cols; ++c) {
+      const int up = (c & 1) ? r : r - 1, lo = up + 1;
+      taps += 1 + (r > 0) + (r + 1 < h->rows);
+      for (int dc = -1; dc <= 1; dc += 2)
+        if (c + dc >= 0 && c + dc < h->cols) taps += (up >= 0 && up < h->rows) + (lo >= 0 && lo < h->rows);
+    }
+  return taps;
 }
 
-// weights [cout][c0 + c1][k][k] (k = 1 or 3) -> the per-lane stream conv_kernel reads.
-// weights -> the per-lane stream conv_kernel reads.  Square: w0 = [cout][c0 + c1][k][k] (k = 1 or 3), w1 unused.
+// weights -> the per-lane streams the kernels read.  Square: w0 = [cout][c0 + c1][k][k] (k = 1 or 3), w1 unused.
 // Hexagonal (hexagdly.Conv2d, kernel_size 1): w0 = kernel0 [cout][cin][3][1] (the cell's own column: N, centre, S),
 // w1 = kernel1 [cout][cin][2][2] ([upper, lower] x [left column, right column]).
+// Every stream is filled on the host through weight() and tensor_index(), then uploaded into its owner: a failure
+// leaves nothing behind.
 bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, int c1, int k, int c0p, int c1p) {
   const bool hex = h->net.hex != 0;
   const int ntaps = hex ? 7 : 9;
   PackedConv pc;
   pc.cout = cout; pc.coutp = pad16(cout); pc.cin = c0 + c1; pc.c0p = c0p; pc.c1p = c1p;
   const int ntiles = pc.coutp / 16, kgt = (c0p + c1p) / 16, cin = c0 + c1;
-  std::vector<float> host((size_t)ntiles * (ntaps + 1) * kgt * 256, 0.f);      // last tap: zeros (see conv_kernel)
   std::vector<float> wh((size_t)cout * cin * (hex ? 3 : k * k)), wh1(hex ? (size_t)cout * cin * 4 : 0);
   if (hipMemcpy(wh.data(), w0, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return false;
   if (hex && hipMemcpy(wh1.data(), w1, wh1.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return false;
-  auto weight = [&](int co, int ci, int tap) -> float {
+  // channel `ch` of the two sources' concat, the first source padded to `p0` channels -> tensor index (-1: padding)
+  auto tensor_index = [&](int ch, int p0) {
+    if (ch < p0) return ch < c0 ? ch : -1;
+    ch -= p0;
+    return ch < c1 ? c0 + ch : -1;
+  };
+  auto weight = [&](int co, int ci, int tap) -> float {        // 0 for a padded output or input channel
+    if (co >= cout || ci < 0) return 0.f;
     if (hex) {
       if (tap < 3) return wh[((size_t)co * cin + ci) * 3 + tap];
       const int side = tap >= 5, lower = (tap - 3) & 1;                      // 3 NW, 4 SW, 5 NE, 6 SE
@@ -1291,112 +1341,59 @@ bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, in
     if (k == 1) return tap == 4 ? wh[(size_t)co * cin + ci] : 0.f;
     return wh[((size_t)co * cin + ci) * 9 + tap];
   };
+  // the word of each piece for the channel pair (ch, ch + 1) of such a concat
+  auto pair = [&](int co, int ch, int p0, int tap, uint32_t word[3]) {
+    split3_pair(weight(co, tensor_index(ch, p0), tap), weight(co, tensor_index(ch + 1, p0), tap), word);
+  };
+  // float32, conv_kernel and fused_net_kernel: [nt][tap (+ 1: zeros, see conv_kernel)][kg][lane][4], the padded concat
+  std::vector<float> host((size_t)ntiles * (ntaps + 1) * kgt * 256, 0.f);
   for (int nt = 0; nt < ntiles; ++nt)
     for (int tap = 0; tap < ntaps; ++tap)
       for (int kg = 0; kg < kgt; ++kg)
         for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 4; ++j) {
-            const int co = nt * 16 + (lane & 15);
-            int ch = kg * 16 + (lane >> 4) * 4 + j;          // channel within the padded concat
-            int cin_idx;
-            if (ch < c0p) cin_idx = ch < c0 ? ch : -1;
-            else { ch -= c0p; cin_idx = ch < c1 ? c0 + ch : -1; }
-            if (co >= cout || cin_idx < 0) continue;
-            host[(((size_t)nt * (ntaps + 1) + tap) * kgt + kg) * 256 + lane * 4 + j] = weight(co, cin_idx, tap);
-          }
-  if (hipMalloc((void**)&pc.dev, host.size() * sizeof(float)) != hipSuccess) return false;
-  if (hipMemcpy(pc.dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return false;
-  if (pc.coutp <= 64) {     // narrow layer: the three-piece bf16 stream of the one-launch BF16 network
+          for (int j = 0; j < 4; ++j)
+            host[(((size_t)nt * (ntaps + 1) + tap) * kgt + kg) * 256 + lane * 4 + j] =
+                weight(nt * 16 + (lane & 15), tensor_index(kg * 16 + (lane >> 4) * 4 + j, c0p), tap);
+  // narrow layer, the three-piece bf16 stream of the one-launch BF16 network and of the per-wavefront form:
+  // [nt][tap][32-channel group][piece][lane][4]; each source is padded to whole 32-channel groups on its own
+  std::vector<uint32_t> sp16;
+  if (pc.coutp <= 64) {
     pc.kg0_32 = (c0p + 31) / 32; pc.kg1_32 = (c1p + 31) / 32;
     const int kg32 = pc.kg0_32 + pc.kg1_32;
-    std::vector<uint32_t> sp((size_t)ntiles * ntaps * kg32 * 3 * 64 * 4, 0u);
-    auto pieces16 = [](float a, uint16_t p3[3]) {                     // a = p3[0] + p3[1] + p3[2], bf16 each (truncating)
-      float r = a;
-      for (int i = 0; i < 3; ++i) {
-        uint32_t bits;
-        memcpy(&bits, &r, 4);
-        bits &= 0xFFFF0000u;
-        p3[i] = (uint16_t)(bits >> 16);
-        float t;
-        memcpy(&t, &bits, 4);
-        r = r - t;
-      }
-    };
-    auto cin16 = [&](int kg, int within) {                            // channel `within` of 32-channel group kg -> tensor index
-      if (kg < pc.kg0_32) { const int ch = kg * 32 + within; return ch < c0 ? ch : -1; }
-      const int ch = (kg - pc.kg0_32) * 32 + within;
-      return ch < c1 ? c0 + ch : -1;
-    };
+    sp16.assign((size_t)ntiles * ntaps * kg32 * 3 * 64 * 4, 0u);
     for (int nt = 0; nt < ntiles; ++nt)
       for (int tap = 0; tap < ntaps; ++tap)
         for (int kg = 0; kg < kg32; ++kg)
           for (int lane = 0; lane < 64; ++lane)
             for (int j = 0; j < 4; ++j) {
-              const int co = nt * 16 + (lane & 15);
-              const int ci0 = cin16(kg, (lane >> 4) * 8 + 2 * j), ci1 = cin16(kg, (lane >> 4) * 8 + 2 * j + 1);
-              uint16_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-              if (co < cout && ci0 >= 0) pieces16(weight(co, ci0, tap), lo);
-              if (co < cout && ci1 >= 0) pieces16(weight(co, ci1, tap), hi);
+              uint32_t word[3];
+              pair(nt * 16 + (lane & 15), kg * 32 + (lane >> 4) * 8 + 2 * j, pc.kg0_32 * 32, tap, word);
               for (int piece = 0; piece < 3; ++piece)
-                sp[(((((size_t)nt * ntaps + tap) * kg32 + kg) * 3 + piece) * 64 + lane) * 4 + j] =
-                    (uint32_t)lo[piece] | ((uint32_t)hi[piece] << 16);
+                sp16[(((((size_t)nt * ntaps + tap) * kg32 + kg) * 3 + piece) * 64 + lane) * 4 + j] = word[piece];
             }
-    if (hipMalloc((void**)&pc.dev16, sp.size() * sizeof(uint32_t)) != hipSuccess) return false;
-    if (hipMemcpy(pc.dev16, sp.data(), sp.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return false;
   }
-  if (pc.coutp % 128 == 0 && c0p % 32 == 0 && c1p % 32 == 0) {      // wide layer: the split form for conv_wide_kernel
+  // wide layer, the split form for conv_wide_kernel: [ct][tap (+ 1)][kq][piece][8 tiles][lane][4], the padded concat
+  std::vector<uint32_t> spw;
+  if (pc.coutp % 128 == 0 && c0p % 32 == 0 && c1p % 32 == 0) {
     const int kqt = (c0p + c1p) / 32, cts = pc.coutp / 128;
-    std::vector<uint32_t> sp((size_t)cts * (ntaps + 1) * kqt * 3 * 8 * 64 * 4, 0u);
-    auto cin_of = [&](int ch) {                                       // channel within the padded concat -> tensor index
-      if (ch < c0p) return ch < c0 ? ch : -1;
-      ch -= c0p;
-      return ch < c1 ? c0 + ch : -1;
-    };
-    auto pieces = [](float a, uint16_t p3[3]) {                       // a = p3[0] + p3[1] + p3[2], bf16 each
-      float r = a;
-      for (int i = 0; i < 3; ++i) {
-        uint32_t bits;
-        memcpy(&bits, &r, 4);
-        bits &= 0xFFFF0000u;
-        p3[i] = (uint16_t)(bits >> 16);
-        float t;
-        memcpy(&t, &bits, 4);
-        r = r - t;
-      }
-    };
+    spw.assign((size_t)cts * (ntaps + 1) * kqt * 3 * 8 * 64 * 4, 0u);
     for (int ct = 0; ct < cts; ++ct)
       for (int tap = 0; tap < ntaps; ++tap)
         for (int kq = 0; kq < kqt; ++kq)
           for (int nt = 0; nt < 8; ++nt)
             for (int lane = 0; lane < 64; ++lane)
               for (int j = 0; j < 4; ++j) {
-                const int co = ct * 128 + nt * 16 + (lane & 15);
-                const int ci0 = cin_of(kq * 32 + (lane >> 4) * 8 + 2 * j), ci1 = cin_of(kq * 32 + (lane >> 4) * 8 + 2 * j + 1);
-                uint16_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-                if (co < cout && ci0 >= 0) pieces(weight(co, ci0, tap), lo);
-                if (co < cout && ci1 >= 0) pieces(weight(co, ci1, tap), hi);
+                uint32_t word[3];
+                pair(ct * 128 + nt * 16 + (lane & 15), kq * 32 + (lane >> 4) * 8 + 2 * j, c0p, tap, word);
                 for (int piece = 0; piece < 3; ++piece)
-                  sp[((((((size_t)ct * (ntaps + 1) + tap) * kqt + kq) * 3 + piece) * 8 + nt) * 64 + lane) * 4 + j] =
-                      (uint32_t)lo[piece] | ((uint32_t)hi[piece] << 16);
+                  spw[((((((size_t)ct * (ntaps + 1) + tap) * kqt + kq) * 3 + piece) * 8 + nt) * 64 + lane) * 4 + j] = word[piece];
               }
-    if (hipMalloc((void**)&pc.dev_split, sp.size() * sizeof(uint32_t)) != hipSuccess) return false;
-    if (hipMemcpy(pc.dev_split, sp.data(), sp.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return false;
   }
-  h->convs.push_back(pc);
-  // algorithmic flops per position: taps inside the board only
-  int64_t taps = 0;
-  if (hex) {
-    for (int r = 0; r < h->rows; ++r)
-      for (int c = 0; c < h->cols; ++c) {
-        const int up = (c & 1) ? r : r - 1, lo = up + 1;
-        taps += 1 + (r > 0) + (r + 1 < h->rows);
-        for (int dc = -1; dc <= 1; dc += 2)
-          if (c + dc >= 0 && c + dc < h->cols) taps += (up >= 0 && up < h->rows) + (lo >= 0 && lo < h->rows);
-      }
-  } else {
-    taps = k == 1 ? (int64_t)h->hw : (int64_t)(3 * h->rows - 2) * (3 * h->cols - 2);
-  }
-  h->flops += 2 * taps * cin * cout;
+  if (!upload(&pc.dev, host.data(), host.size())) return false;
+  if (!sp16.empty() && !upload(&pc.dev16, sp16.data(), sp16.size())) return false;
+  if (!spw.empty() && !upload(&pc.dev_split, spw.data(), spw.size())) return false;
+  h->w.convs.push_back(std::move(pc));
+  h->w.flops += 2 * taps_inside(h, k) * cin * cout;
   return true;
 }
 
@@ -1442,23 +1439,93 @@ void dispatch_conv(const ConvArgs& a, int ntiles, hipStream_t s) {
     else launch_conv<1, 1, 4>(a, ntiles, s);
   }
 }
+
+net_fn_t<FusedProgram> net_pick(bool hex, const FusedProgram&) { return hex ? fused_net_kernel<true> : fused_net_kernel<false>; }
+net_fn_t<Fused16Program> net_pick(bool hex, const Fused16Program&) { return hex ? fused16_net_kernel<true> : fused16_net_kernel<false>; }
 }  // namespace
 
 
 namespace {
+// ---- what the planners of an LDS program share --------------------------------------------------------------------------
+// the two trunk buffers (ids 1..3) nobody needs once the trunk is done: `trunk_out` holds its output
+void free_after_trunk(int trunk_out, int free_ids[2]) {
+  int nf = 0;
+  for (int b = 1; b <= 3; ++b)
+    if (b != trunk_out && nf < 2) free_ids[nf++] = b;
+}
+
+struct Place { int off, cs, ps; };          // a buffer in LDS: float offset, floats per row, floats from piece to piece (0: float32 rows)
+constexpr Place NOWHERE{-1, 0, 0};          // no buffer (a layer without a residual)
+
+// A buffer of bf16 pieces (two per float).  The one-launch kernels keep a buffer's pieces as three planes of rows + 1
+// rows (the last: zeros), so the piece stride is (rows + 1) * cs.  A wavefront keeps them inside the row, as wave_conv of
+// scs_search.hip reads them: [row][32-channel group][piece][16 floats], piece stride 16; rows 256 bytes apart would share
+// their LDS banks, so an even number of groups gets 16 floats of padding per row.
+struct Pieces {
+  int rows;
+  bool in_row;
+  int cs(int channels) const {
+    const int kg = (channels + 31) / 32;
+    return in_row ? kg * 48 + (kg % 2 == 0 ? 16 : 0) : kg * 16;
+  }
+  int ps(int channels) const { return in_row ? 16 : (rows + 1) * cs(channels); }
+  size_t floats(int channels) const { return (size_t)(in_row ? 1 : 3) * (rows + 1) * cs(channels); }
+  Place at(int off, int channels) const { return Place{off, cs(channels), ps(channels)}; }
+};
+
+// the float32 rows of the logits and of the value plane (they take whole 16-channel output tiles: the padded channels
+// of the last tile are stored too)
+struct HeadRows {
+  int pol_cs, val_cs;
+  size_t pol_floats, val_floats;
+  HeadRows(const nz_net_desc& nd, int rows)
+      : pol_cs(pad16(nd.policy_channels) + FUSED_PAD), val_cs(pad16(1) + FUSED_PAD),
+        pol_floats(((size_t)rows * pol_cs + 3) / 4 * 4), val_floats(((size_t)rows * val_cs + 3) / 4 * 4) {}
+};
+
+// buffer id of the per-layer form -> where it lives in a program that keeps the per-layer form's buffers (ResNets, the
+// per-wavefront form): the value chain 6, 7 takes the two trunk buffers free after the trunk (6 after the policy head
+// is done with it), its last layer writes the value plane
+struct Places {
+  Place trunk[4];                           // ids 0 (the input pieces) .. 3
+  Place hidden;                             // id 4, the policy head's hidden layer
+  Place pol, val;
+  int free_ids[2];
+  Place of(int id, bool last_value) const {
+    if (id < 0) return NOWHERE;
+    if (id <= 3) return trunk[id];
+    if (id == 4) return hidden;
+    if (id == 5) return pol;
+    if (last_value) return val;
+    return trunk[free_ids[id == 6 ? 0 : 1]];
+  }
+};
+
+// One layer of a Fused16Program: one source, the dev16 stream read from memory.  A builder that stages weights in LDS
+// says so afterwards (w_lds, w_slot, w_after_barrier).
+void fill_op16(Fused16Op* f, const PackedConv& pc, const ConvOp& op, Place src, Place dst, Place res, int ntaps) {
+  f->w = pc.dev16.get();
+  f->off0 = src.off; f->cs0 = src.cs; f->ps0 = src.ps; f->kg0 = pc.kg0_32;
+  f->off1 = -1; f->cs1 = 0; f->ps1 = 0; f->kg1 = 0;
+  f->offd = dst.off; f->csd = dst.cs; f->psd = dst.ps;
+  f->offr = res.off; f->csr = res.cs; f->psr = res.ps;
+  f->ntiles = pc.coutp / 16; f->act = op.act;
+  f->w_chunks = ntaps * pc.kg0_32 * 3 * 64;
+  f->w_lds = 0; f->w_slot = 0; f->w_after_barrier = 0;
+}
+
 // The one-launch program for fused_net_kernel, when a workgroup's share of the largest batch fits in LDS: the ops of
 // forward_impl with LDS buffers instead of HBM ones.  The value head's two buffers reuse the two trunk buffers that are
 // free once the trunk is done (`trunk_out` holds its output).
 void build_fused(nz_boardnet* h, int trunk_out) {
-  if ((int)h->ops.size() > FUSED_MAX_OPS) return;
+  if ((int)h->w.ops.size() > FUSED_MAX_OPS) return;
   int n_cu = 0;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n_cu <= 0) return;
   const int grid = h->max_batch < n_cu ? h->max_batch : n_cu;
   const int p_max = (h->max_batch + grid - 1) / grid;
   const int rows_max = (p_max * h->hw + 15) / 16 * 16;
-  int free_ids[2], nf = 0;
-  for (int b = 1; b <= 3; ++b)
-    if (b != trunk_out && nf < 2) free_ids[nf++] = b;
+  int free_ids[2];
+  free_after_trunk(trunk_out, free_ids);
   // the heads run after the trunk, policy first: its hidden layer and the value head's two buffers live in the two
   // trunk buffers that are free by then (when they are wide enough); the logits keep their own buffer for the softmax
   int alias[FUSED_BUFFERS] = {0, 1, 2, 3, 4, 5, free_ids[0], free_ids[1]};
@@ -1479,7 +1546,7 @@ void build_fused(nz_boardnet* h, int trunk_out) {
   }
   for (int b = 0; b < FUSED_BUFFERS; ++b)
     if (alias[b] != b) { buf_off[b] = buf_off[alias[b]]; buf_cs[b] = buf_cs[alias[b]]; }
-  const int n_ops = (int)h->ops.size();
+  const int n_ops = (int)h->w.ops.size();
   pg.ops_off = -1;
   if (n_ops <= FUSED_LDS_OPS) { pg.ops_off = (int32_t)off; off += (size_t)n_ops * FUSED_OP_WORDS; off = (off + 3) / 4 * 4; }
   const size_t budget = 156 * 1024 / sizeof(float);      // 160 KB of LDS per CU
@@ -1496,10 +1563,10 @@ void build_fused(nz_boardnet* h, int trunk_out) {
   size_t wbuf = 0;
   int last_input_reader = -1;
   for (int i = 0; i < n_ops; ++i) {
-    const ConvOp& op = h->ops[i];
-    const PackedConv& pc = h->convs[i];
+    const ConvOp& op = h->w.ops[i];
+    const PackedConv& pc = h->w.convs[i];
     FusedOp& f = pg.ops[i];
-    f.w = pc.dev;
+    f.w = pc.dev.get();
     f.off0 = buf_off[op.src0]; f.cs0 = buf_cs[op.src0];
     f.off1 = op.src1 >= 0 ? buf_off[op.src1] : -1; f.cs1 = op.src1 >= 0 ? buf_cs[op.src1] : 0;
     f.offd = buf_off[op.dst]; f.csd = buf_cs[op.dst];
@@ -1540,17 +1607,7 @@ void build_fused(nz_boardnet* h, int trunk_out) {
     if (i < second_from) { slot = 0; f.w_after_barrier = prev_reads ? 1 : 0; }
     f.w_slot = slot;
   }
-  const size_t bytes = off * sizeof(float);
-  const hipError_t e = h->net.hex
-      ? hipFuncSetAttribute((const void*)fused_net_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
-      : hipFuncSetAttribute((const void*)fused_net_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return; }
-  FusedProgram* dev = nullptr;
-  if (hipMalloc((void**)&dev, sizeof(pg)) != hipSuccess) return;
-  if (hipMemcpy(dev, &pg, sizeof(pg), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return; }
-  h->fused_dev = dev;
-  h->fused_grid = grid;
-  h->fused_lds_bytes = bytes;
+  (void)h->w.fused.set(pg, h->net.hex != 0, grid, off * sizeof(float));
 }
 // The one-launch network on the BF16 matrix cores, for ConvNets (a chain: two activation buffers).  LDS, in floats:
 // [zeros][input pieces -- after the first layer: weight buffer 1][weight buffer 0][activations A][activations B]; the
@@ -1560,11 +1617,11 @@ bool build_fused16_for(nz_boardnet* h, int p_max);
 bool build_fused16_resnet(nz_boardnet* h, int p_max);
 void build_fused16(nz_boardnet* h) {
   const nz_net_desc& nd = h->net;
-  if ((nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) || (int)h->ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return;
-  const int n_ops = (int)h->ops.size(), n_trunk = n_ops - 6;     // first layer + num_blocks layers, then 2 + 4 head layers
+  if ((nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) || (int)h->w.ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return;
+  const int n_ops = (int)h->w.ops.size(), n_trunk = n_ops - 6;     // first layer + num_blocks layers, then 2 + 4 head layers
   if (n_trunk < 1) return;
-  for (const PackedConv& pc : h->convs)
-    if (!pc.dev16) return;
+  for (const PackedConv& pc : h->w.convs)
+    if (!pc.dev16.get()) return;
   int n_cu = 0;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n_cu <= 0) return;
   if (const char* e = getenv("NZ_BOARDNET_CUS")) n_cu = std::max(1, std::min(n_cu, atoi(e)));   // a stream with a CU mask: its share of the chip
@@ -1577,12 +1634,11 @@ void build_fused16(nz_boardnet* h) {
 
 bool build_fused16_for(nz_boardnet* h, int p_max) {
   const nz_net_desc& nd = h->net;
-  const int n_ops = (int)h->ops.size(), n_trunk = n_ops - 6;
+  const int n_ops = (int)h->w.ops.size(), n_trunk = n_ops - 6;
   const int grid = (h->max_batch + p_max - 1) / p_max;
   const int rows = p_max * h->hw;                               // rows past the last one are never read or written
   const int ntaps = nd.hex ? 7 : 9;
-  auto cs_of = [](int channels) { return (channels + 31) / 32 * 16; };           // floats per row and piece
-  auto pieces_floats = [&](int channels) { return (size_t)3 * (rows + 1) * cs_of(channels); };   // + the row of zeros
+  const Pieces pieces{rows, false};
   const size_t budget = 160 * 1024 / sizeof(float);
   Fused16Program pg;
   memset(&pg, 0, sizeof(pg));
@@ -1592,26 +1648,23 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
   // trunk weights: every staged layer has the same shape
   size_t wslot = 0;
   for (int i = 1; i < n_trunk; ++i) {
-    const PackedConv& pc = h->convs[i];
+    const PackedConv& pc = h->w.convs[i];
     wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * 3 * 64 * 4);
   }
   if (wslot > (size_t)FUSED16_WREGS * FUSED_THREADS * 4) return false;
-  const size_t in_floats = pieces_floats(h->inp);
+  const size_t in_floats = pieces.floats(h->inp);
   const size_t region_i = std::max(in_floats, wslot);
   const int off_i = (int)off; off += region_i;
   const int off_w0 = (int)off;
   const std::vector<int> pcn = head_channels(W, nd.policy_channels, 2);
   const std::vector<int> vcn = head_channels(W, 1, 4);
   const int hidden = std::max(std::max(pcn[1], vcn[1]), std::max(vcn[2], vcn[3]));
-  // (float32 rows take whole 16-channel output tiles: the padded channels of the last tile are stored too)
-  const int pol_cs = pad16(nd.policy_channels) + FUSED_PAD, val_cs = pad16(1) + FUSED_PAD;
-  const size_t pol_floats = ((size_t)rows * pol_cs + 3) / 4 * 4;
-  const size_t val_floats = ((size_t)rows * val_cs + 3) / 4 * 4;
-  const size_t heads = pol_floats + val_floats + 2 * pieces_floats(hidden);
+  const HeadRows hr(nd, rows);
+  const size_t heads = hr.pol_floats + hr.val_floats + 2 * pieces.floats(hidden);
   const size_t region_w0 = std::max(wslot, heads);
   off += region_w0;
-  const int off_a = (int)off; off += pieces_floats(W);
-  const int off_b = (int)off; off += pieces_floats(W);
+  const int off_a = (int)off; off += pieces.floats(W);
+  const int off_b = (int)off; off += pieces.floats(W);
   off = (off + 3) / 4 * 4;
   if (off > budget) return false;
   pg.lds_floats = (int32_t)off;
@@ -1620,25 +1673,26 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
   pg.n_ops = n_ops;
   pg.hw = h->hw; pg.h = h->rows; pg.wd = h->cols;
   pg.planes = nd.policy_channels; pg.hex = nd.hex ? 1 : 0;
-  pg.in_off = off_i; pg.in_cs = cs_of(h->inp); pg.in_ps = (rows + 1) * pg.in_cs;
+  const Place in_pl = pieces.at(off_i, h->inp);
+  pg.in_off = in_pl.off; pg.in_cs = in_pl.cs; pg.in_ps = in_pl.ps;
   pg.wbuf_off[0] = off_w0; pg.wbuf_off[1] = off_i;
-  pg.pol_off = off_w0; pg.pol_cs = pol_cs;
-  pg.val_off = off_w0 + (int)pol_floats; pg.val_cs = val_cs;
-  const int off_h1 = pg.val_off + (int)val_floats, off_h2 = off_h1 + (int)pieces_floats(hidden);
-  const int cs_w = cs_of(W), ps_w = (rows + 1) * cs_w, cs_h = cs_of(hidden), ps_h = (rows + 1) * cs_h;
-  struct Place { int off, cs, ps; };
+  pg.pol_off = off_w0; pg.pol_cs = hr.pol_cs;
+  pg.val_off = off_w0 + (int)hr.pol_floats; pg.val_cs = hr.val_cs;
+  const int off_h1 = pg.val_off + (int)hr.val_floats, off_h2 = off_h1 + (int)pieces.floats(hidden);
+  const Place a_pl = pieces.at(off_a, W), b_pl = pieces.at(off_b, W);
+  const Place h1_pl = pieces.at(off_h1, hidden), h2_pl = pieces.at(off_h2, hidden);
+  const int cs_h = h1_pl.cs, ps_h = h1_pl.ps;
   pg.zero_at_op = n_trunk; pg.n_zero = 6; pg.zero_len = cs_h;
   for (int piece = 0; piece < 3; ++piece) {
     pg.zero_off[piece] = off_h1 + piece * ps_h + rows * cs_h;
     pg.zero_off[3 + piece] = off_h2 + piece * ps_h + rows * cs_h;
   }
-  const Place in_pl{off_i, pg.in_cs, pg.in_ps}, a_pl{off_a, cs_w, ps_w}, b_pl{off_b, cs_w, ps_w};
-  const Place h1_pl{off_h1, cs_h, ps_h}, h2_pl{off_h2, cs_h, ps_h};
   const Place pol_pl{pg.pol_off, pg.pol_cs, 0}, val_pl{pg.val_off, pg.val_cs, 0};
+  // the trunk goes by layer parity over its two buffers, not by the per-layer form's buffer ids
   const Place trunk_out = (n_trunk - 1) & 1 ? b_pl : a_pl, trunk_other = (n_trunk - 1) & 1 ? a_pl : b_pl;
   for (int i = 0; i < n_ops; ++i) {
-    const ConvOp& op = h->ops[i];
-    const PackedConv& pc = h->convs[i];
+    const ConvOp& op = h->w.ops[i];
+    const PackedConv& pc = h->w.convs[i];
     Fused16Op& f = pg.ops[i];
     if (op.src1 >= 0 || op.res >= 0) return false;                     // a ConvNet has neither
     Place src, dst;
@@ -1656,13 +1710,7 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
         default: src = h1_pl; dst = val_pl; break;
       }
     }
-    f.w = pc.dev16;
-    f.off0 = src.off; f.cs0 = src.cs; f.ps0 = src.ps; f.kg0 = pc.kg0_32;
-    f.off1 = -1; f.cs1 = 0; f.ps1 = 0; f.kg1 = 0;
-    f.offd = dst.off; f.csd = dst.cs; f.psd = dst.ps;
-    f.offr = -1; f.csr = 0; f.psr = 0;
-    f.ntiles = pc.coutp / 16; f.act = op.act;
-    f.w_chunks = ntaps * pc.kg0_32 * 3 * 64;
+    fill_op16(&f, pc, op, src, dst, NOWHERE, ntaps);
     // the K groups a layer reads must exist in its source rows
     if (f.kg0 * 16 > f.cs0) return false;
     const size_t wf = (size_t)f.ntiles * f.w_chunks * 4;
@@ -1671,22 +1719,9 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
     } else if (i >= n_trunk && wf <= region_i && wf <= (size_t)FUSED16_WREGS * FUSED_THREADS * 4) {
       // head layers: buffer 0 is their activations' home, so all of them use buffer 1, written once the layer before is done
       f.w_lds = 1; f.w_slot = 1; f.w_after_barrier = 1;
-    } else {
-      f.w_lds = 0; f.w_slot = 0; f.w_after_barrier = 0;
     }
   }
-  const size_t bytes = off * sizeof(float);
-  const hipError_t e = nd.hex
-      ? hipFuncSetAttribute((const void*)fused16_net_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
-      : hipFuncSetAttribute((const void*)fused16_net_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-  Fused16Program* dev = nullptr;
-  if (hipMalloc((void**)&dev, sizeof(pg)) != hipSuccess) return false;
-  if (hipMemcpy(dev, &pg, sizeof(pg), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return false; }
-  h->fused16_dev = dev;
-  h->fused16_grid = grid;
-  h->fused16_lds_bytes = bytes;
-  return true;
+  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float));
 }
 // The same for ResNets: three trunk buffers (a block reads its input again as the residual).  LDS, in floats:
 // [input pieces -- after the first layer: trunk buffers 2 and 3][the weight buffer][trunk buffer 1][logits][value plane];
@@ -1694,13 +1729,12 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
 // MFMAs all the same).  The head layers use the two trunk buffers that are free by then.
 bool build_fused16_resnet(nz_boardnet* h, int p_max) {
   const nz_net_desc& nd = h->net;
-  const int n_ops = (int)h->ops.size(), n_trunk = n_ops - 6;
+  const int n_ops = (int)h->w.ops.size(), n_trunk = n_ops - 6;
   if (n_trunk < 1) return false;
   const int grid = (h->max_batch + p_max - 1) / p_max;
   const int rows = p_max * h->hw;
   const int ntaps = nd.hex ? 7 : 9;
-  auto cs_of = [](int channels) { return (channels + 31) / 32 * 16; };
-  auto pieces_floats = [&](int channels) { return (size_t)3 * (rows + 1) * cs_of(channels); };
+  const Pieces pieces{rows, false};
   const size_t budget = 160 * 1024 / sizeof(float);
   Fused16Program pg;
   memset(&pg, 0, sizeof(pg));
@@ -1708,89 +1742,61 @@ bool build_fused16_resnet(nz_boardnet* h, int p_max) {
   const int W = nd.width;
   size_t wslot = 0;
   for (int i = 1; i < n_ops; ++i) {
-    const PackedConv& pc = h->convs[i];
+    const PackedConv& pc = h->w.convs[i];
     wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * 3 * 64 * 4);
   }
   if (wslot > (size_t)FUSED16_WREGS * FUSED_THREADS * 4) return false;
   size_t off = 0;
-  const size_t act = pieces_floats(W);
-  const size_t region_i = std::max(pieces_floats(h->inp), 2 * act);
+  const size_t act = pieces.floats(W);
+  const size_t region_i = std::max(pieces.floats(h->inp), 2 * act);
   const int off_i = (int)off; off += region_i;
   const int off_w0 = (int)off; off += wslot;
   const int off_a = (int)off; off += act;
-  const int pol_cs = pad16(nd.policy_channels) + FUSED_PAD, val_cs = pad16(1) + FUSED_PAD;
-  const int off_pol = (int)off; off += ((size_t)rows * pol_cs + 3) / 4 * 4;
-  const int off_val = (int)off; off += ((size_t)rows * val_cs + 3) / 4 * 4;
+  const HeadRows hr(nd, rows);
+  const int off_pol = (int)off; off += hr.pol_floats;
+  const int off_val = (int)off; off += hr.val_floats;
   if (off > budget) return false;
   pg.lds_floats = (int32_t)off;
   pg.clear_from = off_a;
   // trunk buffers 2 and 3 lie over the input pieces (every float of which the kernel's input loop writes) and reach past
   // them when the input is narrower than two trunk buffers: that part of LDS is zeroed, so that a layer reading its
   // source rows' padded channels (coutp = 16 mod 32: the K group's upper half is never stored) reads numbers
-  pg.clear2_from = off_i + (int)std::min(pieces_floats(h->inp), region_i);
+  pg.clear2_from = off_i + (int)std::min(pieces.floats(h->inp), region_i);
   pg.clear2_to = off_i + (int)region_i;
   pg.n_ops = n_ops;
   pg.hw = h->hw; pg.h = h->rows; pg.wd = h->cols;
   pg.planes = nd.policy_channels; pg.hex = nd.hex ? 1 : 0;
-  pg.in_off = off_i; pg.in_cs = cs_of(h->inp); pg.in_ps = (rows + 1) * pg.in_cs;
+  Places pl;
+  pl.trunk[0] = pieces.at(off_i, h->inp);
+  pl.trunk[1] = pieces.at(off_a, W); pl.trunk[2] = pieces.at(off_i, W); pl.trunk[3] = pieces.at(off_i + (int)act, W);
+  pg.in_off = pl.trunk[0].off; pg.in_cs = pl.trunk[0].cs; pg.in_ps = pl.trunk[0].ps;
   pg.wbuf_off[0] = off_w0; pg.wbuf_off[1] = off_w0;
-  pg.pol_off = off_pol; pg.pol_cs = pol_cs;
-  pg.val_off = off_val; pg.val_cs = val_cs;
-  const int cs_w = cs_of(W), ps_w = (rows + 1) * cs_w;
-  struct Place { int off, cs, ps; };
-  const Place in_pl{off_i, pg.in_cs, pg.in_ps};
-  const Place trunk[4] = {in_pl, {off_a, cs_w, ps_w}, {off_i, cs_w, ps_w}, {off_i + (int)act, cs_w, ps_w}};   // buffer ids 0..3
+  pg.pol_off = off_pol; pg.pol_cs = hr.pol_cs;
+  pg.val_off = off_val; pg.val_cs = hr.val_cs;
+  const int cs_w = pl.trunk[1].cs, ps_w = pl.trunk[1].ps;
   // buffers 2 and 3 take over the input's space: their rows of zeros are made when the first layer is done
   pg.zero_at_op = 1; pg.n_zero = 6; pg.zero_len = cs_w;
   for (int piece = 0; piece < 3; ++piece) {
-    pg.zero_off[piece] = trunk[2].off + piece * ps_w + rows * cs_w;
-    pg.zero_off[3 + piece] = trunk[3].off + piece * ps_w + rows * cs_w;
+    pg.zero_off[piece] = pl.trunk[2].off + piece * ps_w + rows * cs_w;
+    pg.zero_off[3 + piece] = pl.trunk[3].off + piece * ps_w + rows * cs_w;
   }
-  const int t_out = h->ops[n_trunk].src0;                        // the trunk's output buffer (what the policy head reads)
+  const int t_out = h->w.ops[n_trunk].src0;                        // the trunk's output buffer (what the policy head reads)
   if (t_out < 1 || t_out > 3) return false;
-  int free_ids[2], nf = 0;
-  for (int b = 1; b <= 3; ++b)
-    if (b != t_out) free_ids[nf++] = b;
-  const Place pol_pl{off_pol, pol_cs, 0}, val_pl{off_val, val_cs, 0};
-  auto place_of = [&](int id, bool last_value) -> Place {         // buffer id of the per-layer form -> where it lives here
-    if (id >= 0 && id <= 3) return trunk[id];
-    if (id == 4) return trunk[free_ids[0]];                       // policy hidden
-    if (id == 5) return pol_pl;
-    if (last_value) return val_pl;
-    return trunk[free_ids[id == 6 ? 0 : 1]];                      // value chain 6, 7 (6 after the policy head is done with it)
-  };
+  free_after_trunk(t_out, pl.free_ids);
+  pl.hidden = pl.trunk[pl.free_ids[0]];
+  pl.pol = Place{off_pol, hr.pol_cs, 0}; pl.val = Place{off_val, hr.val_cs, 0};
   for (int i = 0; i < n_ops; ++i) {
-    const ConvOp& op = h->ops[i];
-    const PackedConv& pc = h->convs[i];
+    const ConvOp& op = h->w.ops[i];
+    const PackedConv& pc = h->w.convs[i];
     Fused16Op& f = pg.ops[i];
-    if (op.src1 >= 0 || !pc.dev16) return false;
-    const Place src = place_of(op.src0, false), dst = place_of(op.dst, i == n_ops - 1);
-    f.w = pc.dev16;
-    f.off0 = src.off; f.cs0 = src.cs; f.ps0 = src.ps; f.kg0 = pc.kg0_32;
-    f.off1 = -1; f.cs1 = 0; f.ps1 = 0; f.kg1 = 0;
-    f.offd = dst.off; f.csd = dst.cs; f.psd = dst.ps;
-    if (op.res >= 0) { const Place r = place_of(op.res, false); f.offr = r.off; f.csr = r.cs; f.psr = r.ps; }
-    else { f.offr = -1; f.csr = 0; f.psr = 0; }
-    f.ntiles = pc.coutp / 16; f.act = op.act;
-    f.w_chunks = ntaps * pc.kg0_32 * 3 * 64;
+    if (op.src1 >= 0 || !pc.dev16.get()) return false;
+    fill_op16(&f, pc, op, pl.of(op.src0, false), pl.of(op.dst, i == n_ops - 1), pl.of(op.res, false), ntaps);
     if (f.kg0 * 16 > f.cs0) return false;
     const size_t wf = (size_t)f.ntiles * f.w_chunks * 4;
     f.w_lds = i >= 1 && wf <= wslot ? 1 : 0;
-    f.w_slot = 0;
     f.w_after_barrier = 1;
   }
-  const size_t bytes = off * sizeof(float);
-  const hipError_t e = nd.hex
-      ? hipFuncSetAttribute((const void*)fused16_net_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
-      : hipFuncSetAttribute((const void*)fused16_net_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-  Fused16Program* dev = nullptr;
-  if (hipMalloc((void**)&dev, sizeof(pg)) != hipSuccess) return false;
-  if (hipMemcpy(dev, &pg, sizeof(pg), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return false; }
-  h->fused16_dev = dev;
-  h->fused16_grid = grid;
-  h->fused16_lds_bytes = bytes;
-  return true;
+  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float));
 }
 }  // namespace
 
@@ -1801,33 +1807,30 @@ bool build_fused16_resnet(nz_boardnet* h, int p_max) {
 // (build_fused16_resnet's arrangement).  The leaf's float32 planes are staged over the trunk buffers before they are
 // split into the input pieces.
 bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* why) {
-  auto no = [&](const char* msg) { h->wave_state = -1; h->wave_why = msg; if (why) *why = msg; return false; };
   if (!h || !h->ready) { if (why) *why = "no weights set"; return false; }
-  if (h->wave_state == 1) { *out = h->wave; return true; }
-  if (h->wave_state == -1) { if (why) *why = h->wave_why; return false; }
+  Weights& g = h->w;
+  auto no = [&](const char* msg) { g.wave_state = -1; g.wave_why = msg; if (why) *why = msg; return false; };
+  if (g.wave_state == 1) { *out = g.wave; return true; }
+  if (g.wave_state == -1) { if (why) *why = g.wave_why; return false; }
   const nz_net_desc& nd = h->net;
   if (nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) return no("only feed-forward nets (ConvNet, ResNet) have a per-wavefront form");
-  const int n_ops = (int)h->ops.size(), n_trunk = n_ops - 6;
+  const int n_ops = (int)g.ops.size(), n_trunk = n_ops - 6;
   if (n_trunk < 1 || n_ops > FUSED_MAX_OPS) return no("too many layers");
   if (h->hw > 32) return no("boards of more than 32 cells do not fit two row tiles");
   if (h->inp % 8 != 0 || h->inp > 128) return no("input planes");
-  for (const PackedConv& pc : h->convs)
-    if (!pc.dev16 || pc.coutp > 64 || pc.kg0_32 > 4) return no("a layer is wider than 64 channels");
-  const int rows = h->hw, R1 = rows + 1;
-  // pieces buffers: [row][32-channel group][piece][16 floats] (scs_search.hip, wave_conv); rows 256 bytes apart would
-  // share their LDS banks, so an even number of groups gets 16 floats of padding per row
-  auto cs_of = [](int channels) { const int kg = (channels + 31) / 32; return kg * 48 + (kg % 2 == 0 ? 16 : 0); };
-  auto pieces_floats = [&](int channels) { return (size_t)R1 * cs_of(channels); };
+  for (const PackedConv& pc : g.convs)
+    if (!pc.dev16.get() || pc.coutp > 64 || pc.kg0_32 > 4) return no("a layer is wider than 64 channels");
+  const int rows = h->hw;
+  const Pieces pieces{rows, true};
   const int W = nd.width;
   if (h->buffer_channels[4] > h->widthp || h->buffer_channels[6] > h->widthp) return no("head layers wider than the trunk");
   Fused16Program pg;
   memset(&pg, 0, sizeof(pg));
-  const int pol_cs = pad16(nd.policy_channels) + FUSED_PAD, val_cs = pad16(1) + FUSED_PAD;
-  const size_t pol_floats = ((size_t)rows * pol_cs + 3) / 4 * 4, val_floats = ((size_t)rows * val_cs + 3) / 4 * 4;
+  const HeadRows hr(nd, rows);
   size_t off = 0;
   const int off_i = 0;
-  off += std::max(pieces_floats(h->inp), pol_floats + val_floats);
-  const size_t act = pieces_floats(W);
+  off += std::max(pieces.floats(h->inp), hr.pol_floats + hr.val_floats);
+  const size_t act = pieces.floats(W);
   const int off_t = (int)off;
   const size_t stage = (size_t)rows * h->inp;
   off += std::max(3 * act, (stage + 3) / 4 * 4);
@@ -1837,68 +1840,48 @@ bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* wh
   pg.n_ops = n_ops;
   pg.hw = h->hw; pg.h = h->rows; pg.wd = h->cols;
   pg.planes = nd.policy_channels; pg.hex = nd.hex ? 1 : 0;
-  pg.in_off = off_i; pg.in_cs = cs_of(h->inp); pg.in_ps = 16;
-  pg.pol_off = off_i; pg.pol_cs = pol_cs;
-  pg.val_off = off_i + (int)pol_floats; pg.val_cs = val_cs;
-  const int cs_w = cs_of(W), ps_w = 16;
-  struct Place { int off, cs, ps; };
-  const Place in_pl{off_i, pg.in_cs, pg.in_ps};
-  const Place trunk[4] = {in_pl, {off_t, cs_w, ps_w}, {off_t + (int)act, cs_w, ps_w}, {off_t + 2 * (int)act, cs_w, ps_w}};
-  const int t_out = h->ops[n_trunk].src0;
+  Places pl;
+  pl.trunk[0] = pieces.at(off_i, h->inp);
+  for (int b = 1; b <= 3; ++b) pl.trunk[b] = pieces.at(off_t + (b - 1) * (int)act, W);
+  pg.in_off = pl.trunk[0].off; pg.in_cs = pl.trunk[0].cs; pg.in_ps = pl.trunk[0].ps;
+  pg.pol_off = off_i; pg.pol_cs = hr.pol_cs;
+  pg.val_off = off_i + (int)hr.pol_floats; pg.val_cs = hr.val_cs;
+  pl.pol = Place{pg.pol_off, hr.pol_cs, 0}; pl.val = Place{pg.val_off, hr.val_cs, 0};
+  const int t_out = g.ops[n_trunk].src0;
   if (t_out < 1 || t_out > 3) return no("internal: trunk output buffer");
+  free_after_trunk(t_out, pl.free_ids);
   // The two heads are independent chains behind the trunk (blocks.py:56-66,144-153): the pair's leader runs the policy
   // head's two layers, its helper the value head's four, side by side with no meeting in between -- if the policy head's
   // hidden buffer (which then cannot share a trunk buffer with the value head's) fits behind the logits' and the value
   // plane's rows in the input pieces' space, free since the first layer.
-  const size_t hid_floats = pieces_floats(h->buffer_channels[4]);
-  const size_t off_hid = (pol_floats + val_floats + 3) / 4 * 4;
-  const bool solo = off_hid + hid_floats <= pieces_floats(h->inp) && getenv("NZ_SCS_PERSIST_NO_SOLO") == nullptr;
-  const int cs_hid = cs_of(h->buffer_channels[4]);
-  int free_ids[2], nf = 0;
-  for (int b = 1; b <= 3; ++b)
-    if (b != t_out) free_ids[nf++] = b;
-  const Place pol_pl{pg.pol_off, pol_cs, 0}, val_pl{pg.val_off, val_cs, 0};
-  auto place_of = [&](int id, bool last_value) -> Place {
-    if (id >= 0 && id <= 3) return trunk[id];
-    if (id == 4) return solo ? Place{off_i + (int)off_hid, cs_hid, 16} : trunk[free_ids[0]];
-    if (id == 5) return pol_pl;
-    if (last_value) return val_pl;
-    return trunk[free_ids[id == 6 ? 0 : 1]];
-  };
+  const size_t hid_floats = pieces.floats(h->buffer_channels[4]);
+  const size_t off_hid = (hr.pol_floats + hr.val_floats + 3) / 4 * 4;
+  const bool solo = off_hid + hid_floats <= pieces.floats(h->inp) && getenv("NZ_SCS_PERSIST_NO_SOLO") == nullptr;
+  const Place hid_pl = pieces.at(off_i + (int)off_hid, h->buffer_channels[4]);
+  pl.hidden = solo ? hid_pl : pl.trunk[pl.free_ids[0]];
   const int ntaps = nd.hex ? 7 : 9;
   for (int i = 0; i < n_ops; ++i) {
-    const ConvOp& op = h->ops[i];
-    const PackedConv& pc = h->convs[i];
+    const ConvOp& op = g.ops[i];
     Fused16Op& f = pg.ops[i];
     if (op.src1 >= 0) return no("a layer with two sources");
     if (i > 0 && (op.src0 == 0 || op.res == 0)) return no("the input is read after the first layer");
-    const Place src = place_of(op.src0, false), dst = place_of(op.dst, i == n_ops - 1);
-    f.w = pc.dev16;
-    f.off0 = src.off; f.cs0 = src.cs; f.ps0 = src.ps; f.kg0 = pc.kg0_32;
-    f.off1 = -1; f.cs1 = 0; f.ps1 = 0; f.kg1 = 0;
-    f.offd = dst.off; f.csd = dst.cs; f.psd = dst.ps;
-    if (op.res >= 0) { const Place r = place_of(op.res, false); f.offr = r.off; f.csr = r.cs; f.psr = r.ps; }
-    else { f.offr = -1; f.csr = 0; f.psr = 0; }
-    f.ntiles = pc.coutp / 16; f.act = op.act;
-    f.w_chunks = ntaps * pc.kg0_32 * 3 * 64;
-    f.w_lds = 0; f.w_slot = 0; f.w_after_barrier = 0;
+    const Place dst = pl.of(op.dst, i == n_ops - 1);
+    fill_op16(&f, g.convs[i], op, pl.of(op.src0, false), dst, pl.of(op.res, false), ntaps);   // weights: never staged
     if (f.kg0 * 48 > f.cs0) return no("internal: K groups beyond the source rows");
     if (dst.ps != 0 && (f.ntiles + 1) / 2 * 48 > dst.cs) return no("internal: output tiles beyond the destination rows");
   }
   pg.solo_at = solo ? n_trunk : n_ops; pg.solo_pol = 2;
-  pg.solo_zero_off = off_i + (int)off_hid + rows * cs_hid; pg.solo_zero_len = solo ? cs_hid : 0;
-  Fused16Program* dev = nullptr;
-  if (hipMalloc((void**)&dev, sizeof(pg)) != hipSuccess) return no("device allocation failed");
-  if (hipMemcpy(dev, &pg, sizeof(pg), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dev); return no("upload failed"); }
-  h->wave_dev = dev;
-  nz::WaveNet& w = h->wave;
-  w.prog = dev; w.lds_floats = pg.lds_floats; w.stage_off = off_t; w.stage_floats = (int32_t)((stage + 3) / 4 * 4);
+  pg.solo_zero_off = hid_pl.off + rows * hid_pl.cs; pg.solo_zero_len = solo ? hid_pl.cs : 0;
+  if (!g.wave_prog.ensure(1)) return no("device allocation failed");
+  if (!upload(&g.wave_prog, &pg, 1)) return no("upload failed");
+  nz::WaveNet& w = g.wave;
+  w.prog = g.wave_prog.get(); w.lds_floats = pg.lds_floats; w.stage_off = off_t; w.stage_floats = (int32_t)((stage + 3) / 4 * 4);
   w.inp = h->inp; w.in_channels = nd.in_channels;
   w.hw = h->hw; w.rows = h->rows; w.cols = h->cols; w.planes = nd.policy_channels; w.hex = nd.hex ? 1 : 0; w.n_ops = n_ops;
-  w.flops = h->flops;
+  w.flops = g.flops;
   w.mfmas = 0;
   for (int i = 0; i < n_ops; ++i) w.mfmas += (int64_t)2 * pg.ops[i].ntiles * ntaps * pg.ops[i].kg0 * 6;
-  h->wave_state = 1;
+  g.wave_state = 1;
   *out = w;
   return true;
 }
@@ -1910,12 +1893,7 @@ const char* nz_boardnet_last_error(const nz_boardnet* h) { return h ? h->error.c
 void nz_boardnet_destroy(nz_boardnet* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  for (float* b : h->buffers) (void)hipFree(b);
-  for (auto& c : h->convs) { (void)hipFree(c.dev); if (c.dev_split) (void)hipFree(c.dev_split); if (c.dev16) (void)hipFree(c.dev16); }
-  if (h->fused_dev) (void)hipFree(h->fused_dev);
-  if (h->fused16_dev) (void)hipFree(h->fused16_dev);
-  if (h->wave_dev) (void)hipFree(h->wave_dev);
+  (void)hipDeviceSynchronize();            // (the owners do not wait for work that still reads them)
   delete h;
 }
 
@@ -1945,32 +1923,21 @@ nz_status nz_boardnet_create(nz_boardnet** out, const nz_net_desc* net, int32_t 
   int vmax = 16;
   for (size_t i = 1; i < vc.size(); ++i) vmax = std::max(vmax, pad16(vc[i]));
   h->buffer_channels = {h->inp, h->widthp, h->widthp, h->widthp, pad16(pc[1]), pad16(pc[2]), vmax, vmax};
-  for (int c : h->buffer_channels) {
-    float* b = nullptr;
+  for (int c : h->buffer_channels) {          // zeroed: padded channels are read before anything writes them
+    DevBuf<float> b;
     const size_t n = (size_t)((max_batch + 15) / 16 * 16) * h->hw * c;
-    if (hipMalloc((void**)&b, n * sizeof(float)) != hipSuccess || hipMemset(b, 0, n * sizeof(float)) != hipSuccess) {
+    if (!b.ensure(n) || hipMemset(b.get(), 0, n * sizeof(float)) != hipSuccess) {
       nz_boardnet_destroy(h);
       return bfail(nullptr, NZ_ERR_HIP, "device allocation failed");
     }
-    h->buffers.push_back(b);
+    h->buffers.push_back(std::move(b));
   }
   *out = h;
   return NZ_OK;
 }
 
-// weights: the reference's state_dict tensors in order (device or host pointers), float32.
-nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, int32_t n_weights,
-                                  int32_t recurrent_iterations) {
-  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_set_weights: null handle");
-  if (!weights) return bfail(h, NZ_ERR_ARG, "nz_boardnet_set_weights: null weights");
-  B_HIP(h, hipSetDevice(h->device));
-  B_HIP(h, hipDeviceSynchronize());
-  for (auto& c : h->convs) { (void)hipFree(c.dev); if (c.dev_split) (void)hipFree(c.dev_split); if (c.dev16) (void)hipFree(c.dev16); }
-  h->convs.clear(); h->ops.clear(); h->flops = 0; h->ready = false;
-  if (h->fused_dev) { (void)hipFree(h->fused_dev); h->fused_dev = nullptr; }
-  if (h->fused16_dev) { (void)hipFree(h->fused16_dev); h->fused16_dev = nullptr; }
-  if (h->wave_dev) { (void)hipFree(h->wave_dev); h->wave_dev = nullptr; }
-  h->wave_state = 0;
+// Fills the (empty) weights group from the reference's tensors: every layer packed, then the one-launch programs.
+static nz_status fill_weights(nz_boardnet* h, const float* const* weights, int32_t n_weights, int32_t recurrent_iterations) {
   const nz_net_desc& nd = h->net;
   const int W = nd.width, Wp = h->widthp, IN = nd.in_channels, INp = h->inp;
   const int vact = nd.value_activation == NZ_ACT_RELU ? 1 : 2;
@@ -1979,15 +1946,14 @@ nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, i
   auto add = [&](int cout, int c0, int c1, int k, int c0p, int c1p, int src0, int src1, int res, int dst, int act) {
     if (wi + per_conv > n_weights) return false;
     if (!pack(h, weights[wi], nd.hex ? weights[wi + 1] : nullptr, cout, c0, c1, k, c0p, c1p)) return false;
-    h->ops.push_back(ConvOp{src0, src1, res, dst, wi, act});
+    h->w.ops.push_back(ConvOp{src0, src1, res, dst, wi, act});
     wi += per_conv;
     return true;
   };
   bool ok = true;
   int cur = 1;                                  // trunk buffer holding the current activations
-  auto block = [&](int w0) {                    // BasicBlock: relu(conv(relu(conv(t))) + t)
+  auto block = [&]() {                          // BasicBlock: relu(conv(relu(conv(t))) + t)
     const int y = cur % 3 + 1, o = y % 3 + 1;
-    (void)w0;
     ok = ok && add(W, W, 0, 3, Wp, 0, cur, -1, -1, y, 1) && add(W, W, 0, 3, Wp, 0, y, -1, cur, o, 1);
     cur = o;
   };
@@ -2004,13 +1970,13 @@ nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, i
         ok = ok && add(W, W, IN, 3, Wp, INp, cur, 0, -1, o, 0);
         cur = o;
       }
-      for (int b = 0; b < nd.num_blocks && ok; ++b) block(wi);
+      for (int b = 0; b < nd.num_blocks && ok; ++b) block();
     }
     wi = first + per_iter * per_conv;
   } else if (nd.arch == NZ_ARCH_RESNET) {
     if (n_weights != (1 + 2 * nd.num_blocks + 6) * per_conv) return bfail(h, NZ_ERR_ARG, "ResNet needs %d tensors, got %d", (1 + 2 * nd.num_blocks + 6) * per_conv, n_weights);
     ok = add(W, IN, 0, 3, INp, 0, 0, -1, -1, 1, 1);
-    for (int b = 0; b < nd.num_blocks && ok; ++b) block(wi);
+    for (int b = 0; b < nd.num_blocks && ok; ++b) block();
   } else {
     if (n_weights != (1 + nd.num_blocks + 6) * per_conv) return bfail(h, NZ_ERR_ARG, "ConvNet needs %d tensors, got %d", (1 + nd.num_blocks + 6) * per_conv, n_weights);
     const int k = nd.kernel_size;
@@ -2037,11 +2003,26 @@ nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, i
   h->policy_buf = 5; h->value_buf = vsrc;
   build_fused(h, cur);
   build_fused16(h);
-  h->ready = true;
   return NZ_OK;
 }
 
-int64_t nz_boardnet_flops(const nz_boardnet* h) { return h ? h->flops : 0; }
+// weights: the reference's state_dict tensors in order (device or host pointers), float32.  On any failure the handle
+// is back to "no weights set", whatever it held before.
+nz_status nz_boardnet_set_weights(nz_boardnet* h, const float* const* weights, int32_t n_weights,
+                                  int32_t recurrent_iterations) {
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_set_weights: null handle");
+  if (!weights) return bfail(h, NZ_ERR_ARG, "nz_boardnet_set_weights: null weights");
+  B_HIP(h, hipSetDevice(h->device));
+  B_HIP(h, hipDeviceSynchronize());          // (the owners do not wait for a forward that still reads them)
+  h->ready = false;
+  h->w = Weights{};
+  const nz_status st = fill_weights(h, weights, n_weights, recurrent_iterations);
+  if (st != NZ_OK) h->w = Weights{};
+  h->ready = st == NZ_OK;
+  return st;
+}
+
+int64_t nz_boardnet_flops(const nz_boardnet* h) { return h ? h->w.flops : 0; }
 
 // Diagnostic (-DNZ_WIDE_STAMPS builds only; NZ_ERR_STATE otherwise): conv_wide_kernel's phase ticks summed over its launches
 // so far: [0] loads issued, [1] first fragments, [2] MFMAs + staging, [3] barrier, [4] loop overhead, [5] K steps, [6] launches.
@@ -2062,7 +2043,7 @@ nz_status nz_boardnet_wide_stamps(uint64_t* out8) {
 nz_status nz_boardnet_fused(nz_boardnet* h, int32_t enable, int32_t* available) {
   if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_fused: null handle");
   if (enable >= 0) h->use_fused = enable != 0;
-  if (available) *available = h->fused_dev != nullptr || h->fused16_dev != nullptr ? 1 : 0;
+  if (available) *available = h->w.fused.built() || h->w.fused16.built() ? 1 : 0;
   return NZ_OK;
 }
 
@@ -2089,37 +2070,29 @@ static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n
   const size_t total = (size_t)((n + 15) / 16 * 16) * h->hw * h->inp;
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
   if (images_dev != nullptr)        // else: the caller filled the input rows itself (nz_boardnet_input_rows)
-    hipLaunchKernelGGL(nchw_to_rows_kernel, dim3(blocks), dim3(256), 0, s, images_dev, h->buffers[0], n_dev, n,
+    hipLaunchKernelGGL(nchw_to_rows_kernel, dim3(blocks), dim3(256), 0, s, images_dev, h->buffers[0].get(), n_dev, n,
                        h->net.in_channels, h->inp, h->hw);
-  if (h->fused16_dev != nullptr && h->use_fused) {  // one launch, on the BF16 matrix cores (three-way split arithmetic)
-    if (h->net.hex)
-      hipLaunchKernelGGL(fused16_net_kernel<true>, dim3(h->fused16_grid), dim3(FUSED_THREADS), h->fused16_lds_bytes, s,
-                         h->fused16_dev, h->buffers[0], h->inp, n_dev, n, logits_dev, probs_dev, value_dev);
-    else
-      hipLaunchKernelGGL(fused16_net_kernel<false>, dim3(h->fused16_grid), dim3(FUSED_THREADS), h->fused16_lds_bytes, s,
-                         h->fused16_dev, h->buffers[0], h->inp, n_dev, n, logits_dev, probs_dev, value_dev);
+  // every layer, the softmax and the value in one launch (activations in LDS): on the BF16 matrix cores (three-way split
+  // arithmetic) when that form was built, else on the FP32 ones
+  auto one_launch = [&](const auto& f) {
+    hipLaunchKernelGGL(f.fn, dim3(f.grid), dim3(FUSED_THREADS), f.lds_bytes, s, f.prog.get(), h->buffers[0].get(), h->inp,
+                       n_dev, n, logits_dev, probs_dev, value_dev);
+  };
+  if (h->use_fused && (h->w.fused16.built() || h->w.fused.built())) {
+    if (h->w.fused16.built()) one_launch(h->w.fused16);
+    else one_launch(h->w.fused);
     B_HIP(h, hipGetLastError());
     return NZ_OK;
   }
-  if (h->fused_dev != nullptr && h->use_fused) {    // every layer, the softmax and the value in one launch (activations in LDS)
-    if (h->net.hex)
-      hipLaunchKernelGGL(fused_net_kernel<true>, dim3(h->fused_grid), dim3(FUSED_THREADS), h->fused_lds_bytes, s, h->fused_dev,
-                         h->buffers[0], h->inp, n_dev, n, logits_dev, probs_dev, value_dev);
-    else
-      hipLaunchKernelGGL(fused_net_kernel<false>, dim3(h->fused_grid), dim3(FUSED_THREADS), h->fused_lds_bytes, s, h->fused_dev,
-                         h->buffers[0], h->inp, n_dev, n, logits_dev, probs_dev, value_dev);
-    B_HIP(h, hipGetLastError());
-    return NZ_OK;
-  }
-  for (const ConvOp& op : h->ops) {
-    const PackedConv& pc = h->convs[&op - h->ops.data()];
+  for (const ConvOp& op : h->w.ops) {
+    const PackedConv& pc = h->w.convs[&op - h->w.ops.data()];
     ConvArgs a;
-    a.src0 = h->buffers[op.src0];
-    a.src1 = op.src1 >= 0 ? h->buffers[op.src1] : nullptr;
-    a.w = pc.dev;
-    a.ws = pc.dev_split;
-    a.res = op.res >= 0 ? h->buffers[op.res] : nullptr;
-    a.dst = h->buffers[op.dst];
+    a.src0 = h->buffers[op.src0].get();
+    a.src1 = op.src1 >= 0 ? h->buffers[op.src1].get() : nullptr;
+    a.w = pc.dev.get();
+    a.ws = pc.dev_split.get();
+    a.res = op.res >= 0 ? h->buffers[op.res].get() : nullptr;
+    a.dst = h->buffers[op.dst].get();
     a.n_dev = n_dev; a.n_host = n; a.hw = h->hw; a.h = h->rows; a.wd = h->cols;
     a.c0 = pc.c0p; a.c1 = pc.c1p;
     a.s0 = h->buffer_channels[op.src0];
@@ -2130,8 +2103,8 @@ static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n
     if (a.c0 > a.s0 || a.c1 > a.s1 || pc.coutp > a.cd) return bfail(h, NZ_ERR_STATE, "internal: layer shapes disagree");
     dispatch_conv(a, pc.coutp / 16, s);
   }
-  hipLaunchKernelGGL(finalize_kernel, dim3(n), dim3(64), 0, s, h->buffers[h->policy_buf], h->buffer_channels[h->policy_buf],
-                     h->net.policy_channels, h->buffers[h->value_buf], h->buffer_channels[h->value_buf], h->hw, n_dev, n,
+  hipLaunchKernelGGL(finalize_kernel, dim3(n), dim3(64), 0, s, h->buffers[h->policy_buf].get(), h->buffer_channels[h->policy_buf],
+                     h->net.policy_channels, h->buffers[h->value_buf].get(), h->buffer_channels[h->value_buf], h->hw, n_dev, n,
                      logits_dev, probs_dev, value_dev);
   B_HIP(h, hipGetLastError());
   return NZ_OK;
@@ -2146,7 +2119,7 @@ nz_status nz_boardnet_forward(nz_boardnet* h, const float* images_dev, int32_t n
 nz_status nz_boardnet_input_rows(nz_boardnet* h, float** rows_dev, int32_t* row_stride) {
   if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_input_rows: null handle");
   if (!rows_dev || !row_stride) return bfail(h, NZ_ERR_ARG, "nz_boardnet_input_rows: null argument");
-  *rows_dev = h->buffers[0];
+  *rows_dev = h->buffers[0].get();
   *row_stride = h->inp;
   return NZ_OK;
 }

@@ -11,7 +11,9 @@ struct nz_boardnet;
 namespace nz {
 
 struct WaveNet {
-  const Fused16Program* prog;     // device memory; offsets are floats from the wavefront's LDS block
+  const Fused16Program* prog;     // device memory, borrowed: the network handle owns it, and its next set_weights (or its
+                                  // destroy) releases it -- ask boardnet_wave_program again on every play, keep no copy.
+                                  // Offsets are floats from the wavefront's LDS block
   int32_t lds_floats;             // size of that block
   int32_t stage_off, stage_floats;  // float32 image [hw][inp] the leaf's planes are written to before they are split into
                                   // the input pieces (it lies over trunk buffers: zeroed again once the pieces are made)

@@ -16,6 +16,7 @@
 #include "hip_own.hpp"
 #include "scs_mt.hpp"
 #include "ttt_agents.hpp"
+#include "weight_pack.hpp"
 
 using namespace nz;
 
@@ -145,17 +146,6 @@ struct Span {
   }
 };
 
-int head_channel(int width, int out, int n_layers, int idx) {   // blocks.py:56-66,144-153
-  const double step = (double)(out - width) / n_layers;
-  double prev = width;
-  int c = width;
-  for (int i = 0; i < idx; ++i) {
-    prev += step;
-    c = (int)prev;
-  }
-  return c;
-}
-
 // One conv tensor repacked for the MFMA kernel (net_dev.hpp): per 16-channel output
 // tile nt a contiguous weight stream main[nt][kgroup of 32 ch][tap][piece][lane][8 bf16] (the
 // three exact bf16 pieces of every weight) and, for the two convs that also read the raw
@@ -164,19 +154,6 @@ struct PackedConv {
   int cout, cin, cin_main, kgroups, ntiles, extra;
   int32_t w_off, wx_off;
 };
-// a = p[0] + p[1] + p[2] exactly, each piece a bf16 number (the next 8 significant bits, truncated)
-static void split3(float a, uint16_t p[3]) {
-  float r = a;
-  for (int i = 0; i < 3; ++i) {
-    uint32_t bits;
-    memcpy(&bits, &r, 4);
-    bits &= 0xFFFF0000u;
-    p[i] = (uint16_t)(bits >> 16);
-    float t;
-    memcpy(&t, &bits, 4);
-    r = r - t;
-  }
-}
 PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vector<float>& out) {
   PackedConv pc{};
   pc.cout = cout; pc.cin = cin; pc.cin_main = cin_main;
@@ -192,13 +169,11 @@ PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vecto
         for (int piece = 0; piece < 3; ++piece)
           for (int lane = 0; lane < 64; ++lane)
             for (int pr = 0; pr < 4; ++pr) {       // lane holds channels 32 kg + 8 (lane >> 4) + 0..7 as 4 bf16 pairs
-              uint16_t lo[3], hi[3];
               const int co = nt * 16 + (lane & 15), ci = kg * 32 + (lane >> 4) * 8 + 2 * pr;
-              split3(weight(co, ci, t), lo);
-              split3(weight(co, ci + 1, t), hi);
-              const uint32_t word = (uint32_t)lo[piece] | ((uint32_t)hi[piece] << 16);
+              uint32_t word[3];
+              split3_pair(weight(co, ci, t), weight(co, ci + 1, t), word);
               float f;
-              memcpy(&f, &word, 4);
+              memcpy(&f, &word[piece], 4);
               out.push_back(f);
             }
   pc.wx_off = (int32_t)out.size();
@@ -426,9 +401,9 @@ std::string net_layout(const nz_net_desc* net, int recurrent_iterations, NetLayo
   shapes.push_back({W, IN, L.trunk_k});
   if (L.recall) shapes.push_back({W, W + IN, 3});
   for (int i = (int)shapes.size(); i < L.trunk_tensors; ++i) shapes.push_back({W, W, L.trunk_k});
-  for (int i = 0; i < 2; ++i)
-    shapes.push_back({head_channel(W, net->policy_channels, 2, i + 1), head_channel(W, net->policy_channels, 2, i), 3});
-  for (int i = 0; i < 4; ++i) shapes.push_back({head_channel(W, 1, 4, i + 1), head_channel(W, 1, 4, i), 3});
+  const std::vector<int> pc = head_channels(W, net->policy_channels, 2), vc = head_channels(W, 1, 4);
+  for (int i = 0; i < 2; ++i) shapes.push_back({pc[i + 1], pc[i], 3});
+  for (int i = 0; i < 4; ++i) shapes.push_back({vc[i + 1], vc[i], 3});
   return "";
 }
 // The network as per-wave job lists (`convs`: the packed tensors' layout); `flops`: in-bounds taps only, 2 * Cout * Cin *

@@ -312,6 +312,48 @@ def test_set_weights_on_a_live_handle(name):
     net.close()
 
 
+@pytest.mark.parametrize("name", ["two_by_two", "rec_odd"])
+def test_a_board_net_leaves_nothing_behind(name):
+    """Twelve handles made, given weights, run in each form, given other weights, run and closed: the device's free
+    memory after the twelfth is what it was after the second, give or take one handle (tests/test_gpu_scs_lifecycle.py,
+    test_nothing_left_behind).  two_by_two holds both one-launch programs, rec_odd the float32 one and two-source
+    layers."""
+    import torch
+    case = bc.BY_NAME[name]
+    n = 17
+    x, _ = _want(case, 0, n)
+    images = _images(x)
+    w1, w2 = bc.weights(case), bc.weights(case, seed=case.seed + 1000)
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    def cycle():
+        before = free()
+        net = _net(case, bc.SHARED_MAX_BATCH, w1)
+        assert net.fused(True)
+        _forward(net, images, n)
+        net.fused(False)
+        _forward(net, images, n)
+        net.fused(True)
+        net.set_weights(w2, case.iters)
+        _forward(net, images, n)
+        held = before - free()
+        net.close()
+        return held
+
+    readings, footprint = {}, 0
+    for i in range(1, 13):
+        held = cycle()
+        if i in (2, 12):
+            readings[i] = free()
+        if i == 2:
+            footprint = held                       # (cycle 1 also warms the tensor allocator up)
+    print(f"{name}: free after cycle 2: {readings[2]}, after cycle 12: {readings[12]}, one handle holds {footprint} bytes")
+    assert readings[12] >= readings[2] - footprint
+
+
 @pytest.mark.parametrize("name", SURFACE_CASES)
 def test_call_on_a_side_stream(name):
     """Images produced on a non-default stream and the network called on it with no synchronisation in between."""
@@ -414,6 +456,19 @@ def test_refusals_carry_a_status_and_a_message():
     assert err.value.code == _lib.NZ_ERR_ARG
     with pytest.raises(_lib.NzError, match="no weights set"):       # and the handle stays unusable, not half set
         net.forward(torch.zeros((1, rec.in_channels, rec.rows, rec.cols), device="cuda"))
+    net.close()
+
+    # a live handle, one tensor too few: refused before anything is packed, and the old weights are gone with it
+    net = _net(case, 17)
+    want17 = _forward(net, images, 17)
+    short = dict(list(bc.weights(case).items())[:-1])
+    with pytest.raises(_lib.NzError, match="tensors") as err:
+        net.set_weights(short, case.iters)
+    assert err.value.code == _lib.NZ_ERR_ARG
+    st = lib.nz_boardnet_forward(net._h, c_void_p(images.data_ptr()), 17, None, None, None, value.ptr(), stream)
+    assert st == _lib.NZ_ERR_STATE and b"no weights set" in lib.nz_boardnet_last_error(net._h)
+    net.set_weights(bc.weights(case), case.iters)              # the right weights: a fresh handle's bits
+    assert _equal(_forward(net, images, 17), want17)
     net.close()
 
     # NULL handles: a status and a message in the handle-less slot

@@ -213,3 +213,39 @@ def test_nothing_left_behind(randomized):
     print(f"free after cycle 2: {readings[2]}, after cycle 12: {readings[12]}, one handle holds {footprint} bytes")
     assert footprint > 0
     assert readings[12] >= readings[2] - footprint
+
+
+def test_nothing_left_behind_with_the_network_handle(randomized):
+    """The same with the network handle made and closed inside the cycle: every play asks the new handle for its
+    per-wavefront program (persistent(1) stays set), which that handle builds, owns and releases."""
+    import torch
+    cfg, _ = randomized
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    def cycle():
+        before = free()
+        net, _ = _net(cfg, "convnet", 32, 3, seed=12, gain=2.0)
+        sp = _engine(cfg, training=True)
+        sp.cache(1 << 12)
+        sp.persistent(1)
+        sp.record([0, 3], 16)
+        sp.play_round(net, range(300, 316))
+        assert sp.persistent()
+        held = before - free()
+        sp.close()
+        net.close()
+        return held
+
+    readings, footprint = {}, 0
+    for i in range(1, 13):
+        held = cycle()
+        if i in (2, 12):
+            readings[i] = free()
+        if i == 2:
+            footprint = held                       # (cycle 1 also warms the tensor allocator up)
+    print(f"free after cycle 2: {readings[2]}, after cycle 12: {readings[12]}, search and network hold {footprint} bytes")
+    assert footprint > 0
+    assert readings[12] >= readings[2] - footprint

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 
 def split3_trunc(x):
-    """x = p0 + p1 + p2, each the next 8 significant bits (truncation), as engine.hip split3 / net_dev.hpp split_pair."""
+    """x = p0 + p1 + p2, each the next 8 significant bits (truncation), as weight_pack.hpp split3 / net_dev.hpp split_pair."""
     x = np.asarray(x, np.float32)
     pieces, r = [], x.copy()
     for _ in range(3):
