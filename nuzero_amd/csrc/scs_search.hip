@@ -279,19 +279,19 @@ __device__ __forceinline__ SNode* arena(const SearchParams& p, int g) {
   return p.nodes + (size_t)g * p.cap + (size_t)p.half[g] * p.half_cap;
 }
 
-__global__ void search_reset_kernel(SearchParams p) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g == 0) {
-    *p.leaf_count = 0; *p.active_count = 0; *p.error_flag = 0;
-    for (int i = 0; i < 16; ++i)
-      if (i < 8 || i > 10) p.counters[i] = 0;      // [8..10] belong to the inference cache (nz_scs_search_cache)
-  }
-  if (g >= p.n_games) return;
+// a node nobody has visited or evaluated: the root of a new game (prior 0, action 0), a fresh child of an expansion
+__device__ __forceinline__ SNode blank_node(double prior, int action) {
+  SNode n;
+  n.prior = prior; n.value_sum = 0.0; n.visit = 0; n.child_base = 0; n.n_children = 0; n.action = (uint16_t)action;
+  n.to_play = -1; n.prior_f64 = 0; n.terminal = 0; n.pad = 0;
+  return n;
+}
+
+// slot g starts a new game: the rules' initial state, a tree of one blank root in half 0 of the arena, no records
+__device__ __forceinline__ void reset_slot(const SearchParams& p, int g) {
   Scs(rules_of(p, g), p.real[g]).reset();
   p.half[g] = 0;
-  SNode& n = p.nodes[(size_t)g * p.cap];
-  n.prior = 0.0; n.value_sum = 0.0; n.visit = 0; n.child_base = 0; n.n_children = 0; n.action = 0;
-  n.to_play = -1; n.prior_f64 = 0; n.terminal = 0; n.pad = 0;
+  p.nodes[(size_t)g * p.cap] = blank_node(0.0, 0);
   p.node_count[g] = 1;
   p.root[g] = 0;
   p.sims_left[g] = 0;
@@ -302,6 +302,16 @@ __global__ void search_reset_kernel(SearchParams p) {
     p.rec_children[(size_t)g * p.max_moves + m] = 0;
     p.rec_tree_size[(size_t)g * p.max_moves + m] = 0;
   }
+}
+
+__global__ void search_reset_kernel(SearchParams p) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g == 0) {
+    *p.leaf_count = 0; *p.active_count = 0; *p.error_flag = 0;
+    for (int i = 0; i < 16; ++i)
+      if (i < 8 || i > 10) p.counters[i] = 0;      // [8..10] belong to the inference cache (nz_scs_search_cache)
+  }
+  if (g < p.n_games) reset_slot(p, g);
 }
 
 // ---- rounds of more games than slots (nz_scs_search_play_round) ----------------------------------------------------
@@ -346,22 +356,7 @@ __global__ void archive_kernel(SearchParams p, RoundStore st, const int32_t* __r
 // search_reset_kernel for the slots with restart[g] != 0 (counters and flags are the round's: untouched)
 __global__ void restart_kernel(SearchParams p, const int32_t* __restrict__ restart) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= p.n_games || !restart[g]) return;
-  Scs(rules_of(p, g), p.real[g]).reset();
-  p.half[g] = 0;
-  SNode& n = p.nodes[(size_t)g * p.cap];
-  n.prior = 0.0; n.value_sum = 0.0; n.visit = 0; n.child_base = 0; n.n_children = 0; n.action = 0;
-  n.to_play = -1; n.prior_f64 = 0; n.terminal = 0; n.pad = 0;
-  p.node_count[g] = 1;
-  p.root[g] = 0;
-  p.sims_left[g] = 0;
-  p.pending[g] = -1;
-  p.path_len[g] = 0;
-  for (int m = 0; m < p.max_moves; ++m) {
-    p.rec_action[(size_t)g * p.max_moves + m] = -1;
-    p.rec_children[(size_t)g * p.max_moves + m] = 0;
-    p.rec_tree_size[(size_t)g * p.max_moves + m] = 0;
-  }
+  if (g < p.n_games && restart[g]) reset_slot(p, g);
 }
 
 // children of each live game's root (the number of gamma draws of the next move)
@@ -458,6 +453,164 @@ __global__ __launch_bounds__(64) void cache_put_kernel(SearchParams p, const int
   for (int i = lane; i < A; i += 64) p.c_probs[e * A + i] = p.eval_probs[(size_t)slot * A + i];
 }
 
+// ---- the tree step both search routes run ---------------------------------------------------------------------------
+// wave_kernel (a launch per simulation wave) and persist_leader (a move's whole search in one launch) play the same games
+// bit for bit, so the steps whose exactness that rests on -- selection with its tie rule and dtypes, expansion with
+// numpy's sum and its total == 0 retry, a fresh child's layout, the backup's addition, the leaf's cache key -- are
+// written once, here.  Each route keeps what differs: where a level's first 64 children come from (a load / a copy
+// fetched under the rule step), where the path lives (memory / a register per lane), when the backup reads the path's
+// statistics, where the evaluation comes from.  No helper is told which route called it.
+
+// what a level of the descent needs of the node it leaves
+struct Level { int visit, child_base, n_children, to_play; };
+__device__ __forceinline__ Level level_of(const SNode& n) { return Level{n.visit, n.child_base, n.n_children, n.to_play}; }
+
+// One level of the descent (Explorer.select_child, :99-112): lane j scores children j, j + 64, ... of the node `par`,
+// `first(j)` supplying child j < 64 and the rest loaded here; the wavefront's best (score, action) wins.  Returns the
+// winning key (action << 8 | child index), the chosen child's slot in `node` and its Level in `par`.
+// One dependent load per level: the chosen child's record was read when it was scored, so the lane that holds it
+// hands the four words the next level needs (visit count, first child, children count, to_play) to the wavefront
+// (v_readlane: the winner is wave-uniform) instead of every level re-reading its parent from memory.
+template <typename First>
+__device__ __forceinline__ int select_level(const SearchParams& p, const SNode* nodes, Level& par, double sq, double cb,
+                                            int lane, First first, int& node) {
+  const bool negate = par.to_play == p.negate_player;
+  double score = -INFINITY;
+  int key = -1;
+  Level best{0, 0, 0, 0};                                        // this lane's best child so far
+  for (int j = lane; j < par.n_children; j += 64) {              // one chunk of 64 children per round, usually one
+    const SNode c = j < 64 ? first(j) : nodes[par.child_base + j];
+    const double sc = child_score(p, c, sq, cb, negate);
+    const int ky = ((int)c.action << 8) | j;                     // j < 256; children are in ascending action order
+    if (sc > score || (sc == score && ky > key)) {
+      score = sc; key = ky;
+      best = level_of(c);
+    }
+  }
+  const int my_key = key;
+  key = wave_argmax_key(score, key);          // max over (score, action): the larger action wins a tie (Explorer.py:100)
+  // the lane that scored the winner (keys are unique: they carry the child index)
+  const unsigned long long holders = __ballot(my_key == key);
+  const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)holders) - 1);
+  node = par.child_base + (key & 0xff);
+  par = Level{__builtin_amdgcn_readlane(best.visit, wl), __builtin_amdgcn_readlane(best.child_base, wl),
+              __builtin_amdgcn_readlane(best.n_children, wl), __builtin_amdgcn_readlane(best.to_play, wl)};
+  return key;
+}
+
+// The ascending list of the legal actions in a mask (Explorer.py:163-165) into sidx: lane l enumerates mask word
+// 64 w + l = `word(w)` (0 past the mask's end) behind a prefix sum of the words' bit counts.  Returns their number.
+template <typename Words>
+__device__ __forceinline__ int legal_list_of(Words word, int* sidx, int lane) {
+  int k = 0;
+#pragma unroll
+  for (int w = 0; w < (MASK_WORDS + 63) / 64; ++w) {
+    uint32_t bits = word(w);
+    int inc = __popc(bits);
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += o;
+    }
+    int off = k + inc - __popc(bits);
+    while (bits) {
+      const int b = __ffs(bits) - 1;
+      bits &= bits - 1;
+      if (off < MAXC_LIMIT) sidx[off] = (w * 64 + lane) * 32 + b;
+      ++off;
+    }
+    k += __shfl(inc, 63, 64);
+  }
+  return k;
+}
+
+// Expansion (Explorer.py:162-181): child j = the j-th legal action, prior = its masked probability / their float32
+// np.sum.  Child 64 c + lane's action is in my_idx[c] (0x7fffffff past the k-th) and its probability in my_val[c] (0
+// past the k-th); the records go to nodes[base .. base + k) and `parent` is linked to them.
+template <int CH>
+__device__ __forceinline__ void expand_children(const SearchParams& p, SNode* nodes, int parent, int base, int k, int lane,
+                                                const int (&my_idx)[CH], float (&my_val)[CH]) {
+  float total = np_sum_sparse_f32_wave<CH>(p, my_idx, my_val, k);
+  if (total == 0.0f) {                  // probs += mask (Explorer.py:171-173)
+#pragma unroll
+    for (int c = 0; c < CH; ++c) my_val[c] = my_val[c] + 1.0f;
+    total = np_sum_sparse_f32_wave<CH>(p, my_idx, my_val, k);
+  }
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const int j = c * 64 + lane;
+    if (j < k) nodes[base + j] = blank_node((double)(my_val[c] / total), my_idx[c]);
+  }
+  if (lane == 0) {
+    nodes[parent].child_base = base;
+    nodes[parent].n_children = (uint16_t)k;
+  }
+}
+
+// backup (Explorer.py:132-135): the same value to every node of the path, root included
+__device__ __forceinline__ void backup_node(SNode& n, double v) {
+  n.visit += 1;
+  n.value_sum = n.value_sum + v;
+}
+// the path's entries from level `from` on, read from memory: from = 64 behind a first 64 levels that the caller holds in
+// registers (one per lane), 0 for the whole path
+__device__ __forceinline__ void backup_tail(SNode* nodes, const int32_t* path, int from, int plen, int lane, double v) {
+  for (int i = from + lane; i < plen; i += 64) backup_node(nodes[path[i]], v);
+}
+
+// the cache key (hi, lo) of game slot g's leaf with scratch state sc; returns the entry its low bits select
+__device__ __forceinline__ size_t leaf_cache_key(const SearchParams& p, int g, const ScsState& sc, int lane, uint64_t& hi,
+                                                 uint64_t& lo) {
+  state_hash_wave(sc, lane, hi, lo);
+  cache_key_of(p, g, hi, lo);
+  return (size_t)(lo & ((1ull << p.c_bits) - 1));
+}
+// what probability pr of action i adds to a cache entry's check word (cache_check_word)
+__device__ __forceinline__ uint64_t check_term(int i, float pr) {
+  return mix64((((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, pr)) ^ 0x9e3779b97f4a7c15ull);
+}
+
+// Lanes walk the actions i = lane, lane + 64, ... < A as f(i, cell, plane, j) -- action i = plane * hw + cell, the policy
+// planes' layout -- without a division per entry; j = the entry's place in its block of BLOCK entries (a constant after
+// unrolling, for callers that keep a register per place).
+template <int BLOCK, typename F>
+__device__ __forceinline__ void for_each_action_blocked(int A, int hw, int lane, F f) {
+  int cell = lane % hw, plane = lane / hw;
+  const int dcell = 64 % hw, dplane = 64 / hw;
+  for (int i0 = lane; i0 < A; i0 += 64 * BLOCK) {
+#pragma unroll
+    for (int j = 0; j < BLOCK; ++j) {
+      const int i = i0 + 64 * j;
+      if (i < A) f(i, cell, plane, j);
+      cell += dcell; plane += dplane;
+      if (cell >= hw) { cell -= hw; ++plane; }
+    }
+  }
+}
+template <typename F>
+__device__ __forceinline__ void for_each_action(int A, int hw, int lane, F f) {
+  for_each_action_blocked<1>(A, hw, lane, [&](int i, int cell, int plane, int) { f(i, cell, plane); });
+}
+
+// The per-pass constants of wave_network and what its callers place around a pass: the program's header words (read
+// once per move by the caller).
+struct WaveNetArgs {
+  const Fused16Program* prog;
+  int n_ops, rows, H, Wd;
+  int solo_at, solo_pol, solo_zero_off, solo_zero_len;
+  int in_off, in_cs, pol_off, pol_cs, val_off, val_cs;
+};
+// the program's header, one dword per lane, handed round by v_readlane
+__device__ __forceinline__ WaveNetArgs wave_net_args(const Fused16Program* prog, int lane) {
+  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
+  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
+  static_assert(HDR_DWORDS <= 64, "one dword per lane");
+  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(prog))[lane] : 0u;
+#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
+  return WaveNetArgs{prog, PHDR(n_ops), PHDR(hw), PHDR(h), PHDR(wd), PHDR(solo_at), PHDR(solo_pol), PHDR(solo_zero_off),
+                     PHDR(solo_zero_len), PHDR(in_off), PHDR(in_cs), PHDR(pol_off), PHDR(pol_cs), PHDR(val_off), PHDR(val_cs)};
+#undef PHDR
+}
+
 // One simulation wave of one game, one wavefront per game (Explorer.run_mcts, :49-61):
 //   mode & 1  finish the pending expansion with the supplied evaluation (Explorer.py:162-181) and
 //             back its value up           probs [n_leaves][A] float32 post-softmax, value [n_leaves]
@@ -510,25 +663,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
     const int my_node = lane < plen ? my_path0 : 0;
     const int my_visit = lane < plen ? nodes[my_node].visit : 0;
     const double my_vs = lane < plen ? nodes[my_node].value_sum : 0.0;
-    // legal actions in ascending order: lane w enumerates mask word w (and word 64 + w)
-    int k = 0;
-#pragma unroll
-    for (int w = 0; w < (MASK_WORDS + 63) / 64; ++w) {
-      uint32_t bits = mword[w];
-      int inc = __popc(bits);
-      for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-      }
-      int off = k + inc - __popc(bits);
-      while (bits) {
-        const int b = __ffs(bits) - 1;
-        bits &= bits - 1;
-        if (off < MAXC_LIMIT) sidx[off] = (w * 64 + lane) * 32 + b;
-        ++off;
-      }
-      k += __shfl(inc, 63, 64);
-    }
+    const int k = legal_list_of([&](int w) { return mword[w]; }, sidx, lane);
     const int base = base_in;
     const bool overflow = k > p.maxc;
     if (overflow || base + k > p.half_cap) {
@@ -543,28 +678,8 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
         my_idx[c] = j < k ? sidx[j] : 0x7fffffff;
         my_val[c] = j < k ? probs[(size_t)slot * A + my_idx[c]] : 0.0f;
       }
-      float total = np_sum_sparse_f32_wave(p, my_idx, my_val, k);
-      if (total == 0.0f) {                  // probs += mask (Explorer.py:171-173)
-#pragma unroll
-        for (int c = 0; c < MAXC_CHUNKS; ++c) my_val[c] = my_val[c] + 1.0f;
-        total = np_sum_sparse_f32_wave(p, my_idx, my_val, k);
-      }
-#pragma unroll
-      for (int c = 0; c < MAXC_CHUNKS; ++c) {
-        const int j = c * 64 + lane;
-        if (j < k) {
-          SNode n;
-          n.prior = (double)(my_val[c] / total);
-          n.value_sum = 0.0; n.visit = 0; n.child_base = 0; n.n_children = 0; n.action = (uint16_t)my_idx[c];
-          n.to_play = -1; n.prior_f64 = 0; n.terminal = 0; n.pad = 0;
-          nodes[base + j] = n;
-        }
-      }
-      if (lane == 0) {
-        nodes[leaf].child_base = base;
-        nodes[leaf].n_children = (uint16_t)k;
-        p.node_count[g] = base + k;
-      }
+      expand_children<MAXC_CHUNKS>(p, nodes, leaf, base, k, lane, my_idx, my_val);
+      if (lane == 0) p.node_count[g] = base + k;
     }
     if (lane == 0) {
       p.pending[g] = -1;
@@ -575,11 +690,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
       nodes[my_node].visit = my_visit + 1;
       nodes[my_node].value_sum = my_vs + v;
     }
-    for (int i = 64 + lane; i < plen; i += 64) {
-      SNode& n = nodes[path[i]];
-      n.visit += 1;
-      n.value_sum = n.value_sum + v;
-    }
+    backup_tail(nodes, path, 64, plen, lane, v);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   }
   NZ_STAMP(0);                                  // expansion + backup of the evaluated leaf
@@ -630,40 +741,11 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
     int node = root, plen = 1;
     if (lane == 0) path[0] = root;
     bool bad = false;
-    // One dependent load per level: the chosen child's record was read when it was scored, so the lane that holds it
-    // hands the four words the next level needs (visit count, first child, children count, to_play) to the wavefront
-    // (v_readlane: the winner is wave-uniform) instead of every level re-reading its parent from memory.
-    int par_visit, par_base, par_k, par_to_play;
-    {
-      const SNode r0 = nodes[root];
-      par_visit = r0.visit; par_base = r0.child_base; par_k = r0.n_children; par_to_play = r0.to_play;
-    }
-    while (par_k > 0) {
-      if (par_visit >= p.tab_len || plen >= p.max_path) { bad = true; break; }
-      const double sq = p.sqrt_tab[par_visit], cb = p.bias_tab[par_visit];
-      const bool negate = par_to_play == p.negate_player;
-      double score = -INFINITY;
-      int key = -1;
-      int b_visit = 0, b_base = 0, b_k = 0, b_to_play = 0;        // this lane's best child so far
-      for (int j = lane; j < par_k; j += 64) {                     // one chunk of 64 children per round, usually one
-        const SNode c = nodes[par_base + j];
-        const double sc = child_score(p, c, sq, cb, negate);
-        const int ky = ((int)c.action << 8) | j;                   // j < 256; children are in ascending action order
-        if (sc > score || (sc == score && ky > key)) {
-          score = sc; key = ky;
-          b_visit = c.visit; b_base = c.child_base; b_k = c.n_children; b_to_play = c.to_play;
-        }
-      }
-      const int my_key = key;
-      key = wave_argmax_key(score, key);          // max over (score, action): the larger action wins a tie (Explorer.py:100)
-      // the lane that scored the winner (keys are unique: they carry the child index)
-      const unsigned long long holders = __ballot(my_key == key);
-      const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)holders) - 1);
-      node = par_base + (key & 0xff);
-      par_visit = __builtin_amdgcn_readlane(b_visit, wl);
-      par_base = __builtin_amdgcn_readlane(b_base, wl);
-      par_k = __builtin_amdgcn_readlane(b_k, wl);
-      par_to_play = __builtin_amdgcn_readlane(b_to_play, wl);
+    Level par = level_of(nodes[root]);
+    while (par.n_children > 0) {
+      if (par.visit >= p.tab_len || plen >= p.max_path) { bad = true; break; }
+      const double sq = p.sqrt_tab[par.visit], cb = p.bias_tab[par.visit];
+      const int key = select_level(p, nodes, par, sq, cb, lane, [&](int j) { return nodes[par.child_base + j]; }, node);
       if (lane == 0) path[plen] = node;
       scs_step_wave(R, sc, key >> 8, lane);
       ++plen;
@@ -684,11 +766,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       const double v = (double)sc.terminal_value;
-      for (int i = lane; i < plen; i += 64) {
-        SNode& n = nodes[path[i]];
-        n.visit += 1;
-        n.value_sum = n.value_sum + v;
-      }
+      backup_tail(nodes, path, 0, plen, lane, v);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       --sims_left;
       --budget;
@@ -701,9 +779,7 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
     bool hit = false;
     size_t entry = 0;
     if (p.c_bits > 0) {
-      state_hash_wave(sc, lane, key_hi, key_lo);
-      cache_key_of(p, g, key_hi, key_lo);
-      entry = (size_t)(key_lo & ((1ull << p.c_bits) - 1));
+      entry = leaf_cache_key(p, g, sc, lane, key_hi, key_lo);
       hit = p.c_id[2 * entry] == key_hi && p.c_id[2 * entry + 1] == key_lo;      // uniform: every lane reads the same words
     }
     int slot = 0;
@@ -1132,12 +1208,6 @@ __device__ __forceinline__ void pair_sync(int* flags, int me, int& seq, int lane
 #else
 #define WSTAMP(slot)
 #endif
-// The per-pass constants of wave_network: the program's header words it needs (read once per move by the caller).
-struct WaveNetArgs {
-  const Fused16Program* prog;
-  int n_ops, rows, H, Wd;
-  int solo_at, solo_pol, solo_zero_off, solo_zero_len;
-};
 // Every layer of the network for the position whose input pieces sit in the game's block.  Trunk layers: this wavefront
 // takes column tiles half, half + 2, ... of the layer's PAIRS of column tiles (both row tiles each), then row tile `half`
 // of an odd last column tile (whole it was the leader's alone and the helper waited), and the pair meets after every
@@ -1235,34 +1305,16 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
   }
 }
 
-// The ascending list of a position's legal actions (Explorer.py:163-165): the mask in LDS, then lane w enumerates mask
-// word w (and word 64 + w) behind a prefix sum of the words' bit counts.  Returns their number.
+// The ascending list of a position's legal actions: the mask in LDS, then its list (legal_list_of).  Returns their number.
 __device__ __forceinline__ int legal_list_wave(const ScsRules& R, const ScsState& sc, uint32_t* smask, int* sidx, int lane) {
   scs_legal_mask_wave<MASK_WORDS, false>(R, sc, smask, lane);
-  int k = 0;
-#pragma unroll
-  for (int w = 0; w < (MASK_WORDS + 63) / 64; ++w) {
-    uint32_t bits = w * 64 + lane < MASK_WORDS ? smask[w * 64 + lane] : 0u;
-    int inc = __popc(bits);
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += o;
-    }
-    int off = k + inc - __popc(bits);
-    while (bits) {
-      const int b = __ffs(bits) - 1;
-      bits &= bits - 1;
-      if (off < MAXC_LIMIT) sidx[off] = (w * 64 + lane) * 32 + b;
-      ++off;
-    }
-    k += __shfl(inc, 63, 64);
-  }
-  return k;
+  return legal_list_of([&](int w) { return w * 64 + lane < MASK_WORDS ? smask[w * 64 + lane] : 0u; }, sidx, lane);
 }
 // This wavefront's half (`half` = 0 leader, 1 helper) of turning the staged float32 planes into the input pieces (every
 // row of the input region, its row of zeros included) ...
-__device__ __forceinline__ void split_planes_half(float* __restrict__ net, const PersistArgs& q, int hw, int in_off, int in_cs,
-                                                  int lane, int half) {
+__device__ __forceinline__ void split_planes_half(float* __restrict__ net, const PersistArgs& q, const WaveNetArgs& wn, int lane,
+                                                  int half) {
+  const int hw = wn.rows, in_off = wn.in_off, in_cs = wn.in_cs;
   const float* const stage = net + q.stage_off;
   const int chunks = q.inp >> 3;
   for (int i = lane + 64 * half; i < (hw + 1) * chunks; i += 128) {
@@ -1316,17 +1368,8 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
   }
   const int rec = q.rec_slot ? q.rec_slot[g] : -1;
   int rec_n = rec >= 0 ? q.rec_count[rec] : 0;
-  // the program's header, one dword per lane
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
-  static_assert(HDR_DWORDS <= 64, "one dword per lane");
-  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(q.prog))[lane] : 0u;
-#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
-  const int hw = PHDR(hw), H = PHDR(h), Wd = PHDR(wd), n_ops = PHDR(n_ops), planes = PHDR(planes);
-  const int in_off = PHDR(in_off), in_cs = PHDR(in_cs);
-  const int pol_off = PHDR(pol_off), pp = PHDR(pol_cs), val_off = PHDR(val_off), vp = PHDR(val_cs);
-  const WaveNetArgs wna{q.prog, n_ops, hw, H, Wd, PHDR(solo_at), PHDR(solo_pol), PHDR(solo_zero_off), PHDR(solo_zero_len)};
-#undef PHDR
+  const WaveNetArgs wna = wave_net_args(q.prog, lane);
+  const int hw = wna.rows, pp = wna.pol_cs;
   scs_sync<false>();
   int n_sim = 0, n_exp = 0, n_hit = 0, n_miss = 0;      // (of this move: 32 bits are plenty, and half the registers)
   bool failed = false;
@@ -1354,45 +1397,20 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
     int node = root, plen = 1;
     int my_path = root;                         // lane i holds path[i] (levels past 63 go to memory)
     bool bad = false;
-    int par_visit, par_base, par_k, par_to_play;
-    {
-      const SNode r0 = nodes[root];
-      par_visit = r0.visit; par_base = r0.child_base; par_k = r0.n_children; par_to_play = r0.to_play;
-    }
+    Level par = level_of(nodes[root]);
     // A level's children (its first 64) and its two table entries are fetched BEFORE the rule step that leads to it:
     // the round trip to L2 runs under the step's serial code instead of after it.
     SNode cnext;
     double sq = 0.0, cb = 0.0;
     auto fetch_level = [&]() {
-      if (lane < par_k) cnext = nodes[par_base + lane];
-      if (par_visit < p.tab_len) { sq = p.sqrt_tab[par_visit]; cb = p.bias_tab[par_visit]; }
+      if (lane < par.n_children) cnext = nodes[par.child_base + lane];
+      if (par.visit < p.tab_len) { sq = p.sqrt_tab[par.visit]; cb = p.bias_tab[par.visit]; }
     };
     fetch_level();
-    while (par_k > 0) {
-      if (par_visit >= p.tab_len || plen >= p.max_path) { bad = true; break; }
-      const bool negate = par_to_play == p.negate_player;
-      double score = -INFINITY;
-      int key = -1;
-      int b_visit = 0, b_base = 0, b_k = 0, b_to_play = 0;
-      for (int j = lane; j < par_k; j += 64) {
-        const SNode c = j < 64 ? cnext : nodes[par_base + j];
-        const double scv = child_score(p, c, sq, cb, negate);
-        const int ky = ((int)c.action << 8) | j;
-        if (scv > score || (scv == score && ky > key)) {
-          score = scv; key = ky;
-          b_visit = c.visit; b_base = c.child_base; b_k = c.n_children; b_to_play = c.to_play;
-        }
-      }
-      const int my_key = key;
-      key = wave_argmax_key(score, key);
-      const unsigned long long holders = __ballot(my_key == key);
-      const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)holders) - 1);
-      node = par_base + (key & 0xff);
-      par_visit = __builtin_amdgcn_readlane(b_visit, wl);
-      par_base = __builtin_amdgcn_readlane(b_base, wl);
-      par_k = __builtin_amdgcn_readlane(b_k, wl);
-      par_to_play = __builtin_amdgcn_readlane(b_to_play, wl);
-      if (par_k > 0) fetch_level();
+    while (par.n_children > 0) {
+      if (par.visit >= p.tab_len || plen >= p.max_path) { bad = true; break; }
+      const int key = select_level(p, nodes, par, sq, cb, lane, [&](int) { return cnext; }, node);
+      if (par.n_children > 0) fetch_level();
       if (plen < 64) { if (lane == plen) my_path = node; }
       else if (lane == 0) path[plen] = node;
       scs_step_wave<false>(R, sc, key >> 8, lane, tiles_magic);
@@ -1424,9 +1442,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
 #ifdef NZ_PERSIST_STAMP_GO    // diagnostic of a diagnostic: the leaf's bookkeeping up to the helper's wake-up, reported in the "slowest" slot
       PSTAMP(9);
 #endif
-      float* const pol = net + pol_off;
-      // (action i = plane * hw + cell; lanes walk i = lane, lane + 64, ... without a division per entry)
-      const int cell0 = lane % hw, plane0 = lane / hw, dcell = 64 % hw, dplane = 64 / hw;
+      float* const pol = net + wna.pol_off;
       float sum = 1.0f, value = 0.f;
       // The inference cache (Explorer.py:146-155): the table is shared by every game of the engine and, on this route, read
       // and written while the kernel runs -- by games on all eight XCDs, so every access is an agent-scope atomic (past this
@@ -1440,19 +1456,19 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
       size_t entry = 0;
       bool hit = false;
       if (p.c_bits > 0) {
-        state_hash_wave(sc, lane, key_hi, key_lo);
+        entry = (size_t)uniform64(leaf_cache_key(p, g, sc, lane, key_hi, key_lo));
         key_hi = uniform64(key_hi); key_lo = uniform64(key_lo);         // (the same on every lane: scalar registers)
-        cache_key_of(p, g, key_hi, key_lo);
-        entry = (size_t)(key_lo & ((1ull << p.c_bits) - 1));
         unsigned long long* const id = reinterpret_cast<unsigned long long*>(p.c_id + 2 * entry);
         const unsigned long long id0 = __hip_atomic_load(id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long id1 = __hip_atomic_load(id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long chk = __hip_atomic_load(reinterpret_cast<unsigned long long*>(p.c_check + entry), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const float cval = __hip_atomic_load(p.c_value + entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint64_t acc = 0;
-        {   // (all of a block's loads in flight together: one round trip to memory, not one per probability)
+        {   // (all of a block's loads in flight together: one round trip to memory, not one per probability -- which is
+            // why this walk over the actions is not for_each_action's: that one hands out an entry at a time)
           constexpr int PER = 12;
-          int cell = cell0, plane = plane0;
+          int cell = lane % hw, plane = lane / hw;
+          const int dcell = 64 % hw, dplane = 64 / hw;
           for (int i0 = 0; i0 < A; i0 += 64 * PER) {
             float r[PER];
 #pragma unroll
@@ -1465,7 +1481,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
               const int i = i0 + j * 64 + lane;
               if (i < A) {
                 pol[cell * pp + plane] = r[j];
-                acc += mix64((((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, r[j])) ^ 0x9e3779b97f4a7c15ull);
+                acc += check_term(i, r[j]);
               }
               cell += dcell; plane += dplane;
               if (cell >= hw) { cell -= hw; ++plane; }
@@ -1506,7 +1522,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
         }
       }
       if (!hit) {
-      split_planes_half(net, q, hw, in_off, in_cs, lane, 0);
+      split_planes_half(net, q, wna, lane, 0);
       scs_sync<false>();
       pair_sync(flags, 0, seq, lane);             // (both halves of the pieces are made: the staging space can go)
       zero_stage_half(net, q, lane, 0);
@@ -1522,32 +1538,17 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
 
       // softmax over ALL logits (Explorer.py:158-160) and value = tanh(mean of the value plane) (blocks.py:82-84)
       float mx = -INFINITY;
-      for (int i = lane, cell = cell0, plane = plane0; i < A; i += 64) {
-        mx = fmaxf(mx, pol[cell * pp + plane]);
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
+      for_each_action(A, hw, lane, [&](int, int cell, int plane) { mx = fmaxf(mx, pol[cell * pp + plane]); });
       for (int w = 32; w; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w, 64));
       // the sum in fused16_net_kernel's order for a workgroup of up to four positions (four wavefronts per position, each
       // lane adding every 256th entry, a butterfly per wavefront, the four partial sums added in turn), so that a game
       // plays the same moves on either route
       float part[4] = {0.f, 0.f, 0.f, 0.f};
-      {
-        int cell = cell0, plane = plane0;
-        for (int i0 = 0; i0 < A; i0 += 256) {
-#pragma unroll
-          for (int sub = 0; sub < 4; ++sub) {
-            const int i = i0 + sub * 64 + lane;
-            if (i < A) {
-              const float e = expf(pol[cell * pp + plane] - mx);
-              pol[cell * pp + plane] = e;
-              part[sub] += e;
-            }
-            cell += dcell; plane += dplane;
-            if (cell >= hw) { cell -= hw; ++plane; }
-          }
-        }
-      }
+      for_each_action_blocked<4>(A, hw, lane, [&](int, int cell, int plane, int sub) {
+        const float e = expf(pol[cell * pp + plane] - mx);
+        pol[cell * pp + plane] = e;
+        part[sub] += e;
+      });
       sum = 0.f;
 #pragma unroll
       for (int sub = 0; sub < 4; ++sub) {
@@ -1556,23 +1557,20 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
         sum += ps;
       }
       pair_sync(flags, 0, seq, lane);             // (the helper's value head is done)
-      float sv = lane < hw ? net[val_off + lane * vp] : 0.f;
+      float sv = lane < hw ? net[wna.val_off + lane * wna.val_cs] : 0.f;
       for (int w = 32; w; w >>= 1) sv += __shfl_xor(sv, w, 64);
       value = tanhf(sv / (float)hw);
-      (void)planes;
       scs_sync<false>();
       PSTAMP(5);                                // softmax + value
       if (p.c_bits > 0) {
         // KeylessCache.put (KeylessCache.py:60-75): the newest evaluation takes the entry; stores only, nothing to wait for
         unsigned long long* const id = reinterpret_cast<unsigned long long*>(p.c_id + 2 * entry);
         uint64_t acc = 0;
-        for (int i = lane, cell = cell0, plane = plane0; i < A; i += 64) {
+        for_each_action(A, hw, lane, [&](int i, int cell, int plane) {
           const float pr = pol[cell * pp + plane] / sum;
           __hip_atomic_store(p.c_probs + entry * A + i, pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          acc += mix64((((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, pr)) ^ 0x9e3779b97f4a7c15ull);
-          cell += dcell; plane += dplane;
-          if (cell >= hw) { cell -= hw; ++plane; }
-        }
+          acc += check_term(i, pr);
+        });
         const unsigned long long chk = cache_check_word(acc, value, key_hi, key_lo);
         if (lane == 0) {
           __hip_atomic_store(p.c_value + entry, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1586,16 +1584,13 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
       if (rec >= 0) {
         if (rec_n < q.rec_cap) {
           const size_t at = (size_t)rec * q.rec_cap + rec_n;
-          for (int i = lane; i < A; i += 64) {
-            const int plane = i / hw, cell = i - plane * hw;
-            q.rec_probs[at * A + i] = pol[cell * pp + plane] / sum;
-          }
+          for_each_action(A, hw, lane, [&](int i, int cell, int plane) { q.rec_probs[at * A + i] = pol[cell * pp + plane] / sum; });
           if (lane == 0) { q.rec_value[at] = value; q.rec_digest[2 * at] = dig_hi; q.rec_digest[2 * at + 1] = dig_lo; }
         }
         ++rec_n;
       }
-      // expansion (Explorer.py:162-181): child j = the j-th legal action, prior = masked prob / their float32 np.sum
-      int my_idx[CH];                         // (CH = 1: this game has at most 64 legal actions in a position)
+      // expansion: the j-th legal action and its probability for expand_children
+      int my_idx[CH];                        // (CH = 1: this game has at most 64 legal actions in a position)
       float my_val[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -1608,43 +1603,15 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
         }
         my_val[c] = pr;
       }
-      float total = np_sum_sparse_f32_wave<CH>(p, my_idx, my_val, k);
-      if (total == 0.0f) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) my_val[c] = my_val[c] + 1.0f;
-        total = np_sum_sparse_f32_wave<CH>(p, my_idx, my_val, k);
-      }
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const int j = c * 64 + lane;
-        if (j < k) {
-          SNode n;
-          n.prior = (double)(my_val[c] / total);
-          n.value_sum = 0.0; n.visit = 0; n.child_base = 0; n.n_children = 0; n.action = (uint16_t)my_idx[c];
-          n.to_play = -1; n.prior_f64 = 0; n.terminal = 0; n.pad = 0;
-          nodes[base + j] = n;
-        }
-      }
-      if (lane == 0) {
-        nodes[node].child_base = base;
-        nodes[node].n_children = (uint16_t)k;
-      }
+      expand_children<CH>(p, nodes, node, base, k, lane, my_idx, my_val);
       base += k;
       ++n_exp;
       PSTAMP(6);                                // expansion
     }
-    // backup (Explorer.py:132-135): the same value to every node of the path, root included
+    // backup: levels 0..63 from the lanes' registers, the rest from memory
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (lane < plen && lane < 64) {
-      SNode& n = nodes[my_path];
-      n.visit += 1;
-      n.value_sum = n.value_sum + v;
-    }
-    for (int i = 64 + lane; i < plen; i += 64) {
-      SNode& n = nodes[path[i]];
-      n.visit += 1;
-      n.value_sum = n.value_sum + v;
-    }
+    if (lane < plen && lane < 64) backup_node(nodes[my_path], v);
+    backup_tail(nodes, path, 64, plen, lane, v);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     --sims_left;
     ++n_sim;
@@ -1713,14 +1680,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
   }
   // helper: half of every layer of every network pass of its game, asleep in between
   float* const net = reinterpret_cast<float*>(wb + PERSIST_GAME_BYTES);
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
-  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(q.prog))[lane] : 0u;
-#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
-  const int hw = PHDR(hw), H = PHDR(h), Wd = PHDR(wd), n_ops = PHDR(n_ops);
-  const int in_off = PHDR(in_off), in_cs = PHDR(in_cs);
-  const WaveNetArgs wna{q.prog, n_ops, hw, H, Wd, PHDR(solo_at), PHDR(solo_pol), PHDR(solo_zero_off), PHDR(solo_zero_len)};
-#undef PHDR
+  const WaveNetArgs wna = wave_net_args(q.prog, lane);
   const ScsState& sc = *reinterpret_cast<const ScsState*>(wb + PERSIST_STATE_BYTES);
   uint32_t* const smask = reinterpret_cast<uint32_t*>(wb + 2 * PERSIST_STATE_BYTES);
   int* const sidx = reinterpret_cast<int*>(wb + 2 * PERSIST_STATE_BYTES + PERSIST_MASK_BYTES);
@@ -1738,7 +1698,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
     pair_sync(flags, 1, seq, lane);
     const int job = flags[5], base = flags[7];
     if (job == 0 || k > p.maxc || base + k > p.half_cap) continue;     // (a hit, or the leader is raising the overflow flag)
-    split_planes_half(net, q, hw, in_off, in_cs, lane, 1);
+    split_planes_half(net, q, wna, lane, 1);
     scs_sync<false>();
     pair_sync(flags, 1, seq, lane);
     zero_stage_half(net, q, lane, 1);
@@ -1764,43 +1724,34 @@ __global__ __launch_bounds__(PERSIST_THREADS) void netbench_kernel(PersistArgs q
   unsigned char* const wb = smem + PERSIST_RULES_BYTES + (size_t)slot * q.wave_bytes;
   int* const flags = reinterpret_cast<int*>(wb + PERSIST_GAME_BYTES - PERSIST_FLAG_BYTES);
   float* const net = reinterpret_cast<float*>(wb + PERSIST_GAME_BYTES);
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
-  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(q.prog))[lane] : 0u;
-#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
-  const int hw = PHDR(hw), H = PHDR(h), Wd = PHDR(wd), n_ops = PHDR(n_ops);
-  const WaveNetArgs wna{q.prog, n_ops, hw, H, Wd, PHDR(solo_at), PHDR(solo_pol), PHDR(solo_zero_off), PHDR(solo_zero_len)};
-#undef PHDR
+  const WaveNetArgs wna = wave_net_args(q.prog, lane);
   if (leader)
     for (int i = lane * 4; i < q.net_floats; i += 256) *reinterpret_cast<f32x4*>(net + i) = f32x4{0.f, 0.f, 0.f, 0.f};
   int seq = 0;
   pair_sync(flags, leader ? 0 : 1, seq, lane);
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#ifdef NZ_PERSIST_STAMPS    // diagnostic build: iters bits 24.. = 1 + the phase whose ticks are reported instead of the pass
-  unsigned long long tkn[5] = {0, 0, 0, 0, 0};   // K loops, epilogues, meetings, first operands (HEADSTAMP), layer headers
-  const int phase = (iters >> 24) - 1;
+  unsigned long long* tkn = nullptr;
+#ifdef NZ_PERSIST_STAMPS
+  unsigned long long phase_ticks[5] = {0, 0, 0, 0, 0};   // K loops, epilogues, meetings, first operands (HEADSTAMP), layer headers
+  tkn = phase_ticks;
+#endif
   const int active = (iters >> 16) & 0xff ? (iters >> 16) & 0xff : PERSIST_GAMES, n_it = iters & 0xffff;
   if (slot < active)
     for (int it = 0; it < n_it; ++it) {
       wave_network<HEX>(wna, net, lane, leader ? 0 : 1, flags, seq, tkn);
       pair_sync(flags, leader ? 0 : 1, seq, lane);
     }
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  unsigned long long rep = t1 - t0;
+  unsigned long long rep = __builtin_amdgcn_s_memtime() - t0;
+  bool reports = leader;
+#ifdef NZ_PERSIST_STAMPS    // diagnostic build: iters bits 24.. = 1 + the phase whose ticks are reported instead of the pass
+  const int phase = (iters >> 24) - 1;
   for (int k = 0; k < 5; ++k) if (phase == k) rep = tkn[k];
   if (phase >= 8 && phase < 13) {              // phases 8..12: the HELPER's
-    if (!leader && lane == 0) out[blockIdx.x * PERSIST_GAMES + slot] = tkn[phase - 8] / (unsigned long long)n_it;
-  } else if (leader && lane == 0) out[blockIdx.x * PERSIST_GAMES + slot] = rep / (unsigned long long)n_it;
-#else
-  const int active = (iters >> 16) & 0xff ? (iters >> 16) & 0xff : PERSIST_GAMES, n_it = iters & 0xffff;
-  if (slot < active)
-    for (int it = 0; it < n_it; ++it) {
-      wave_network<HEX>(wna, net, lane, leader ? 0 : 1, flags, seq);
-      pair_sync(flags, leader ? 0 : 1, seq, lane);
-    }
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  if (leader && lane == 0) out[blockIdx.x * PERSIST_GAMES + slot] = (t1 - t0) / (unsigned long long)n_it;
+    rep = tkn[phase - 8];
+    reports = !leader;
+  }
 #endif
+  if (reports && lane == 0) out[blockIdx.x * PERSIST_GAMES + slot] = rep / (unsigned long long)n_it;
 }
 
 __global__ void search_status_kernel(SearchParams p, int32_t* out) {
