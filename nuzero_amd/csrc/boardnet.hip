@@ -65,6 +65,8 @@ struct ConvArgs {
   int32_t hex;           // 0: 3x3 square taps; 1: 7 hexagonal taps (centre + 6 neighbours, odd columns shifted down)
 };
 
+// (the per-layer FP32 kernels' activation: libm's expm1f on purpose -- not epi16_activate's arithmetic, which trades the
+// relative error near zero for speed)
 __device__ __forceinline__ float activate(float v, int act) {
   switch (act) {
     case 1: return v > 0.f ? v : 0.f;
@@ -88,17 +90,12 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs p) {
   const int nt0 = blockIdx.y * NT;
   const int kg0 = p.c0 >> 4, kg1 = p.src1 ? (p.c1 >> 4) : 0, kgt = kg0 + kg1;
 
-  // Taps.  Square: tap = 3 (dy + 1) + (dx + 1).  Hexagonal (hexagdly's addressing: odd columns sit half a cell
-  // lower): 0 N, 1 centre, 2 S (same column), 3 NW, 4 SW (column - 1), 5 NE, 6 SE (column + 1); the upper / lower
-  // neighbour in an adjacent column is row - 1 / row for a cell in an even column, row / row + 1 in an odd one.
-  constexpr int ntaps = HEX ? 7 : 9;
+  constexpr int ntaps = tap_count<HEX>();              // (the taps: fused16_dev.hpp)
   const int cy = cell / p.wd, cx = cell % p.wd;
-  auto tap_dy = [&](int tap) { return HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1; };
-  auto tap_dx = [&](int tap) { return HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1; };
   uint32_t vmask = 0;                                // taps that stay on the board for this cell
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    const int y = cy + tap_dy(tap), x = cx + tap_dx(tap);
+    const int y = cy + tap_dy<HEX>(tap, cx), x = cx + tap_dx<HEX>(tap);
     if (tap < ntaps && (unsigned)y < (unsigned)p.h && (unsigned)x < (unsigned)p.wd) vmask |= 1u << tap;
   }
   int row[MT];
@@ -129,7 +126,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs p) {
 
   f32x4 a[DEPTH][MT], b[DEPTH][NT];
   auto issue = [&](int d) {
-    const int shift = (tap_dy(tap) * p.wd + tap_dx(tap)) * 16;
+    const int shift = (tap_dy<HEX>(tap, cx) * p.wd + tap_dx<HEX>(tap)) * 16;
     const bool second = kg >= kg0;
     const float* src = second ? p.src1 : p.src0;
     const int cs = second ? p.s1 : p.s0;
@@ -228,14 +225,12 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
   if (gbase >= n_groups) return;                       // uniform per workgroup
   const int kq0 = p.c0 >> 5, kq1 = p.src1 ? (p.c1 >> 5) : 0, kqt = kq0 + kq1;      // 32-channel groups
 
-  constexpr int ntaps = HEX ? 7 : 9;
+  constexpr int ntaps = tap_count<HEX>();
   const int cy = cell / p.wd, cx = cell % p.wd;
-  auto tap_dy = [&](int tap) { return HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1; };
-  auto tap_dx = [&](int tap) { return HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1; };
   uint32_t vmask = 0;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    const int y = cy + tap_dy(tap), x = cx + tap_dx(tap);
+    const int y = cy + tap_dy<HEX>(tap, cx), x = cx + tap_dx<HEX>(tap);
     if (tap < ntaps && (unsigned)y < (unsigned)p.h && (unsigned)x < (unsigned)p.wd) vmask |= 1u << tap;
   }
   const int total = __popc(vmask) * kqt;
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
   auto fetch = [&](auto set) {                         // global -> registers for the cursor's step, then advance
     f32x4 (&ra)[8] = ra2[decltype(set)::value];
     u32x4 (&rb)[6] = rb2[decltype(set)::value];
-    const int shift = (tap_dy(tap) * p.wd + tap_dx(tap)) * 16;
+    const int shift = (tap_dy<HEX>(tap, cx) * p.wd + tap_dx<HEX>(tap)) * 16;
     const bool second = kq >= kq0;
     const float* src = (second ? p.src1 : p.src0) + (second ? kq - kq0 : kq) * 32 + my_chunk * 4;
     const int cs = second ? p.s1 : p.s0;
@@ -301,12 +296,12 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     const int ppos = (tid >> 3) + 32 * j;
     const int off = ppos * 64 + (((my_chunk >> 1) ^ ((ppos >> 2) & 3)) << 4) + (my_chunk & 1) * 8;
     const float x0 = ra[j][0], x1 = ra[j][1], x2 = ra[j][2], x3 = ra[j][3];
-    const float r0 = x0 - wide_trunc(x0), r1 = x1 - wide_trunc(x1), r2 = x2 - wide_trunc(x2), r3 = x3 - wide_trunc(x3);
+    const float r0 = x0 - bf16_trunc(x0), r1 = x1 - bf16_trunc(x1), r2 = x2 - bf16_trunc(x2), r3 = x3 - bf16_trunc(x3);
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    *reinterpret_cast<u32x2*>(ab + 0 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{wide_pack_hi16(x0, x1), wide_pack_hi16(x2, x3)};
-    *reinterpret_cast<u32x2*>(ab + 1 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{wide_pack_hi16(r0, r1), wide_pack_hi16(r2, r3)};
+    *reinterpret_cast<u32x2*>(ab + 0 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{pack_hi16(x0, x1), pack_hi16(x2, x3)};
+    *reinterpret_cast<u32x2*>(ab + 1 * (WIDE_GROUPS * 16 * 64) + off) = u32x2{pack_hi16(r0, r1), pack_hi16(r2, r3)};
     *reinterpret_cast<u32x2*>(ab + 2 * (WIDE_GROUPS * 16 * 64) + off) =
-        u32x2{wide_pack_hi16(r0 - wide_trunc(r0), r1 - wide_trunc(r1)), wide_pack_hi16(r2 - wide_trunc(r2), r3 - wide_trunc(r3))};
+        u32x2{pack_hi16(r0 - bf16_trunc(r0), r1 - bf16_trunc(r1)), pack_hi16(r2 - bf16_trunc(r2), r3 - bf16_trunc(r3))};
   };
   auto stage_b = [&](int buf) {
     u32x4 (&rb)[6] = rb2[0];
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
     const bool ahead = fs + 1 < total;
     const bool second = kq >= kq0;
     const char* const fsrc = reinterpret_cast<const char*>((second ? p.src1 : p.src0) + (second ? kq - kq0 : kq) * 32) +
-                             (ptrdiff_t)(tap_dy(tap) * p.wd + tap_dx(tap)) * 16 * (second ? p.s1 : p.s0) * 4;
+                             (ptrdiff_t)(tap_dy<HEX>(tap, cx) * p.wd + tap_dx<HEX>(tap)) * 16 * (second ? p.s1 : p.s0) * 4;
     const u32x4* const fw = wtile + ((size_t)tap * kqt + kq) * (3 * WIDE_NT * 64);
     f32x4 (&fa)[8] = ra2[par];
     u32x4 (&fb)[6] = rb2[par];
@@ -407,10 +402,10 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
         for (int i = 0; i < 4; ++i) sr[i] = ra[j][i];
       }
       if (t == 0 || t == 5 || t == 10)
-        *reinterpret_cast<u32x2*>(ab + (t / 5) * (WIDE_GROUPS * 16 * 64) + soff) = u32x2{wide_pack_hi16(sr[0], sr[1]), wide_pack_hi16(sr[2], sr[3])};
+        *reinterpret_cast<u32x2*>(ab + (t / 5) * (WIDE_GROUPS * 16 * 64) + soff) = u32x2{pack_hi16(sr[0], sr[1]), pack_hi16(sr[2], sr[3])};
       else {
         const int i = (t - 1) % 5;
-        sr[i] = sr[i] - wide_trunc(sr[i]);
+        sr[i] = sr[i] - bf16_trunc(sr[i]);
       }
     };
 #pragma unroll
@@ -420,7 +415,7 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(ConvArgs p) {
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
 #define NZ_WIDE_STEP(B, X, T)                                                  \
-  acc[g][n] = wide_mfma(wf[n][B], X, acc[g][n]);                               \
+  acc[g][n] = mfma_bf16(wf[n][B], X, acc[g][n]);                               \
   {                                                                            \
     /* the 94 staging granules spread evenly over the 168 gaps behind MFMAs 24..191, the 14 loads over the 74 gaps they leave */ \
     constexpr int SG = 94, FG = 14, GAPS = 168, FREE = GAPS - SG;              \
@@ -504,26 +499,26 @@ __global__ __launch_bounds__(64) void finalize_kernel(const float* __restrict__ 
   const int lane = threadIdx.x;
   const int A = planes * hw;
   float mx = -INFINITY;
-  for (int a = lane; a < A; a += 64) {
-    const float v = pol[row_of(n, a % hw, hw) * pp + a / hw];
+  for_each_action(A, hw, lane, 64, [&](int a, int cell, int plane) {
+    const float v = pol[row_of(n, cell, hw) * pp + plane];
     if (logits) logits[(size_t)n * A + a] = v;
     mx = fmaxf(mx, v);
-  }
+  });
   for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
   if (probs) {
     float sum = 0.f;
-    for (int a = lane; a < A; a += 64) {
-      const float e = expf(pol[row_of(n, a % hw, hw) * pp + a / hw] - mx);
+    for_each_action(A, hw, lane, 64, [&](int a, int cell, int plane) {
+      const float e = expf(pol[row_of(n, cell, hw) * pp + plane] - mx);
       probs[(size_t)n * A + a] = e;
       sum += e;
-    }
-    for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
+    });
+    sum = wave_sum(sum);
     for (int a = lane; a < A; a += 64) probs[(size_t)n * A + a] /= sum;
   }
   float s = 0.f;
   for (int c = lane; c < hw; c += 64) s += val[row_of(n, c, hw) * vp];
-  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-  if (lane == 0) value[n] = tanhf(s / (float)hw);
+  s = value_of_plane(s, hw);
+  if (lane == 0) value[n] = s;
 }
 
 
@@ -655,7 +650,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_net_kernel(const FusedPro
 #define FSTAMP(x)
 #endif
   const int rows = np * hw, row_tiles = (rows + 15) >> 4;
-  constexpr int ntaps = HEX ? 7 : 9;
+  constexpr int ntaps = tap_count<HEX>();
   const int q4 = (lane >> 4) * 4;
   const int zoff = prog->zrow_off;
 
@@ -720,8 +715,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_net_kernel(const FusedPro
         on_mask = 0;
 #pragma unroll
         for (int tap = 0; tap < ntaps; ++tap) {
-          const int dy = HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1;
-          const int dx = HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1;
+          const int dy = tap_dy<HEX>(tap, cx), dx = tap_dx<HEX>(tap);
           if (row_ok && (unsigned)(cy + dy) < (unsigned)H && (unsigned)(cx + dx) < (unsigned)Wd) on_mask |= 1u << tap;
           srow[tap] = row + dy * Wd + dx;
         }
@@ -779,39 +773,30 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_net_kernel(const FusedPro
   const float* val = lds + prog->val_off;
   const int vp = prog->val_cs;
   const int A = prog->planes * hw;
-  const int cell0 = lane % hw, plane0 = lane / hw, dcell = 64 % hw, dplane = 64 / hw;
   for (int pl = wave; pl < np; pl += FUSED_WAVES) {
     const size_t n = (size_t)(p0 + pl);
     float* prow = pol + pl * hw * pp;
     float mx = -INFINITY;
-    for (int i = lane, cell = cell0, plane = plane0; i < A; i += 64) {
+    for_each_action(A, hw, lane, 64, [&](int i, int cell, int plane) {
       const float v = prow[cell * pp + plane];
       if (logits) logits[n * A + i] = v;
       mx = fmaxf(mx, v);
-      cell += dcell; plane += dplane;
-      if (cell >= hw) { cell -= hw; ++plane; }
-    }
+    });
     for (int w = 32; w; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
     if (probs) {
       float sum = 0.f;
-      for (int i = lane, cell = cell0, plane = plane0; i < A; i += 64) {
+      for_each_action(A, hw, lane, 64, [&](int, int cell, int plane) {
         const float e = expf(prow[cell * pp + plane] - mx);
         prow[cell * pp + plane] = e;
         sum += e;
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
-      for (int w = 32; w; w >>= 1) sum += __shfl_xor(sum, w);
-      for (int i = lane, cell = cell0, plane = plane0; i < A; i += 64) {
-        probs[n * A + i] = prow[cell * pp + plane] / sum;
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
+      });
+      sum = wave_sum(sum);
+      for_each_action(A, hw, lane, 64, [&](int i, int cell, int plane) { probs[n * A + i] = prow[cell * pp + plane] / sum; });
     }
     float sv = 0.f;
     for (int c = lane; c < hw; c += 64) sv += val[(pl * hw + c) * vp];
-    for (int w = 32; w; w >>= 1) sv += __shfl_xor(sv, w);
-    if (lane == 0) value[n] = tanhf(sv / (float)hw);
+    sv = value_of_plane(sv, hw);
+    if (lane == 0) value[n] = sv;
   }
 #ifdef NZ_FUSED_STAMPS
   FSTAMP(tk_fin);
@@ -911,26 +896,19 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // The program's header and its first two layer descriptors come in three VECTOR loads issued together (lane i holds
-  // dword i, v_readlane makes the scalars): as scalar loads they are a chain of dependent round trips to memory, a
-  // few microseconds at the start of every launch.
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4), OP_DWORDS = (int)(sizeof(Fused16Op) / 4);
-  static_assert(HDR_DWORDS <= 64 && sizeof(Fused16Op) % 4 == 0 && OP_DWORDS <= 64, "one dword per lane");
-  const gptr1u prog_words = (gptr1u)reinterpret_cast<const uint32_t*>(prog);
-  const uint32_t hdr_v = lane < HDR_DWORDS ? prog_words[lane] : 0u;
-  const uint32_t op0_v = lane < OP_DWORDS ? prog_words[HDR_DWORDS + lane] : 0u;
-  const uint32_t op1_v = lane < OP_DWORDS ? prog_words[HDR_DWORDS + OP_DWORDS + lane] : 0u;
-#define HDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
+  // The program's header and its first two layer descriptors come in three vector loads issued together (as scalar
+  // loads: a few microseconds of dependent round trips at the start of every launch)
+  const uint32_t hdr_v = fused16_header_dword(prog, lane);
+  const uint32_t op0_v = fused16_op_dword(prog, 0, lane), op1_v = fused16_op_dword(prog, 1, lane);
   const int n_pos = n_dev ? *n_dev : n_host;
   const int P = (n_pos + (int)gridDim.x - 1) / (int)gridDim.x;
   const int p0 = blockIdx.x * P;
   if (p0 >= n_pos) return;                                  // uniform per workgroup
   const int np = min(P, n_pos - p0);
-  const int hw = HDR(hw), H = HDR(h), Wd = HDR(wd), n_ops = HDR(n_ops);
-  const int h_in_off = HDR(in_off), h_in_cs = HDR(in_cs), h_in_ps = HDR(in_ps), zrow_index = HDR(zrow_index);   // (every buffer's row of zeros)
+  const int hw = FUSED16_HDR(hdr_v, hw), H = FUSED16_HDR(hdr_v, h), Wd = FUSED16_HDR(hdr_v, wd), n_ops = FUSED16_HDR(hdr_v, n_ops);
+  const int h_in_off = FUSED16_HDR(hdr_v, in_off), h_in_cs = FUSED16_HDR(hdr_v, in_cs), h_in_ps = FUSED16_HDR(hdr_v, in_ps), zrow_index = FUSED16_HDR(hdr_v, zrow_index);   // (every buffer's row of zeros)
   const int rows = np * hw, row_tiles = (rows + 15) >> 4;
-  constexpr int ntaps = HEX ? 7 : 9;
+  constexpr int ntaps = tap_count<HEX>();
   const int kq = lane >> 4;
 #ifdef NZ_FUSED_STAMPS
   unsigned long long tk_in = 0, tk_job[32], tk_bar[32], tk_k[32], tk_fin = 0, ts = __builtin_amdgcn_s_memtime();
@@ -942,8 +920,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
 #endif
   // K groups reach past a narrow layer's channels and row tiles past the last row (zero weights, discarded rows): what
   // they read must be numbers, so everything starts as zeros
-  for (int i = HDR(clear_from) + tid * 4, end = HDR(lds_floats); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int i = HDR(clear2_from) + tid * 4, end = HDR(clear2_to); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = FUSED16_HDR(hdr_v, clear_from) + tid * 4, end = FUSED16_HDR(hdr_v, lds_floats); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = FUSED16_HDR(hdr_v, clear2_from) + tid * 4, end = FUSED16_HDR(hdr_v, clear2_to); i < end; i += FUSED_THREADS * 4) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int i = tid; i < 3 * h_in_cs; i += FUSED_THREADS)     // the input's row of zeros
     lds[h_in_off + (i / h_in_cs) * h_in_ps + zrow_index * h_in_cs + i % h_in_cs] = 0.f;
   // (no barrier here: the input rows written next are none of the floats cleared above; the barrier after them covers both)
@@ -965,7 +943,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       const size_t grow = ((size_t)(n >> 4) * hw + cell) * 16 + (n & 15);
       const float* src = in_rows + grow * in_channels + c8 * 8;
       u32x4 q0 = u32x4{0u, 0u, 0u, 0u}, q1 = q0, q2 = q0;
-      if (r < rows && c8 < chunks) wide_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
+      if (r < rows && c8 < chunks) split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
       float* d = lds + h_in_off + r * cs + ((c8 ^ ((r >> 2) & 3)) << 2);
       *reinterpret_cast<u32x4*>(d) = q0;
       *reinterpret_cast<u32x4*>(d + ps) = q1;
@@ -975,17 +953,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
 #ifdef NZ_FUSED_STAMPS
   unsigned long long tk_split = 0; FSTAMP(tk_split);
 #endif
-  const int wbuf_off0 = HDR(wbuf_off[0]), wbuf_off1 = HDR(wbuf_off[1]);
-  Fused16Op d0, d1;
-  {
-    uint32_t words[OP_DWORDS];
-#pragma unroll
-    for (int i = 0; i < OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(op0_v, i);
-    __builtin_memcpy(&d0, words, sizeof(Fused16Op));
-#pragma unroll
-    for (int i = 0; i < OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(op1_v, i);
-    __builtin_memcpy(&d1, words, sizeof(Fused16Op));
-  }
+  const int wbuf_off0 = FUSED16_HDR(hdr_v, wbuf_off[0]), wbuf_off1 = FUSED16_HDR(hdr_v, wbuf_off[1]);
+  Fused16Op d0 = fused16_unpack(op0_v), d1 = fused16_unpack(op1_v);
   if (n_ops > 0 && d0.w_lds) {
     u32x4 wreg[FUSED16_WREGS];
     fetch_weights16(d0, wreg, tid);
@@ -995,22 +964,15 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   FSTAMP(tk_in);
 
   int rt_cached = -1, srow[ntaps];
-  // A layer's descriptor is fetched two layers ahead, and with VECTOR loads (lane i holds dword i; v_readlane makes
-  // the scalars a layer later): scalar loads come back out of order, so the first wait for an LDS read behind one waits
-  // for memory too -- a microsecond per layer.
-  const int zero_at_op = HDR(zero_at_op), n_zero = HDR(n_zero), zero_len = HDR(zero_len);
-  const gptr1u ops_words = (gptr1u)reinterpret_cast<const uint32_t*>(prog->ops);
-  uint32_t dvec = (n_ops > 2 && lane < OP_DWORDS) ? ops_words[2 * OP_DWORDS + lane] : 0u;
+  // A layer's descriptor is fetched two layers ahead (a vector load; v_readlane makes the scalars a layer later): behind
+  // scalar loads the first wait for an LDS read waits for memory too -- a microsecond per layer.
+  const int zero_at_op = FUSED16_HDR(hdr_v, zero_at_op), n_zero = FUSED16_HDR(hdr_v, n_zero), zero_len = FUSED16_HDR(hdr_v, zero_len);
+  uint32_t dvec = n_ops > 2 ? fused16_op_dword(prog, 2, lane) : 0u;
   for (int o = 0; o < n_ops; ++o) {
     const Fused16Op op = d0, next = d1;       // both read from memory at least a layer ago
     d0 = d1;
-    if (o + 2 < n_ops) {
-      uint32_t words[OP_DWORDS];
-#pragma unroll
-      for (int i = 0; i < OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(dvec, i);
-      __builtin_memcpy(&d1, words, sizeof(Fused16Op));
-    }
-    if (o + 3 < n_ops && lane < OP_DWORDS) dvec = ops_words[(o + 3) * OP_DWORDS + lane];
+    if (o + 2 < n_ops) d1 = fused16_unpack(dvec);
+    if (o + 3 < n_ops) dvec = fused16_op_dword(prog, o + 3, lane);
 #ifdef NZ_FUSED_STAMPS
     asm volatile("" :: "s"(d1.off0), "s"(d1.kg0));
     const unsigned long long t_top = __builtin_amdgcn_s_memtime();
@@ -1043,8 +1005,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
         const int cy = cell / Wd, cx = cell - cy * Wd;
 #pragma unroll
         for (int tap = 0; tap < ntaps; ++tap) {
-          const int dy = HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1;
-          const int dx = HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1;
+          const int dy = tap_dy<HEX>(tap, cx), dx = tap_dx<HEX>(tap);
           const bool on = row_ok && (unsigned)(cy + dy) < (unsigned)H && (unsigned)(cx + dx) < (unsigned)Wd;
           srow[tap] = on ? row + dy * Wd + dx : zrow_index;
         }
@@ -1055,6 +1016,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
       const float* wl = wbuf + (size_t)ct * op.w_chunks * 4 + lane * 4;            // LDS copy of the column tile
       const uint32_t* wg = op.w + (size_t)ct * op.w_chunks * 4 + lane * 4;         // packed stream in L2
+      // (spelled out, not for_kgroups: through the lambda the square kernel spills a second vector register)
       if (op.w_lds && kgt == 1) conv16_job<ntaps, 1, true>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
       else if (op.w_lds && kgt == 2) conv16_job<ntaps, 2, true>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
       else if (kgt == 1) conv16_job<ntaps, 1, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
@@ -1066,51 +1028,28 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       asm volatile("" :: "v"(acc));
       if (o < 32) tk_k[o] += __builtin_amdgcn_s_memtime() - j0;
 #endif
-      // epilogue: this lane's row, its four channels; the four values go through each step TOGETHER (one wave-uniform
-      // switch, then four independent chains the scheduler interleaves)
+      // epilogue: this lane's row, its four channels (the values: fused16_dev.hpp)
       const int orow = rt * 16 + (lane & 15), c0 = ct * 16 + (lane >> 4) * 4;
       if (orow < rows) {
         const int chunk = (((c0 >> 3) ^ ((orow >> 2) & 3)) << 2) + ((c0 & 7) >> 1);     // float offset of the 8 bytes in the row
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = acc[r];
-        if (op.offr >= 0) {                                 // the residual's pieces add up to the float32 it was split from
+        if (op.offr >= 0) {
           const float* rp = lds + op.offr + orow * op.csr + chunk;
           const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + op.psr),
                       q2 = *reinterpret_cast<const uint2*>(rp + 2 * op.psr);
-          auto lo = [](uint32_t w) { return __builtin_bit_cast(float, w << 16); };
-          auto hi = [](uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); };
-          v[0] += (lo(q0.x) + lo(q1.x)) + lo(q2.x);
-          v[1] += (hi(q0.x) + hi(q1.x)) + hi(q2.x);
-          v[2] += (lo(q0.y) + lo(q1.y)) + lo(q2.y);
-          v[3] += (hi(q0.y) + hi(q1.y)) + hi(q2.y);
+          epi16_add_residual(v, q0, q1, q2);
         }
-        switch (op.act) {
-          case 1:
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
-            break;
-          case 2:
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
-            break;
-          case 3:
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : fast_expm1(v[r]);
-            break;
-          default: break;
-        }
+        epi16_activate<4>(v, op.act);
         if (op.psd == 0) {                                  // float32 rows (logits, value plane): 16 bytes
           *reinterpret_cast<f32x4*>(lds + op.offd + orow * op.csd + c0) = f32x4{v[0], v[1], v[2], v[3]};
         } else {
-          uint16_t h3[4][3];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) split3_bits(v[r], h3[r]);
+          uint2 q[3];
+          epi16_split(v, q);
           float* dp = lds + op.offd + orow * op.csd + chunk;
 #pragma unroll
-          for (int piece = 0; piece < 3; ++piece)
-            *reinterpret_cast<uint2*>(dp + piece * op.psd) =
-                uint2{(uint32_t)h3[0][piece] | ((uint32_t)h3[1][piece] << 16), (uint32_t)h3[2][piece] | ((uint32_t)h3[3][piece] << 16)};
+          for (int piece = 0; piece < 3; ++piece) *reinterpret_cast<uint2*>(dp + piece * op.psd) = q[piece];
         }
       }
     }
@@ -1133,15 +1072,14 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   // softmax over ALL logits and value = tanh(mean) (the two outputs are float32 rows).  A workgroup has few positions and
   // sixteen wavefronts: WPP wavefronts share a position's logits; their partial maxima and sums meet in LDS (the first
   // floats of weight buffer 1, which nothing reads after the last layer's barrier).
-  float* pol = lds + HDR(pol_off);
-  const int pp = HDR(pol_cs);
-  const float* val = lds + HDR(val_off);
-  const int vp = HDR(val_cs);
-  const int A = HDR(planes) * hw;
-  const int WPP = np <= 4 ? 4 : (np <= 8 ? 2 : 1), groups = FUSED_WAVES / WPP;
+  float* pol = lds + FUSED16_HDR(hdr_v, pol_off);
+  const int pp = FUSED16_HDR(hdr_v, pol_cs);
+  const float* val = lds + FUSED16_HDR(hdr_v, val_off);
+  const int vp = FUSED16_HDR(hdr_v, val_cs);
+  const int A = FUSED16_HDR(hdr_v, planes) * hw;
+  const int WPP = softmax_ways(np), groups = FUSED_WAVES / WPP;       // (the sum's order: fused16_dev.hpp)
   const int group = wave / WPP, sub = wave - group * WPP, step = 64 * WPP;
   const int i0 = sub * 64 + lane;
-  const int cell0 = i0 % hw, plane0 = i0 / hw, dcell = step % hw, dplane = step / hw;
   float* red = lds + h_in_off;                             // [2][FUSED_WAVES]
   for (int base = 0; base < np; base += groups) {           // (the same trip count for every wavefront: barriers inside)
     const int pl = base + group;
@@ -1150,13 +1088,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
     float* prow = pol + pl * hw * pp;
     float mx = -INFINITY;
     if (on)
-      for (int i = i0, cell = cell0, plane = plane0; i < A; i += step) {
+      for_each_action(A, hw, i0, step, [&](int i, int cell, int plane) {
         const float v = prow[cell * pp + plane];
         if (logits) logits[n * A + i] = v;
         mx = fmaxf(mx, v);
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
+      });
     if (!probs) continue;                                   // (uniform)
     for (int w = 32; w; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
     if (lane == 0) red[wave] = mx;
@@ -1164,31 +1100,24 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
     for (int j = 0; j < WPP; ++j) mx = fmaxf(mx, red[group * WPP + j]);
     float sum = 0.f;
     if (on)
-      for (int i = i0, cell = cell0, plane = plane0; i < A; i += step) {
+      for_each_action(A, hw, i0, step, [&](int, int cell, int plane) {
         const float e = expf(prow[cell * pp + plane] - mx);
         prow[cell * pp + plane] = e;
         sum += e;
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
-    for (int w = 32; w; w >>= 1) sum += __shfl_xor(sum, w);
+      });
+    sum = wave_sum(sum);
     if (lane == 0) red[FUSED_WAVES + wave] = sum;
     __syncthreads();
     sum = 0.f;
     for (int j = 0; j < WPP; ++j) sum += red[FUSED_WAVES + group * WPP + j];
-    if (on)
-      for (int i = i0, cell = cell0, plane = plane0; i < A; i += step) {
-        probs[n * A + i] = prow[cell * pp + plane] / sum;
-        cell += dcell; plane += dplane;
-        if (cell >= hw) { cell -= hw; ++plane; }
-      }
+    if (on) for_each_action(A, hw, i0, step, [&](int i, int cell, int plane) { probs[n * A + i] = prow[cell * pp + plane] / sum; });
     if (base + groups < np) __syncthreads();                // `red` is written again
   }
   for (int pl = wave; pl < np; pl += FUSED_WAVES) {
     float sv = 0.f;
     for (int c = lane; c < hw; c += 64) sv += val[(pl * hw + c) * vp];
-    for (int w = 32; w; w >>= 1) sv += __shfl_xor(sv, w);
-    if (lane == 0) value[(size_t)(p0 + pl)] = tanhf(sv / (float)hw);
+    sv = value_of_plane(sv, hw);
+    if (lane == 0) value[(size_t)(p0 + pl)] = sv;
   }
 #ifdef NZ_FUSED_STAMPS
   FSTAMP(tk_fin);

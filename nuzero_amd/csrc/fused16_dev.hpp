@@ -1,42 +1,95 @@
-// Device pieces of the one-launch BF16 network (boardnet.hip fused16_net_kernel) that the persistent SCS self-play
-// kernel (scs_search.hip) runs per wavefront too: the split-bf16 arithmetic -- every float32 the exact sum of three bf16
-// pieces, six of the nine piece products on v_mfma_f32_16x16x32_bf16 with float32 accumulation --
-// and the layer program the host resolves (every LDS offset and stride).
+// What the interpreters of a Fused16Program share.  Two kernels run one program: fused16_net_kernel (boardnet.hip), a
+// leaf batch on sixteen wavefronts per workgroup, and wave_network (scs_search.hip), one position on the pair of
+// wavefronts that owns a game of the persistent SCS self-play kernel.  The two search routes play the same games bit
+// for bit only while both do the same float32 operations in the same order, so everything that decides a float is
+// written here, once: the split-bf16 arithmetic -- every float32 the exact sum of three bf16 pieces, six of the nine
+// piece products on v_mfma_f32_16x16x32_bf16 with float32 accumulation --, the conv taps, the
+// layer epilogue's values, the order of the softmax sum, the value's tanh(mean), and the layer program the host
+// resolves (every LDS offset and stride) with the way its descriptors reach scalar registers.  Each kernel keeps its
+// own schedule, LDS layout, addresses and store predicates.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
+
+#include "bf16_split.hpp"
 
 namespace nz {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t wide_pack_hi16(float x0, float x1) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, x1), __builtin_bit_cast(uint32_t, x0), 0x07060302u);
+// ---- conv taps ------------------------------------------------------------------------------------------------------------
+// Square: tap = 3 (dy + 1) + (dx + 1).  Hexagonal (hexagdly's addressing: odd columns sit half a cell lower): 0 N,
+// 1 centre, 2 S (same column), 3 NW, 4 SW (column - 1), 5 NE, 6 SE (column + 1); the upper / lower neighbour in an
+// adjacent column is row - 1 / row for a cell in an even column, row / row + 1 in an odd one.  `cx`: the cell's column.
+template <bool HEX>
+__host__ __device__ constexpr int tap_count() { return HEX ? 7 : 9; }
+template <bool HEX>
+__host__ __device__ constexpr int tap_dy(int tap, int cx) {
+  return HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1;
 }
-__device__ __forceinline__ float wide_trunc(float x) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u);
+template <bool HEX>
+__host__ __device__ constexpr int tap_dx(int tap) { return HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1; }
+
+constexpr bool square_taps_ok() {          // the nine taps are {-1, 0, 1}^2 in the order 3 (dy + 1) + (dx + 1), in every column
+  for (int cx = 0; cx < 2; ++cx)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int tap = 3 * (dy + 1) + (dx + 1);
+        if (tap_dy<false>(tap, cx) != dy || tap_dx<false>(tap) != dx) return false;
+      }
+  return true;
 }
+constexpr bool hex_taps_distinct(int cx) {   // seven different offsets, the centre at tap 1
+  for (int a = 0; a < 7; ++a)
+    for (int b = a + 1; b < 7; ++b)
+      if (tap_dy<true>(a, cx) == tap_dy<true>(b, cx) && tap_dx<true>(a) == tap_dx<true>(b)) return false;
+  return tap_dy<true>(1, cx) == 0 && tap_dx<true>(1) == 0;
+}
+constexpr bool hex_taps_rule(int cx) {       // the comment above, for a cell in column cx
+  const int up = (cx & 1) ? 0 : -1;          // the upper neighbour's row offset in an adjacent column; the lower one's is up + 1
+  return tap_dy<true>(0, cx) == -1 && tap_dx<true>(0) == 0 && tap_dy<true>(2, cx) == 1 && tap_dx<true>(2) == 0 &&
+         tap_dy<true>(3, cx) == up && tap_dx<true>(3) == -1 && tap_dy<true>(4, cx) == up + 1 && tap_dx<true>(4) == -1 &&
+         tap_dy<true>(5, cx) == up && tap_dx<true>(5) == 1 && tap_dy<true>(6, cx) == up + 1 && tap_dx<true>(6) == 1;
+}
+static_assert(tap_count<false>() == 9 && square_taps_ok(), "square taps");
+static_assert(tap_count<true>() == 7 && hex_taps_distinct(0) && hex_taps_distinct(1), "hexagonal taps: seven cells, centre at tap 1");
+static_assert(hex_taps_rule(0) && hex_taps_rule(1) && hex_taps_rule(2) && hex_taps_rule(3), "hexagdly's even / odd column rule");
+
+// ---- split-bf16 arithmetic ------------------------------------------------------------------------------------------------
 // 8 float32 -> three bf16 pieces (exact: 8 + 8 + 8 significant bits)
-__device__ __forceinline__ void wide_split8(const f32x4& lo, const f32x4& hi, u32x4& p0, u32x4& p1, u32x4& p2) {
+__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, u32x4& p0, u32x4& p1, u32x4& p2) {
   const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   uint32_t a[4], b[4], c[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float x0 = v[2 * j], x1 = v[2 * j + 1];
-    a[j] = wide_pack_hi16(x0, x1);
-    const float r0 = x0 - wide_trunc(x0), r1 = x1 - wide_trunc(x1);
-    b[j] = wide_pack_hi16(r0, r1);
-    c[j] = wide_pack_hi16(r0 - wide_trunc(r0), r1 - wide_trunc(r1));
+    a[j] = pack_hi16(x0, x1);
+    const float r0 = x0 - bf16_trunc(x0), r1 = x1 - bf16_trunc(x1);
+    b[j] = pack_hi16(r0, r1);
+    c[j] = pack_hi16(r0 - bf16_trunc(r0), r1 - bf16_trunc(r1));
   }
   p0 = u32x4{a[0], a[1], a[2], a[3]};
   p1 = u32x4{b[0], b[1], b[2], b[3]};
   p2 = u32x4{c[0], c[1], c[2], c[3]};
 }
-__device__ __forceinline__ f32x4 wide_mfma(const u32x4& w, const u32x4& x, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
+// one K step (32 channels of one tap): the six piece products, small terms first (net_dev.hpp pair_mfma)
+// The weights go in as the MFMA's first operand, so the output tile comes out transposed: lane l holds ROW l & 15 and the
+// four consecutive channels 4 (l >> 4) .. + 3 -- one address, one bounds check and three 8-byte stores per lane in the
+// epilogue where the other orientation (a column and four rows per lane) needs four of each and twelve 2-byte stores.
+__device__ __forceinline__ void step16(f32x4& acc, const u32x4 (&a)[3], const u32x4 (&b)[3]) {
+  acc = mfma_bf16(b[1], a[1], acc);
+  acc = mfma_bf16(b[0], a[2], acc);
+  acc = mfma_bf16(b[2], a[0], acc);
+  acc = mfma_bf16(b[0], a[1], acc);
+  acc = mfma_bf16(b[1], a[0], acc);
+  acc = mfma_bf16(b[0], a[0], acc);
 }
+// exp(x) - 1 for x <= 0 to an absolute error of ~1e-7 (v_exp_f32; libm's expm1f keeps the RELATIVE error small near zero,
+// thirty instructions the activations' 1e-5 tolerance has no use for)
+__device__ __forceinline__ float fast_expm1(float x) { return __expf(x) - 1.0f; }
 
+// ---- the program ----------------------------------------------------------------------------------------------------------
 constexpr int FUSED_MAX_OPS = 176;
 struct Fused16Op {
   const uint32_t* w;                       // [col tile][tap][32-channel group][piece][lane][4 dwords = 8 bf16]
@@ -63,32 +116,120 @@ struct Fused16Program {
   int32_t solo_at, solo_pol, solo_zero_off, solo_zero_len;
   Fused16Op ops[FUSED_MAX_OPS];
 };
-// one K step (32 channels of one tap): the six piece products, small terms first (net_dev.hpp pair_mfma)
-// The weights go in as the MFMA's first operand, so the output tile comes out transposed: lane l holds ROW l & 15 and the
-// four consecutive channels 4 (l >> 4) .. + 3 -- one address, one bounds check and three 8-byte stores per lane in the
-// epilogue where the other orientation (a column and four rows per lane) needs four of each and twelve 2-byte stores.
-__device__ __forceinline__ void step16(f32x4& acc, const u32x4 (&a)[3], const u32x4 (&b)[3]) {
-  acc = wide_mfma(b[1], a[1], acc);
-  acc = wide_mfma(b[0], a[2], acc);
-  acc = wide_mfma(b[2], a[0], acc);
-  acc = wide_mfma(b[0], a[1], acc);
-  acc = wide_mfma(b[1], a[0], acc);
-  acc = wide_mfma(b[0], a[0], acc);
+
+// The header and the layer descriptors reach the scalar registers through VECTOR loads: lane i loads dword i, v_readlane
+// makes the scalars when they are wanted.  (As scalar loads they are chains of dependent round trips to memory that come
+// back out of order: the first wait for an LDS read behind one waits for memory too.)
+constexpr int FUSED16_HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4), FUSED16_OP_DWORDS = (int)(sizeof(Fused16Op) / 4);
+static_assert(FUSED16_HDR_DWORDS <= 64 && sizeof(Fused16Op) % 4 == 0 && FUSED16_OP_DWORDS <= 64, "one dword per lane");
+typedef const __attribute__((address_space(1))) uint32_t* fused16_words;       // global (not flat) loads
+// this lane's dword of the header / of layer i's descriptor; zero in the lanes past its end
+__device__ __forceinline__ uint32_t fused16_header_dword(const Fused16Program* prog, int lane) {
+  return lane < FUSED16_HDR_DWORDS ? ((fused16_words)reinterpret_cast<const uint32_t*>(prog))[lane] : 0u;
 }
-// exp(x) - 1 for x <= 0 to an absolute error of ~1e-7 (v_exp_f32; libm's expm1f keeps the RELATIVE error small near zero,
-// thirty instructions the activations' 1e-5 tolerance has no use for)
-__device__ __forceinline__ float fast_expm1(float x) { return __expf(x) - 1.0f; }
-// exact three-way split of one value; piece i as the bf16 bit pattern
-__device__ __forceinline__ void split3_bits(float v, uint16_t (&h)[3]) {
-  float r = v;
+__device__ __forceinline__ uint32_t fused16_op_dword(const Fused16Program* prog, int i, int lane) {
+  return lane < FUSED16_OP_DWORDS ? ((fused16_words)reinterpret_cast<const uint32_t*>(prog->ops))[i * FUSED16_OP_DWORDS + lane] : 0u;
+}
+// a descriptor out of the register fused16_op_dword filled
+__device__ __forceinline__ Fused16Op fused16_unpack(uint32_t v) {
+  uint32_t words[FUSED16_OP_DWORDS];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const uint32_t bits = __builtin_bit_cast(uint32_t, r) & 0xFFFF0000u;
-    h[i] = (uint16_t)(bits >> 16);
-    r = r - __builtin_bit_cast(float, bits);
+  for (int i = 0; i < FUSED16_OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(v, i);
+  Fused16Op op;
+  __builtin_memcpy(&op, words, sizeof(Fused16Op));
+  return op;
+}
+// a header field out of the register fused16_header_dword filled
+#define FUSED16_HDR(hdr_v, field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(::nz::Fused16Program, field) / 4)))
+
+// A layer's K loop is straight-line code for its number of 32-channel K groups: f(std::integral_constant<int, kgt>),
+// kgt = 1 .. 4 (the planners admit no more)
+template <typename F>
+__device__ __forceinline__ void for_kgroups(int kgt, F&& f) {
+  if (kgt == 1) f(std::integral_constant<int, 1>{});
+  else if (kgt == 2) f(std::integral_constant<int, 2>{});
+  else if (kgt == 3) f(std::integral_constant<int, 3>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+// ---- the layer epilogue's values: residual, activation, split ---------------------------------------------------------------
+// A lane holds four consecutive channels of one row; `q`: the residual's three pieces of those channels, 8 bytes each.
+// The pieces add up to the float32 they were split from.
+__device__ __forceinline__ void epi16_add_residual(float* v, const uint2& q0, const uint2& q1, const uint2& q2) {
+  v[0] += (bf16_lo(q0.x) + bf16_lo(q1.x)) + bf16_lo(q2.x);
+  v[1] += (bf16_hi(q0.x) + bf16_hi(q1.x)) + bf16_hi(q2.x);
+  v[2] += (bf16_lo(q0.y) + bf16_lo(q1.y)) + bf16_lo(q2.y);
+  v[3] += (bf16_hi(q0.y) + bf16_hi(q1.y)) + bf16_hi(q2.y);
+}
+// Fused16Op::act (0 none, 1 relu, 2 tanh, 3 elu) of N values: they go through the step TOGETHER (one wave-uniform switch,
+// then N independent chains the scheduler interleaves)
+template <int N>
+__device__ __forceinline__ void epi16_activate(float* v, int act) {
+  switch (act) {
+    case 1:
+#pragma unroll
+      for (int r = 0; r < N; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+      break;
+    case 2:
+#pragma unroll
+      for (int r = 0; r < N; ++r) v[r] = tanhf(v[r]);
+      break;
+    case 3:
+#pragma unroll
+      for (int r = 0; r < N; ++r) v[r] = v[r] > 0.f ? v[r] : fast_expm1(v[r]);
+      break;
+    default: break;
   }
 }
-__device__ __forceinline__ float bf16_bits_to_float(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
+// exact three-way split of the four values: q[piece] = the 8 bytes of that piece (v_perm packs two upper halves)
+__device__ __forceinline__ void epi16_split(const float* v, uint2 (&q)[3]) {
+  float r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = v[i];
+#pragma unroll
+  for (int piece = 0; piece < 3; ++piece) {
+    q[piece] = uint2{pack_hi16(r[0], r[1]), pack_hi16(r[2], r[3])};
+    if (piece < 2) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = r[i] - bf16_trunc(r[i]);
+    }
+  }
+}
 
+// ---- the two outputs ------------------------------------------------------------------------------------------------------
+// Lanes walk the actions i = first, first + stride, ... < A as f(i, cell, plane, j) -- action i = plane * hw + cell, the
+// policy planes' layout -- without a division per entry; j = the entry's place in its block of BLOCK entries (a constant
+// after unrolling, for callers that keep a register per place).
+template <int BLOCK, typename F>
+__device__ __forceinline__ void for_each_action_blocked(int A, int hw, int first, int stride, F f) {
+  int cell = first % hw, plane = first / hw;
+  const int dcell = stride % hw, dplane = stride / hw;
+  for (int i0 = first; i0 < A; i0 += stride * BLOCK) {
+#pragma unroll
+    for (int j = 0; j < BLOCK; ++j) {
+      const int i = i0 + stride * j;
+      if (i < A) f(i, cell, plane, j);
+      cell += dcell; plane += dplane;
+      if (cell >= hw) { cell -= hw; ++plane; }
+    }
+  }
+}
+template <typename F>
+__device__ __forceinline__ void for_each_action(int A, int hw, int first, int stride, F f) {
+  for_each_action_blocked<1>(A, hw, first, stride, [&](int i, int cell, int plane, int) { f(i, cell, plane); });
+}
+// The order of the softmax sum over a position's exp(logit - max): each of `ways` partial sums takes every (64 x ways)-th
+// entry per lane (partial sum s of lane l: entries 64 s + l, + 64 ways, ...), one butterfly over the wavefront per partial
+// sum, the partial sums added in index order.  fused16_net_kernel gives a position `ways` of its sixteen wavefronts, by
+// the positions its workgroup holds; persist_leader forms the same partial sums on one wavefront.
+__host__ __device__ constexpr int softmax_ways(int positions_per_workgroup) {
+  return positions_per_workgroup <= 4 ? 4 : (positions_per_workgroup <= 8 ? 2 : 1);
+}
+__device__ __forceinline__ float wave_sum(float x) {
+  for (int w = 32; w; w >>= 1) x += __shfl_xor(x, w, 64);
+  return x;
+}
+// value = tanh(mean of the value plane) (blocks.py:82-84); `lane_sum`: this lane's cells c = lane, lane + 64, ... added up
+__device__ __forceinline__ float value_of_plane(float lane_sum, int hw) { return tanhf(wave_sum(lane_sum) / (float)hw); }
 
 }  // namespace nz

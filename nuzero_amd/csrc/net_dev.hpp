@@ -51,13 +51,11 @@
 // strip[piece][cell][pos][16 ch] (16-byte slot index XOR-ed with (pos >> 2) & 1) for the one head tile that finds no
 // room in them: the two heads' first convs run as one stage, and their 48 + 32 output channels exceed one buffer's 64.
 #pragma once
+#include "bf16_split.hpp"
 #include "engine.h"
 
 namespace nz {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int POS = 16;            // positions per workgroup (MFMA N)
@@ -222,27 +220,16 @@ struct Operands {
   }
 };
 
-// ---- exact three-way split of float32 into bf16 pieces -------------------------------------------
-__device__ __forceinline__ uint32_t trunc_bf16(float x) { return __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u; }
-// (x0, x1) -> the two upper halves in one register: bf16(x0) | bf16(x1) << 16 (truncating)
-__device__ __forceinline__ uint32_t pack_hi16(float x0, float x1) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, x1), __builtin_bit_cast(uint32_t, x0), 0x07060302u);
-}
+// ---- exact three-way split of float32 into bf16 pieces (the primitives: bf16_split.hpp) ----------------
 // x = p0 + p1 + p2 exactly, 8 significant bits each
 __device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
   p0 = pack_hi16(x0, x1);
-  const float r0 = x0 - __builtin_bit_cast(float, trunc_bf16(x0));
-  const float r1 = x1 - __builtin_bit_cast(float, trunc_bf16(x1));
+  const float r0 = x0 - bf16_trunc(x0);
+  const float r1 = x1 - bf16_trunc(x1);
   p1 = pack_hi16(r0, r1);
-  const float s0 = r0 - __builtin_bit_cast(float, trunc_bf16(r0));
-  const float s1 = r1 - __builtin_bit_cast(float, trunc_bf16(r1));
+  const float s0 = r0 - bf16_trunc(r0);
+  const float s1 = r1 - bf16_trunc(r1);
   p2 = pack_hi16(s0, s1);
-}
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
-
-__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& w, const u32x4& x, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
 }
 // The K loop's MFMAs carry slots: slot g follows the g-th MFMA of a K group (in issue order) and runs whatever the
 // epilogue scheduler `e` has placed there (ProgEpi below; NoEpi: nothing, the chain is as before).
@@ -520,7 +507,7 @@ __device__ __forceinline__ float epi_act(float x) {
   if constexpr (ACT == 3) x = x > 0.0f ? x : expm1f(x);      // nn.ELU(), alpha = 1
   return x;
 }
-__device__ __forceinline__ float epi_rem(float x) { return x - __builtin_bit_cast(float, trunc_bf16(x)); }
+__device__ __forceinline__ float epi_rem(float x) { return x - bf16_trunc(x); }
 // this lane's byte offset inside cell 0 of one piece: half a 16-byte slot (four channels)
 template <bool STRIP>
 __device__ __forceinline__ int epi_off(int lane, int nt) {

@@ -569,28 +569,6 @@ __device__ __forceinline__ uint64_t check_term(int i, float pr) {
   return mix64((((uint64_t)(uint32_t)i << 32) | __builtin_bit_cast(uint32_t, pr)) ^ 0x9e3779b97f4a7c15ull);
 }
 
-// Lanes walk the actions i = lane, lane + 64, ... < A as f(i, cell, plane, j) -- action i = plane * hw + cell, the policy
-// planes' layout -- without a division per entry; j = the entry's place in its block of BLOCK entries (a constant after
-// unrolling, for callers that keep a register per place).
-template <int BLOCK, typename F>
-__device__ __forceinline__ void for_each_action_blocked(int A, int hw, int lane, F f) {
-  int cell = lane % hw, plane = lane / hw;
-  const int dcell = 64 % hw, dplane = 64 / hw;
-  for (int i0 = lane; i0 < A; i0 += 64 * BLOCK) {
-#pragma unroll
-    for (int j = 0; j < BLOCK; ++j) {
-      const int i = i0 + 64 * j;
-      if (i < A) f(i, cell, plane, j);
-      cell += dcell; plane += dplane;
-      if (cell >= hw) { cell -= hw; ++plane; }
-    }
-  }
-}
-template <typename F>
-__device__ __forceinline__ void for_each_action(int A, int hw, int lane, F f) {
-  for_each_action_blocked<1>(A, hw, lane, [&](int i, int cell, int plane, int) { f(i, cell, plane); });
-}
-
 // The per-pass constants of wave_network and what its callers place around a pass: the program's header words (read
 // once per move by the caller).
 struct WaveNetArgs {
@@ -601,14 +579,11 @@ struct WaveNetArgs {
 };
 // the program's header, one dword per lane, handed round by v_readlane
 __device__ __forceinline__ WaveNetArgs wave_net_args(const Fused16Program* prog, int lane) {
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int HDR_DWORDS = (int)(offsetof(Fused16Program, ops) / 4);
-  static_assert(HDR_DWORDS <= 64, "one dword per lane");
-  const uint32_t hdr_v = lane < HDR_DWORDS ? ((gptr1u)reinterpret_cast<const uint32_t*>(prog))[lane] : 0u;
-#define PHDR(field) ((int)__builtin_amdgcn_readlane(hdr_v, (int)(offsetof(Fused16Program, field) / 4)))
-  return WaveNetArgs{prog, PHDR(n_ops), PHDR(hw), PHDR(h), PHDR(wd), PHDR(solo_at), PHDR(solo_pol), PHDR(solo_zero_off),
-                     PHDR(solo_zero_len), PHDR(in_off), PHDR(in_cs), PHDR(pol_off), PHDR(pol_cs), PHDR(val_off), PHDR(val_cs)};
-#undef PHDR
+  const uint32_t hdr = fused16_header_dword(prog, lane);
+  return WaveNetArgs{prog, FUSED16_HDR(hdr, n_ops), FUSED16_HDR(hdr, hw), FUSED16_HDR(hdr, h), FUSED16_HDR(hdr, wd),
+                     FUSED16_HDR(hdr, solo_at), FUSED16_HDR(hdr, solo_pol), FUSED16_HDR(hdr, solo_zero_off),
+                     FUSED16_HDR(hdr, solo_zero_len), FUSED16_HDR(hdr, in_off), FUSED16_HDR(hdr, in_cs), FUSED16_HDR(hdr, pol_off),
+                     FUSED16_HDR(hdr, pol_cs), FUSED16_HDR(hdr, val_off), FUSED16_HDR(hdr, val_cs)};
 }
 
 // One simulation wave of one game, one wavefront per game (Explorer.run_mcts, :49-61):
@@ -938,8 +913,7 @@ __device__ __forceinline__ void wave_tap_rows(TapRows<NTAPS>& t, int row, int ro
   for (int w = 0; w < TapRows<NTAPS>::WORDS; ++w) { t.rows[w] = 0u; t.swz[w] = 0u; }
 #pragma unroll
   for (int tap = 0; tap < NTAPS; ++tap) {
-    const int dy = HEX ? (tap < 3 ? tap - 1 : ((tap - 3) & 1) - 1 + (cx & 1)) : tap / 3 - 1;
-    const int dx = HEX ? (tap < 3 ? 0 : (tap < 5 ? -1 : 1)) : tap % 3 - 1;
+    const int dy = tap_dy<HEX>(tap, cx), dx = tap_dx<HEX>(tap);
     const bool on = row_ok && (unsigned)(cy + dy) < (unsigned)H && (unsigned)(cx + dx) < (unsigned)Wd;
     const int r = on ? row + dy * Wd + dx : rows;       // (row index `rows`: every buffer's row of zeros)
     t.rows[tap >> 2] |= (uint32_t)r << ((tap & 3) * 8);
@@ -997,8 +971,8 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
       u32x4 (&n1)[3] = a[(st + 1) & 1][1];
       u32x4 (&nb)[3] = bq[(st + AHEAD) % (AHEAD + 1)];
 #define NZ_PAIR(B, A)                         \
-  acc[0] = wide_mfma(b[B], a0[A], acc[0]);    \
-  acc[1] = wide_mfma(b[B], a1[A], acc[1]);
+  acc[0] = mfma_bf16(b[B], a0[A], acc[0]);    \
+  acc[1] = mfma_bf16(b[B], a1[A], acc[1]);
       __builtin_amdgcn_sched_barrier(0);
       NZ_PAIR(1, 1)
       if (more) { n0[1] = read(st + 1, 0, 1); n1[1] = read(st + 1, 1, 1); }
@@ -1043,7 +1017,8 @@ __device__ __forceinline__ int pieces_chunk(int ct, int lane, int row) {
   return (ct >> 1) * GROUP_FLOATS + (((((ct & 1) << 1) | (lane >> 5)) ^ ((row >> 2) & 3)) << 2) + ((lane >> 4) & 1) * 2;
 }
 
-// residual, activation, split into pieces (or float32 rows), store: fused16_net_kernel's epilogue for one tile
+// A layer's epilogue for one tile: residual, activation, split into pieces (or float32 rows), store.  The values are
+// fused16_dev.hpp's epi16_* (fused16_net_kernel calls the same); the addresses are this layout's.
 __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restrict__ net, const Fused16Op& op, int rt, int ct,
                                               int lane, int rows) {
   const int orow = rt * 16 + (lane & 15), c0 = ct * 16 + (lane >> 4) * 4;
@@ -1056,45 +1031,24 @@ __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restric
     const float* rp = net + op.offr + orow * op.csr + chunk;
     const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
                 q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
-    auto lo = [](uint32_t w) { return __builtin_bit_cast(float, w << 16); };
-    auto hi = [](uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); };
-    v[0] += (lo(q0.x) + lo(q1.x)) + lo(q2.x);
-    v[1] += (hi(q0.x) + hi(q1.x)) + hi(q2.x);
-    v[2] += (lo(q0.y) + lo(q1.y)) + lo(q2.y);
-    v[3] += (hi(q0.y) + hi(q1.y)) + hi(q2.y);
+    epi16_add_residual(v, q0, q1, q2);
   }
-  switch (op.act) {
-    case 1:
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
-      break;
-    case 2:
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
-      break;
-    case 3:
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : fast_expm1(v[r]);
-      break;
-    default: break;
-  }
+  epi16_activate<4>(v, op.act);
   if (op.psd == 0) {
     *reinterpret_cast<f32x4*>(net + op.offd + orow * op.csd + c0) = f32x4{v[0], v[1], v[2], v[3]};
   } else {
-    uint16_t h3[4][3];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) split3_bits(v[r], h3[r]);
+    uint2 q[3];
+    epi16_split(v, q);
     float* dp = net + op.offd + orow * op.csd + chunk;
 #pragma unroll
-    for (int piece = 0; piece < 3; ++piece)
-      *reinterpret_cast<uint2*>(dp + piece * PIECE_FLOATS) =
-          uint2{(uint32_t)h3[0][piece] | ((uint32_t)h3[1][piece] << 16), (uint32_t)h3[2][piece] | ((uint32_t)h3[3][piece] << 16)};
+    for (int piece = 0; piece < 3; ++piece) *reinterpret_cast<uint2*>(dp + piece * PIECE_FLOATS) = q[piece];
   }
 }
 
 // wave_epilogue for both row tiles of a column tile at once: the eight values go through every step together (one
-// wave-uniform switch, independent chains the scheduler interleaves; v_perm packs two values' upper halves per piece),
-// the stores are predicated per row tile.  Same values as wave_epilogue, piece for piece.
+// wave-uniform switch, independent chains the scheduler interleaves), the residual reads and the stores are predicated
+// per row tile.  (Kept beside wave_epilogue: one template over the number of row tiles cost the persistent kernel 1.4 %,
+// profiles/r09_fused16_shared.txt.)
 __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __restrict__ net, const Fused16Op& op, int ct,
                                                int lane, int rows) {
   const int c0 = ct * 16 + (lane >> 4) * 4;
@@ -1116,30 +1070,11 @@ __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __r
         const float* rp = net + op.offr + orow[rt] * op.csr + chunk[rt];
         const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
                     q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
-        auto lo = [](uint32_t w) { return __builtin_bit_cast(float, w << 16); };
-        auto hi = [](uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); };
-        v[rt][0] += (lo(q0.x) + lo(q1.x)) + lo(q2.x);
-        v[rt][1] += (hi(q0.x) + hi(q1.x)) + hi(q2.x);
-        v[rt][2] += (lo(q0.y) + lo(q1.y)) + lo(q2.y);
-        v[rt][3] += (hi(q0.y) + hi(q1.y)) + hi(q2.y);
+        epi16_add_residual(v[rt], q0, q1, q2);
       }
     }
   }
-  switch (op.act) {
-    case 1:
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i >> 2][i & 3] = v[i >> 2][i & 3] > 0.f ? v[i >> 2][i & 3] : 0.f;
-      break;
-    case 2:
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i >> 2][i & 3] = tanhf(v[i >> 2][i & 3]);
-      break;
-    case 3:
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i >> 2][i & 3] = v[i >> 2][i & 3] > 0.f ? v[i >> 2][i & 3] : fast_expm1(v[i >> 2][i & 3]);
-      break;
-    default: break;
-  }
+  epi16_activate<8>(&v[0][0], op.act);
   if (op.psd == 0) {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
@@ -1148,19 +1083,7 @@ __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __r
   }
   uint2 q[2][3];
 #pragma unroll
-  for (int rt = 0; rt < 2; ++rt) {
-    float r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = v[rt][i];
-#pragma unroll
-    for (int piece = 0; piece < 3; ++piece) {
-      q[rt][piece] = uint2{wide_pack_hi16(r[0], r[1]), wide_pack_hi16(r[2], r[3])};
-      if (piece < 2) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = r[i] - wide_trunc(r[i]);
-      }
-    }
-  }
+  for (int rt = 0; rt < 2; ++rt) epi16_split(v[rt], q[rt]);
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) {
     if (ok[rt]) {
@@ -1217,24 +1140,15 @@ __device__ __forceinline__ void pair_sync(int* flags, int me, int& seq, int lane
 template <bool HEX>
 __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __restrict__ net, int lane, int half, int* flags, int& seq,
                                              unsigned long long* tkn = nullptr) {
+  unsigned long long tsn = 0;                  // (the stamps' clock; tkn is null outside the diagnostic builds)
 #ifdef NZ_PERSIST_STAMPS
-  unsigned long long tsn = __builtin_amdgcn_s_memtime();
+  tsn = __builtin_amdgcn_s_memtime();
 #endif
-  constexpr int ntaps = HEX ? 7 : 9;
+  constexpr int ntaps = tap_count<HEX>();
   const int n_ops = wn.n_ops, rows = wn.rows;
   TapRows<ntaps> srow[2];
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) wave_tap_rows<HEX, ntaps>(srow[rt], rt * 16 + (lane & 15), rows, wn.H, wn.Wd, lane);
-  typedef const __attribute__((address_space(1))) uint32_t* gptr1u;
-  constexpr int OP_DWORDS = (int)(sizeof(Fused16Op) / 4);
-  static_assert(OP_DWORDS <= 64, "one dword per lane");
-  const gptr1u ops_words = (gptr1u)reinterpret_cast<const uint32_t*>(wn.prog->ops);
-  auto unpack = [](uint32_t v, Fused16Op& op) {
-    uint32_t words[OP_DWORDS];
-#pragma unroll
-    for (int i = 0; i < OP_DWORDS; ++i) words[i] = __builtin_amdgcn_readlane(v, i);
-    __builtin_memcpy(&op, words, sizeof(Fused16Op));
-  };
   // this wavefront's layers in order: the shared ones, then its own chain
   const int solo_at = wn.solo_at < n_ops ? wn.solo_at : n_ops;
   const int chain_first = half == 0 ? solo_at : solo_at + wn.solo_pol;
@@ -1243,18 +1157,17 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
   auto layer_at = [&](int i) { return i < solo_at ? i : chain_first + (i - solo_at); };
   // A layer's descriptor stays in ONE vector register (a dword per lane, fetched a layer ahead) until the layer starts:
   // unpacked a layer early its fields were scalar registers the K loop had no room for (spilled to lanes and back).
-  uint32_t cur = (n_mine > 0 && lane < OP_DWORDS) ? ops_words[layer_at(0) * OP_DWORDS + lane] : 0u;
-  uint32_t nxt = (n_mine > 1 && lane < OP_DWORDS) ? ops_words[layer_at(1) * OP_DWORDS + lane] : 0u;
+  uint32_t cur = n_mine > 0 ? fused16_op_dword(wn.prog, layer_at(0), lane) : 0u;
+  uint32_t nxt = n_mine > 1 ? fused16_op_dword(wn.prog, layer_at(1), lane) : 0u;
   int wv = 0;
   u32x4 bq[WAVE_AHEAD + 1][3];
   auto job_weights = [&](const Fused16Op& x, int ct) {
     wave_weights_prologue(bq, wave_weights_rsrc(x.w + (size_t)ct * x.w_chunks * 4, x.w_chunks), wv, lane);
   };
   for (int i = 0; i < n_mine; ++i) {
-    Fused16Op op;
-    unpack(cur, op);
+    const Fused16Op op = fused16_unpack(cur);
     cur = nxt;
-    if (i + 2 < n_mine && lane < OP_DWORDS) nxt = ops_words[layer_at(i + 2) * OP_DWORDS + lane];
+    if (i + 2 < n_mine) nxt = fused16_op_dword(wn.prog, layer_at(i + 2), lane);
     const int kgt = op.kg0;
     const bool shared = i < solo_at;
     if (i == solo_at && half == 0 && lane * 4 < wn.solo_zero_len)       // (the policy head's hidden buffer: its row of zeros)
@@ -1265,17 +1178,7 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
       f32x4 acc[2];
       WSTAMP(4);                    // (the layer's header: descriptor words, addresses)
       job_weights(op, ct);
-#ifdef NZ_PERSIST_STAMPS
-      if (kgt == 1) wave_layer_kloop<ntaps, 1>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn);
-      else if (kgt == 2) wave_layer_kloop<ntaps, 2>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn);
-      else if (kgt == 3) wave_layer_kloop<ntaps, 3>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn);
-      else wave_layer_kloop<ntaps, 4>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn);
-#else
-      if (kgt == 1) wave_layer_kloop<ntaps, 1>(acc, net, op, srow, ct, lane, bq, wv);
-      else if (kgt == 2) wave_layer_kloop<ntaps, 2>(acc, net, op, srow, ct, lane, bq, wv);
-      else if (kgt == 3) wave_layer_kloop<ntaps, 3>(acc, net, op, srow, ct, lane, bq, wv);
-      else wave_layer_kloop<ntaps, 4>(acc, net, op, srow, ct, lane, bq, wv);
-#endif
+      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn); });
       WSTAMP(0);
       wave_epilogue2(acc, net, op, ct, lane, rows);
       WSTAMP(1);
@@ -1291,10 +1194,7 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
       f32x4 acc[1];
       WSTAMP(4);
       job_weights(op, ct);
-      if (kgt == 1) wave_layer_kloop<ntaps, 1, 1>(acc, net, op, srow1, ct, lane, bq, wv);
-      else if (kgt == 2) wave_layer_kloop<ntaps, 2, 1>(acc, net, op, srow1, ct, lane, bq, wv);
-      else if (kgt == 3) wave_layer_kloop<ntaps, 3, 1>(acc, net, op, srow1, ct, lane, bq, wv);
-      else wave_layer_kloop<ntaps, 4, 1>(acc, net, op, srow1, ct, lane, bq, wv);
+      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value, 1>(acc, net, op, srow1, ct, lane, bq, wv); });
       WSTAMP(0);
       wave_epilogue(acc[0], net, op, half, ct, lane, rows);
       WSTAMP(1);
@@ -1328,7 +1228,7 @@ __device__ __forceinline__ void split_planes_half(float* __restrict__ net, const
         if (c8 * 8 + j >= q.in_channels) lo4[j] = 0.f;
         if (c8 * 8 + 4 + j >= q.in_channels) hi4[j] = 0.f;
       }
-      wide_split8(lo4, hi4, q0, q1, q2);
+      split8(lo4, hi4, q0, q1, q2);
     }
     float* d = net + in_off + r * in_cs + (c8 >> 2) * GROUP_FLOATS + (((c8 & 3) ^ ((r >> 2) & 3)) << 2);
     *reinterpret_cast<u32x4*>(d) = q0;
@@ -1538,35 +1438,30 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
 
       // softmax over ALL logits (Explorer.py:158-160) and value = tanh(mean of the value plane) (blocks.py:82-84)
       float mx = -INFINITY;
-      for_each_action(A, hw, lane, [&](int, int cell, int plane) { mx = fmaxf(mx, pol[cell * pp + plane]); });
+      for_each_action(A, hw, lane, 64, [&](int, int cell, int plane) { mx = fmaxf(mx, pol[cell * pp + plane]); });
       for (int w = 32; w; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w, 64));
-      // the sum in fused16_net_kernel's order for a workgroup of up to four positions (four wavefronts per position, each
-      // lane adding every 256th entry, a butterfly per wavefront, the four partial sums added in turn), so that a game
-      // plays the same moves on either route
-      float part[4] = {0.f, 0.f, 0.f, 0.f};
-      for_each_action_blocked<4>(A, hw, lane, [&](int, int cell, int plane, int sub) {
+      // the sum in the order fused16_net_kernel gives a workgroup's only position (softmax_ways), all partial sums on this
+      // wavefront, so that a game plays the same moves on either route
+      constexpr int WAYS = softmax_ways(1);
+      static_assert(WAYS == softmax_ways(4), "the wave-by-wave route's workgroups hold up to four positions");
+      float part[WAYS] = {};
+      for_each_action_blocked<WAYS>(A, hw, lane, 64, [&](int, int cell, int plane, int sub) {
         const float e = expf(pol[cell * pp + plane] - mx);
         pol[cell * pp + plane] = e;
         part[sub] += e;
       });
       sum = 0.f;
 #pragma unroll
-      for (int sub = 0; sub < 4; ++sub) {
-        float ps = part[sub];
-        for (int w = 32; w; w >>= 1) ps += __shfl_xor(ps, w, 64);
-        sum += ps;
-      }
+      for (int sub = 0; sub < WAYS; ++sub) sum += wave_sum(part[sub]);
       pair_sync(flags, 0, seq, lane);             // (the helper's value head is done)
-      float sv = lane < hw ? net[wna.val_off + lane * wna.val_cs] : 0.f;
-      for (int w = 32; w; w >>= 1) sv += __shfl_xor(sv, w, 64);
-      value = tanhf(sv / (float)hw);
+      value = value_of_plane(lane < hw ? net[wna.val_off + lane * wna.val_cs] : 0.f, hw);       // (hw <= 64: a cell per lane)
       scs_sync<false>();
       PSTAMP(5);                                // softmax + value
       if (p.c_bits > 0) {
         // KeylessCache.put (KeylessCache.py:60-75): the newest evaluation takes the entry; stores only, nothing to wait for
         unsigned long long* const id = reinterpret_cast<unsigned long long*>(p.c_id + 2 * entry);
         uint64_t acc = 0;
-        for_each_action(A, hw, lane, [&](int i, int cell, int plane) {
+        for_each_action(A, hw, lane, 64, [&](int i, int cell, int plane) {
           const float pr = pol[cell * pp + plane] / sum;
           __hip_atomic_store(p.c_probs + entry * A + i, pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           acc += check_term(i, pr);
@@ -1584,7 +1479,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
       if (rec >= 0) {
         if (rec_n < q.rec_cap) {
           const size_t at = (size_t)rec * q.rec_cap + rec_n;
-          for_each_action(A, hw, lane, [&](int i, int cell, int plane) { q.rec_probs[at * A + i] = pol[cell * pp + plane] / sum; });
+          for_each_action(A, hw, lane, 64, [&](int i, int cell, int plane) { q.rec_probs[at * A + i] = pol[cell * pp + plane] / sum; });
           if (lane == 0) { q.rec_value[at] = value; q.rec_digest[2 * at] = dig_hi; q.rec_digest[2 * at + 1] = dig_lo; }
         }
         ++rec_n;

@@ -65,7 +65,7 @@ def _oracle_net_on_leaves(path, w, arch, depth, hexnet, r, g, recs, n_check):
     return checked, worst_p, worst_v
 
 
-@pytest.mark.parametrize("arch,hexnet", [("convnet", False), ("resnet", False), ("convnet", True)])
+@pytest.mark.parametrize("arch,hexnet", [("convnet", False), ("resnet", False), ("convnet", True), ("resnet", True)])
 def test_persistent_route_equals_the_oracle_replay_and_the_wave_route(arch, hexnet):
     from nuzero_amd.scs import ScsSelfPlay, ScsGameConfig
     path = os.path.join(GOLDEN, "scs_configs", "late_reinforcements_5x5.yml" if arch == "convnet" else "mirrored_5x5.yml")
