@@ -292,6 +292,36 @@ int32_t nz_net_final_tap(int32_t cell);
 nz_status nz_net_forward(nz_engine* e, const float* states_dev, int32_t batch, float* logits_dev,
                          float* value_dev, float* probs_dev, void* stream);
 
+/* ---- the packed network pass: a pass sized for a few positions per workgroup ----
+ * The persistent kernel gives a workgroup ceil(n_slots / CUs) games; with P <= NZ_NET_PACKED_MAX of them the 16 columns
+ * of its matrix instructions can be (position, cell) pairs instead of positions: ceil(9 P / 16) column tiles, nine
+ * six-MFMA chains each per K group and output tile, where the 16-position tile costs 49.  The outputs are bit for bit
+ * those of the 16-position tile.  NZ_NET_PACKED in the environment at nz_engine_create: 0 = never, N = engines with at
+ * most N games per workgroup, unset = the measured rule. */
+#define NZ_NET_PACKED_MAX 8
+/* nz_net_forward's outputs from a kernel of one workgroup per `positions_per_pass` (1 .. NZ_NET_PACKED_MAX) positions
+ * that runs the packed pass. */
+nz_status nz_net_forward_packed(nz_engine* e, const float* states_dev, int32_t batch, int32_t positions_per_pass,
+                                float* logits_dev, float* value_dev, float* probs_dev, void* stream);
+/* Positions a network pass of nz_engine_play's kernel is sized for: 16 (the full tile), or the engine's games per
+ * workgroup when it takes the packed pass. */
+nz_status nz_engine_positions_per_pass(const nz_engine* e, int32_t* out);
+/* The column map of the packed pass for P positions (host only): *n_tiles = T = ceil(9 P / 16) column tiles, and for
+ * column j of tile t, at index i = 16 t + j: col_pos[i] and col_cell[i] (-1, -1: a dead column) and tap_src[9 i + tap],
+ * the cell of the same position whose activations the column reads for `tap` (tap = 3 (dy + 1) + (dx + 1) as for
+ * nz_net_final_tap; -1: off the board or dead, a zero fragment).  Arrays of max_cols entries (9 max_cols for tap_src);
+ * NZ_ERR_ARG when 16 T exceeds max_cols. */
+nz_status nz_net_packed_columns(int32_t P, int32_t* col_pos, int32_t* col_cell, int32_t* tap_src, int32_t max_cols,
+                                int32_t* n_tiles);
+/* The job lists of the packed pass for `net` and P positions (host only): one row of NZ_NET_PACKED_JOB_FIELDS int32 per
+ * job, barrier-only jobs included -- wave, stage, conv tensor (state_dict order; -1: barrier only), output tile, first
+ * column tile, column tiles, K groups, source area, destination (0 .. 3: areas, 8: policy logits, 9: value), residual
+ * area or -1, activation (0 none, 1 relu, 2 tanh, 3 elu), 1 if the input planes are read, 1 if the workgroup barrier
+ * of a stage follows the job, output tiles of the conv.  Writes at most max_jobs rows, sets *n_jobs to their number. */
+#define NZ_NET_PACKED_JOB_FIELDS 14
+nz_status nz_net_packed_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t P, int32_t* jobs,
+                                int32_t max_jobs, int32_t* n_jobs);
+
 /* Diagnostic build of the network kernel: mean shader-clock ticks wave 0 of a
  * workgroup spends in [0] the K-group loops (LDS reads + MFMA), [1] the
  * input-plane step, [2] the epilogues, [3] at the stage barriers.  Synchronises. */

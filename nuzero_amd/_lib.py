@@ -26,6 +26,8 @@ NZ_LOSS_SE, NZ_LOSS_AE = 0, 1
 NZ_NET_JOB_FIELDS = 13
 NZ_NET_STEAL_FIELDS = 11
 NZ_NET_SOLO_FIELDS = NZ_NET_JOB_FIELDS + 3
+NZ_NET_PACKED_MAX = 8
+NZ_NET_PACKED_JOB_FIELDS = 14
 
 
 class SearchCfg(Structure):
@@ -121,6 +123,10 @@ SIGNATURES = {
                                       POINTER(c_int32)]),
     "nz_net_final_tap": (c_int32, [c_int32]),
     "nz_net_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_net_forward_packed": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_engine_positions_per_pass": (c_int32, [c_void_p, POINTER(c_int32)]),
+    "nz_net_packed_columns": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32)]),
+    "nz_net_packed_program": (c_int32, [POINTER(NetDesc), c_int32, c_int32, c_void_p, c_int32, POINTER(c_int32)]),
     "nz_net_forward_stamps": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(c_double)]),
     "nz_engine_profile": (c_int32, [c_void_p, c_int32]),
     "nz_engine_profile_read": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),

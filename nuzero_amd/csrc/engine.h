@@ -112,9 +112,10 @@ void launch_export_visits(const TreeParams& p, int32_t* visits, int32_t* actions
                           int32_t* n_children, double* bias, hipStream_t s);
 
 int selfplay_blocks(int n_slots, int slots_per_wg);
-// stamps != nullptr selects the diagnostic build ([blocks][4] phase ticks, see selfplay.hip)
+// stamps != nullptr selects the diagnostic build ([blocks][4] phase ticks, see selfplay.hip); `packed`: prog_dev is a
+// packed program for p.slots_per_wg positions (net_packed_dev.hpp) and the kernel's packed instantiation runs it
 void launch_selfplay(const TreeParams& p, const struct NetProgram* prog_dev, int n_layers, const float* weights,
-                     const double* noise, const double* uniforms, unsigned long long* stamps, hipStream_t s);
+                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s);
 
 // ---- network ----------------------------------------------------------------
 // Arithmetic of the fused network: net_dev.hpp.  K groups are 32 channels; the packed weights of
@@ -185,8 +186,33 @@ struct NetProgram {
   int32_t stage_budget[NET_MAX_JOBS];    // simulations a sitting-out wave's row may run before the stage's barrier
 };
 
+// ---- the packed pass (net_packed_dev.hpp): a network pass for P <= NET_PACKED_MAX positions -------------------------
+// The MFMA's 16 columns are (position, cell) pairs instead of positions: pair c = 9 pos + cell sits in column c % 16 of
+// column tile c / 16, and for one tap a column's activation fragment is that of input cell cell + (dy, dx) of its
+// position (zero where that is off the board), so a conv costs 9 ceil(9 P / 16) six-MFMA chains per K group and output
+// tile where the 16-position tile costs 49.  Its program is a NetProgram whose jobs are (conv, output tile, run of
+// column tiles): NetJob::og = first column tile + 8 * tiles (OG_NONE: barrier only), src / dst / res are AREAS, and the
+// solo lists and stage budgets stay empty (no wave sits a packed pass out).
+constexpr int NET_PACKED_MAX = NZ_NET_PACKED_MAX;
+constexpr int NET_PACKED_DEFAULT = 4;        // engines of at most this many games per workgroup take it: the measured rule
+                                             // (engine.hip nz_engine_create_ex, profiles/r10_packed_pass.txt)
+constexpr int NET_PACKED_AREAS = 4;         // areas of 9 P activation rows inside the two activation buffers
+constexpr int NET_PACKED_RUN = 2;            // column tiles one job may hold (accumulators, operand fragments)
+constexpr int NET_PACKED_DST_POLICY = 8;     // NetJob::dst of a packed job: policy logits out
+constexpr int NET_PACKED_DST_VALUE = 9;      // NetJob::dst of a packed job: value out
+__host__ __device__ constexpr int net_packed_tiles(int P) { return (9 * P + 15) / 16; }
+__host__ __device__ constexpr int net_packed_og(int first_tile, int tiles) { return first_tile + 8 * tiles; }
+// source cell of (cell, tap), tap = 3 (dy + 1) + (dx + 1) as for net_final_tap; -1: off the board
+__host__ __device__ constexpr int net_packed_tap_source(int cell, int tap) {
+  const int y = cell / 3 + tap / 3 - 1, x = cell % 3 + tap % 3 - 1;
+  return y >= 0 && y < 3 && x >= 0 && x < 3 ? 3 * y + x : -1;
+}
+
 void launch_net(const NetProgram* prog_dev, int n_layers, const float* packed_weights,
                 const uint32_t* boards, const float* states, const int32_t* count_dev, int max_positions,
                 float* logits, float* value, float* probs, unsigned long long* stamps, hipStream_t s);
+// the same outputs from the packed pass: one workgroup per P positions, `prog_dev` a packed program for P
+void launch_net_packed(const NetProgram* prog_dev, int P, const float* packed_weights, const float* states, int batch,
+                       float* logits, float* value, float* probs, hipStream_t s);
 
 }  // namespace nz

@@ -62,6 +62,12 @@ struct MatchArrays {
     return ok;
   }
 };
+
+// Where pack_conv (below) put one conv tensor's streams, and the shape they were packed for.
+struct PackedConv {
+  int cout, cin, cin_main, kgroups, ntiles, extra;
+  int32_t w_off, wx_off;
+};
 }  // namespace
 
 struct nz_engine {
@@ -80,6 +86,12 @@ struct nz_engine {
   nz_net_desc net;
   int iters = 0;
   NetProgram prog_host;
+  // the packed pass (net_packed_dev.hpp): whether nz_engine_play's kernel takes it (decided at create), and the
+  // programs compiled so far for the current weights, by positions per pass (packed_program below)
+  bool packed = false;
+  std::vector<PackedConv> convs;              // the packed tensors' layout, as nz_engine_set_weights made it
+  DevBuf<NetProgram> packed_prog[NZ_NET_PACKED_MAX + 1];
+  bool packed_ready[NZ_NET_PACKED_MAX + 1] = {};
   DevBuf<float> weights_dev, table_dev;
   const float* borrowed_weights = nullptr;    // fallback engine: the parent's packed weights, used instead of weights_dev
   double executed_bf16_flops_per_position = 0.0, executed_f32_flops_per_position = 0.0;
@@ -150,10 +162,7 @@ struct Span {
 // tile nt a contiguous weight stream main[nt][kgroup of 32 ch][tap][piece][lane][8 bf16] (the
 // three exact bf16 pieces of every weight) and, for the two convs that also read the raw
 // input planes, extra[nt][tap][lane] in float32.
-struct PackedConv {
-  int cout, cin, cin_main, kgroups, ntiles, extra;
-  int32_t w_off, wx_off;
-};
+// (struct PackedConv: above, the engine keeps the layout)
 PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vector<float>& out) {
   PackedConv pc{};
   pc.cout = cout; pc.cin = cin; pc.cin_main = cin_main;
@@ -406,13 +415,117 @@ std::string net_layout(const nz_net_desc* net, int recurrent_iterations, NetLayo
   for (int i = 0; i < 4; ++i) shapes.push_back({vc[i + 1], vc[i], 3});
   return "";
 }
+// The trunk's stages, one conv each, in execution order: activation areas 0 / 1 ping-pong from `cur` = 0, and on return
+// `cur` holds the trunk's output.  The one layer list of both compilers (compile_net, compile_net_packed).
+std::vector<StageConv> trunk_stages(const nz_net_desc* net, const NetLayout& L, int& cur) {
+  std::vector<StageConv> out;
+  cur = 0;
+  if (net->arch == NZ_ARCH_CONVNET) {                                 // ConvNet.py:20-40: (conv, ELU) x (1 + num_layers)
+    out.push_back({0, 0, cur, -1, 3, true});
+    for (int i = 1; i < L.trunk_tensors; ++i) { out.push_back({i, cur, cur ^ 1, -1, 3, true}); cur ^= 1; }
+  } else {
+    out.push_back({0, 0, cur, -1, 1, true});                          // projection / input block + ReLU
+    const int first_block = L.recall ? 2 : 1;
+    for (int it = 0; it < L.iterations; ++it) {
+      if (L.recall) { out.push_back({1, cur, cur ^ 1, -1, 0, true}); cur ^= 1; }    // cat([thought, x]) conv, no activation
+      for (int b = 0; b < net->num_blocks; ++b) {                         // relu(conv2(relu(conv1(t))) + t)
+        out.push_back({first_block + 2 * b, cur, cur ^ 1, -1, 1, true});
+        out.push_back({first_block + 2 * b + 1, cur ^ 1, cur, cur, 1, true});
+      }
+    }
+  }
+  return out;
+}
+
+// The packed pass's program for P positions (net_packed_dev.hpp): the same layer list and weight offsets as compile_net,
+// jobs of (conv, output tile, run of column tiles).  Areas 0 / 1 ping-pong through the trunk; the heads run side by
+// side in four stages as in compile_net, the policy head's first conv into area 2 (no strip).  `tensor_of[w][j]`
+// (optional): the conv tensor of pg.jobs[w][j], -1 for a barrier-only job.  "" or why it does not fit.
+std::string compile_net_packed(const nz_net_desc* net, const NetLayout& L, const std::vector<PackedConv>& convs, int P,
+                               NetProgram& pg, std::vector<int>* tensor_of = nullptr) {
+  if (P < 1 || P > NET_PACKED_MAX) return text("positions per pass must be 1 .. %d", NET_PACKED_MAX);
+  memset(&pg, 0, sizeof(pg));
+  const int T = net_packed_tiles(P);
+  bool ok = true;
+  auto stage = [&](const std::vector<StageConv>& cs) {
+    struct Unit { NetJob job; int cost, tensor; };
+    int n_tiles = 0;
+    for (const StageConv& sc : cs) n_tiles += convs[sc.tensor].ntiles;
+    // runs as long as NET_PACKED_RUN allows while every wave still gets a unit, else shorter ones
+    int run = NET_PACKED_RUN;
+    while (run > 1 && n_tiles * ((T + run - 1) / run) < NET_WAVES_HOST) --run;
+    const int n_runs = (T + run - 1) / run;
+    std::vector<Unit> units;
+    for (const StageConv& sc : cs) {
+      const PackedConv& pc = convs[sc.tensor];
+      for (int nt = 0; nt < pc.ntiles; ++nt)
+        for (int r = 0, t0 = 0; r < n_runs; ++r) {
+          const int len = T / n_runs + (r < T % n_runs ? 1 : 0);      // as even as T allows, longer runs first
+          NetJob j{};
+          j.w_off = pc.w_off + nt * pc.kgroups * NET_KG_DWORDS;
+          j.wx_off = pc.wx_off + nt * 9 * 64;
+          j.kgroups = (int8_t)pc.kgroups;
+          j.nt = (int16_t)nt;
+          j.extra = (int8_t)pc.extra;
+          j.og = (int8_t)net_packed_og(t0, len);
+          j.src = (int8_t)sc.src; j.dst = (int8_t)sc.dst; j.res = (int8_t)sc.res; j.act = (int8_t)sc.act;
+          j.dtile = (int8_t)nt;
+          units.push_back({j, len * 9 * (3 * pc.kgroups + pc.extra) + JOB_OVERHEAD, sc.tensor});
+          t0 += len;
+        }
+    }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.cost > b.cost; });
+    int load[NET_WAVES_HOST] = {}, first[NET_WAVES_HOST];
+    for (int w = 0; w < NET_WAVES_HOST; ++w) first[w] = pg.n_jobs[w];
+    auto push = [&](int w, const NetJob& j, int tensor) {
+      if (pg.n_jobs[w] >= NET_MAX_JOBS) { ok = false; return; }
+      pg.jobs[w][pg.n_jobs[w]++] = j;
+      if (tensor_of) tensor_of[w].push_back(tensor);
+    };
+    for (const Unit& u : units) {
+      int w = 0;
+      for (int i = 1; i < NET_WAVES_HOST; ++i)
+        if (load[i] < load[w]) w = i;
+      load[w] += u.cost;
+      push(w, u.job, u.tensor);
+    }
+    for (int w = 0; w < NET_WAVES_HOST && ok; ++w) {
+      if (pg.n_jobs[w] == first[w]) {            // nothing to do in this stage: barrier only
+        NetJob j{};
+        j.og = OG_NONE;
+        push(w, j, -1);
+      }
+      if (ok) pg.jobs[w][pg.n_jobs[w] - 1].flags |= NET_JOB_STAGE_END;
+    }
+    ++pg.n_stages;
+  };
+  int cur = 0;
+  for (const StageConv& sc : trunk_stages(net, L, cur)) stage({sc});
+  const int ph = L.trunk_tensors, vh = ph + 2;
+  const int vact = net->value_activation == NZ_ACT_RELU ? 1 : 2;
+  const int side = cur ^ 1, pol = 2;
+  stage({{vh, cur, side, -1, vact, true}, {ph, cur, pol, -1, 1, true}});
+  stage({{vh + 1, side, cur, -1, vact, true}, {ph + 1, pol, NET_PACKED_DST_POLICY, -1, 0, true}});
+  stage({{vh + 2, cur, side, -1, vact, true}});
+  stage({{vh + 3, side, NET_PACKED_DST_VALUE, -1, 0, true}});
+  if (!ok) return text("network too deep for one fused launch (%d iterations)", L.iterations);
+  for (int w = 0; w < NET_WAVES_HOST; ++w) {     // prefetch chain, as in compile_net
+    int32_t next = -1;
+    for (int j = pg.n_jobs[w] - 1; j >= 0; --j) {
+      pg.jobs[w][j].next_w_off = next;
+      if (pg.jobs[w][j].og != OG_NONE && pg.jobs[w][j].kgroups > 0) next = pg.jobs[w][j].w_off;
+    }
+    pg.first_w_off[w] = next;
+  }
+  return "";
+}
+
 // The network as per-wave job lists (`convs`: the packed tensors' layout); `flops`: in-bounds taps only, 2 * Cout * Cin *
 // 49 per 3x3 conv application (9 for 1x1).  "" or why it does not fit one fused launch.
 std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::vector<PackedConv>& convs, NetProgram& pg,
                         double& flops) {
   const std::vector<ConvShape>& shapes = L.shapes;
-  const int arch = net->arch, trunk_tensors = L.trunk_tensors, iterations = L.iterations;
-  const bool recall = L.recall;
+  const int trunk_tensors = L.trunk_tensors, iterations = L.iterations;
   flops = 0.0;
   // stages; activation buffers 0/1 ping-pong, `cur` holds the running trunk output.
   // act: 1 relu, 2 tanh, 3 elu
@@ -424,20 +537,7 @@ std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::v
       flops += 2.0 * shapes[sc.tensor].cout * shapes[sc.tensor].cin * (shapes[sc.tensor].k == 3 ? 49.0 : 9.0);
     ok = ok && add_stage(pg, convs, convs_in_stage);
   };
-  if (arch == NZ_ARCH_CONVNET) {                                      // ConvNet.py:20-40: (conv, ELU) x (1 + num_layers)
-    stage({{0, 0, cur, -1, 3, true}});
-    for (int i = 1; i < trunk_tensors; ++i) { stage({{i, cur, cur ^ 1, -1, 3, true}}); cur ^= 1; }
-  } else {
-    stage({{0, 0, cur, -1, 1, true}});                                // projection / input block + ReLU
-    const int first_block = recall ? 2 : 1;
-    for (int it = 0; it < iterations; ++it) {
-      if (recall) { stage({{1, cur, cur ^ 1, -1, 0, true}}); cur ^= 1; }    // cat([thought, x]) conv, no activation
-      for (int b = 0; b < net->num_blocks; ++b) {                         // relu(conv2(relu(conv1(t))) + t)
-        stage({{first_block + 2 * b, cur, cur ^ 1, -1, 1, true}});
-        stage({{first_block + 2 * b + 1, cur ^ 1, cur, cur, 1, true}});
-      }
-    }
-  }
+  for (const StageConv& sc : trunk_stages(net, L, cur)) stage({sc});
   const int ph = trunk_tensors, vh = ph + 2;
   const int vact = net->value_activation == NZ_ACT_RELU ? 1 : 2;
   const int side = cur ^ 1;
@@ -489,6 +589,36 @@ std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::v
     // (the sitting-out wave counts the barriers off its own list: selfplay.hip burst_under_pass)
     if (stage_ends != pg.n_stages) return "job lists disagree on the number of stages";
     pg.solo_n_jobs[p] = (int32_t)solo.size();
+  }
+  return "";
+}
+
+// The engine's packed program for P positions per pass, on the device: compiled for the current weights at first use.
+nz_status packed_program(nz_engine* e, int P, const NetProgram** out) {
+  if (P < 1 || P > NET_PACKED_MAX) return fail(e, NZ_ERR_ARG, "positions per pass must be 1 .. %d", NET_PACKED_MAX);
+  if (!e->packed_ready[P]) {
+    NetLayout L;
+    std::string bad = net_layout(&e->net, e->iters, L);
+    std::unique_ptr<NetProgram> pg(new NetProgram);
+    if (bad.empty()) bad = compile_net_packed(&e->net, L, e->convs, P, *pg);
+    if (!bad.empty()) return fail(e, NZ_ERR_ARG, "%s", bad.c_str());
+    if (!e->packed_prog[P].ensure(1)) return fail(e, NZ_ERR_HIP, "device allocation failed (packed program)");
+    NZ_HIP(e, hipMemcpy(e->packed_prog[P].get(), pg.get(), sizeof(NetProgram), hipMemcpyHostToDevice));
+    e->packed_ready[P] = true;
+  }
+  *out = e->packed_prog[P].get();
+  return NZ_OK;
+}
+
+// the layout compile_net and compile_net_packed need when no weights are at hand (host-only queries): zero weights
+std::string layout_only(const nz_net_desc* net, int recurrent_iterations, NetLayout& L, std::vector<PackedConv>& convs) {
+  const std::string bad = net_layout(net, recurrent_iterations, L);
+  if (!bad.empty()) return bad;
+  std::vector<float> packed;
+  convs.resize(L.shapes.size());
+  for (size_t i = 0; i < L.shapes.size(); ++i) {
+    const std::vector<float> zeros((size_t)L.shapes[i].cout * L.shapes[i].cin * 9, 0.f);
+    convs[i] = pack_conv(zeros.data(), L.shapes[i].cout, L.shapes[i].cin, L.cin_main((int)i, net->in_channels), packed);
   }
   return "";
 }
@@ -661,6 +791,15 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   // (profiles/r06_burst_under_net.txt).
   p.burst_under_net = 1;
   if (const char* v = getenv("NZ_BURST_UNDER_NET")) p.burst_under_net = std::min(2, std::max(0, atoi(v)));   // tuning experiments
+  // An engine of at most NET_PACKED_DEFAULT games per workgroup takes the packed pass (net_packed_dev.hpp; the same
+  // outputs, fewer matrix instructions).  NZ_NET_PACKED (experiments): 0 = never, N = for slots_per_wg <= N.  The packed
+  // pass has no stealing partner, so for such an engine burst_under_net counts as off (results do not depend on it).
+  {
+    int upto = NET_PACKED_DEFAULT;
+    if (const char* v = getenv("NZ_NET_PACKED")) upto = std::min(NET_PACKED_MAX, std::max(0, atoi(v)));
+    e->packed = p.slots_per_wg <= upto;
+    if (e->packed) p.burst_under_net = 0;
+  }
   if (p.burst_under_net == 1 && p.slots_per_wg == 16) p.sims_per_cycle = 6;
   if (const char* v = getenv("NZ_SIMS_PER_CYCLE")) p.sims_per_cycle = std::max(1, atoi(v));   // tuning experiments
   {   // every cycle finishes at least one simulation or one move of every live row of the workgroup
@@ -772,6 +911,13 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
   e->have_net = true;
   e->have_table = false;
   e->tp.table = nullptr;
+  e->convs = convs;
+  for (bool& ready : e->packed_ready) ready = false;
+  if (e->packed) {                               // the program nz_engine_play's kernel will run
+    const NetProgram* unused = nullptr;
+    const nz_status st = packed_program(e, e->tp.slots_per_wg, &unused);
+    if (st != NZ_OK) return st;
+  }
   return NZ_OK;
 }
 
@@ -901,6 +1047,60 @@ nz_status nz_net_solo_program(const nz_net_desc* net, int32_t recurrent_iteratio
 }
 
 int32_t nz_net_final_tap(int32_t cell) { return cell >= 0 && cell < 9 ? net_final_tap(cell) : -1; }
+
+nz_status nz_net_packed_columns(int32_t P, int32_t* col_pos, int32_t* col_cell, int32_t* tap_src, int32_t max_cols,
+                                int32_t* n_tiles) {
+  if (P < 1 || P > NET_PACKED_MAX || !col_pos || !col_cell || !tap_src || !n_tiles) return NZ_ERR_ARG;
+  const int T = net_packed_tiles(P);
+  if (16 * T > max_cols) return NZ_ERR_ARG;
+  for (int i = 0; i < 16 * T; ++i) {             // column i % 16 of tile i / 16 holds pair i (net_packed_dev.hpp pk_column)
+    const bool live = i < 9 * P;
+    col_pos[i] = live ? i / 9 : -1;
+    col_cell[i] = live ? i % 9 : -1;
+    for (int tap = 0; tap < 9; ++tap) tap_src[9 * i + tap] = live ? net_packed_tap_source(i % 9, tap) : -1;
+  }
+  *n_tiles = T;
+  return NZ_OK;
+}
+
+nz_status nz_net_packed_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t P, int32_t* jobs,
+                                int32_t max_jobs, int32_t* n_jobs) {
+  if (!net || !n_jobs || (!jobs && max_jobs > 0)) return NZ_ERR_ARG;
+  NetLayout L;
+  std::vector<PackedConv> convs;
+  std::unique_ptr<NetProgram> pg(new NetProgram);
+  std::vector<int> tensor_of[NET_WAVES_HOST];
+  std::string bad = layout_only(net, recurrent_iterations, L, convs);
+  if (bad.empty()) bad = compile_net_packed(net, L, convs, P, *pg, tensor_of);
+  if (!bad.empty()) {
+    g_create_error = bad;
+    return NZ_ERR_ARG;
+  }
+  int32_t n = 0;
+  for (int w = 0; w < NET_WAVES_HOST; ++w) {
+    int stage = 0;
+    for (int j = 0; j < pg->n_jobs[w]; ++j, ++n) {
+      const NetJob& job = pg->jobs[w][j];
+      const int tensor = tensor_of[w][j], end = (job.flags & NET_JOB_STAGE_END) ? 1 : 0;
+      const bool work = job.og != OG_NONE;
+      if (n < max_jobs) {
+        const int32_t row[NZ_NET_PACKED_JOB_FIELDS] = {w, stage, tensor, job.nt, work ? job.og & 7 : 0, work ? job.og >> 3 : 0,
+                                                       job.kgroups, job.src, job.dst, job.res, job.act, job.extra, end,
+                                                       work ? convs[tensor].ntiles : 0};
+        memcpy(jobs + (size_t)n * NZ_NET_PACKED_JOB_FIELDS, row, sizeof(row));
+      }
+      stage += end;
+    }
+  }
+  *n_jobs = n;
+  return NZ_OK;
+}
+
+nz_status nz_engine_positions_per_pass(const nz_engine* e, int32_t* out) {
+  if (!e || !out) return NZ_ERR_ARG;
+  *out = e->packed ? e->tp.slots_per_wg : 16;
+  return NZ_OK;
+}
 
 nz_status nz_engine_set_table(nz_engine* e, const float* table, int32_t n_rows) {
   if (!e || !table) return NZ_ERR_ARG;
@@ -1220,9 +1420,11 @@ nz_status nz_engine_play_next(nz_engine* e, uint64_t base_seed, int32_t have_nex
   }
   {
     Span sp(e, s, 0);
-    launch_selfplay(e->tp, e->dev.prog.get(), 0, net_weights(e),
+    // (a packed engine that plays from a table has no packed program and never reaches the network phase)
+    const bool packed = e->packed && e->have_net && e->packed_ready[e->tp.slots_per_wg];
+    launch_selfplay(e->tp, packed ? e->packed_prog[e->tp.slots_per_wg].get() : e->dev.prog.get(), 0, net_weights(e),
                     c.training ? e->dev.game_noise.get() : nullptr, c.training ? e->dev.game_uniforms.get() : nullptr,
-                    e->stamps ? e->dev.stamps.get() : nullptr, s);
+                    e->stamps ? e->dev.stamps.get() : nullptr, packed, s);
   }
   NZ_HIP(e, hipGetLastError());
   if (c.training && have_next) {                            // the next round's draws, while the kernel runs
@@ -1382,6 +1584,22 @@ nz_status nz_net_forward(nz_engine* e, const float* states_dev, int32_t batch, f
   Span sp(e, as_stream(stream), 1);
   launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, states_dev, nullptr, batch, logits_dev,
              value_dev, probs_dev, nullptr, as_stream(stream));
+  NZ_HIP(e, hipGetLastError());
+  return NZ_OK;
+}
+
+nz_status nz_net_forward_packed(nz_engine* e, const float* states_dev, int32_t batch, int32_t positions_per_pass,
+                                float* logits_dev, float* value_dev, float* probs_dev, void* stream) {
+  if (!e || !states_dev || !logits_dev || !value_dev) return NZ_ERR_ARG;
+  if (!e->have_net) return fail(e, NZ_ERR_STATE, "no network: call nz_engine_set_weights first");
+  if (batch <= 0) return NZ_OK;
+  NZ_HIP(e, hipSetDevice(e->device));
+  const NetProgram* prog = nullptr;
+  const nz_status st = packed_program(e, positions_per_pass, &prog);
+  if (st != NZ_OK) return st;
+  Span sp(e, as_stream(stream), 1);
+  launch_net_packed(prog, positions_per_pass, net_weights(e), states_dev, batch, logits_dev, value_dev, probs_dev,
+                    as_stream(stream));
   NZ_HIP(e, hipGetLastError());
   return NZ_OK;
 }

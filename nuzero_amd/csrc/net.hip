@@ -2,6 +2,7 @@
 // boards (Neural_Networks/Network_Manager.py:46-64), one workgroup per 16
 // positions.  The arithmetic is net_dev.hpp's net_tile.
 #include "net_dev.hpp"
+#include "net_packed_dev.hpp"
 
 namespace nz {
 namespace {
@@ -46,6 +47,32 @@ __global__ __launch_bounds__(NET_THREADS) void net_kernel(const NetProgram* __re
                    STAMPS ? stamps + blockIdx.x * 4 : nullptr);
 }
 
+// The same outputs from the packed pass (net_packed_dev.hpp): one workgroup per P positions, `prog` compiled for P.
+__global__ __launch_bounds__(NET_THREADS) void net_packed_kernel(const NetProgram* __restrict__ prog, int P,
+                                                                 const float* __restrict__ W,
+                                                                 const float* __restrict__ states, int in_channels,
+                                                                 int count, int policy_channels,
+                                                                 float* __restrict__ logits, float* __restrict__ value) {
+  __shared__ __attribute__((aligned(16))) float lds[NET_LDS_FLOATS];
+  float* const inp = lds + NET_BUFFERS * ACT_FLOATS;
+  const int tile0 = blockIdx.x * P;
+  if (tile0 >= count) return;
+  for (int idx = threadIdx.x; idx < NET_BUFFERS * ACT_FLOATS; idx += NET_THREADS) lds[idx] = 0.0f;
+  for (int idx = threadIdx.x; idx < STRIP_FLOATS; idx += NET_THREADS) lds[NET_LDS_FLOATS - STRIP_FLOATS + idx] = 0.0f;
+  // input planes -> inp[cell][pos][4]; rows P .. 15 are not read
+  for (int idx = threadIdx.x; idx < CELLS * POS * 4; idx += NET_THREADS) {
+    const int c = idx & 3, pp = (idx >> 2) & 15, cell = idx >> 6;
+    const int gp = tile0 + pp;
+    float v = 0.0f;
+    if (pp < P && gp < count && c < in_channels) v = states[((size_t)gp * in_channels + c) * CELLS + cell];
+    inp[idx] = v;
+  }
+  __syncthreads();
+  const int left = count - tile0;
+  net_tile_packed(prog, W, lds, inp, P, policy_channels, left < P ? left : P,
+                  logits + (size_t)tile0 * policy_channels * CELLS, value + tile0);
+}
+
 // scipy softmax over each position's logits (Explorer.py:159), numpy sum order for n = 9
 __global__ void softmax_kernel(const float* __restrict__ logits, float* __restrict__ probs, int batch, int n) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -82,6 +109,16 @@ void launch_net(const NetProgram* prog_dev, int n_layers, const float* packed_we
   if (probs != nullptr)
     hipLaunchKernelGGL(softmax_kernel, dim3((max_positions + 255) / 256), dim3(256), 0, s, logits, probs,
                        max_positions, 9);
+}
+
+void launch_net_packed(const NetProgram* prog_dev, int P, const float* packed_weights, const float* states, int batch,
+                       float* logits, float* value, float* probs, hipStream_t s) {
+  const int blocks = (batch + P - 1) / P;
+  if (blocks <= 0) return;
+  hipLaunchKernelGGL(net_packed_kernel, dim3(blocks), dim3(NET_THREADS), 0, s, prog_dev, P, packed_weights, states, 2,
+                     batch, 1, logits, value);
+  if (probs != nullptr)
+    hipLaunchKernelGGL(softmax_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, logits, probs, batch, 9);
 }
 
 }  // namespace nz

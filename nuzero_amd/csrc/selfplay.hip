@@ -32,6 +32,7 @@
 // `desync`, stops, and is replayed by the lock-step path, which asks the device
 // for the child count before drawing.
 #include "net_dev.hpp"
+#include "net_packed_dev.hpp"
 #include "tree_dev.hpp"
 
 namespace nz {
@@ -153,6 +154,20 @@ __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W
                         POS, out_logits, out_value, nullptr, steal);       // (true: with the solo lists' whole-tile job)
 }
 
+// The packed pass in net_phase's place (net_packed_dev.hpp): `prog` is a packed program for the workgroup's P =
+// slots_per_wg <= NET_PACKED_MAX game slots, rows 0 .. P - 1 of `inp`, `out_logits` and `out_value`.
+__device__ __forceinline__ void net_phase_packed(const NetProgram* prog, const float* W, float* lds, const float* inp,
+                                                 float* out_logits, float* out_value, int P) {
+  auto uniform = [](const void* q) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(q);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
+  };
+  net_tile_packed(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds, inp, P, 1, P,
+                  out_logits, out_value);
+}
+
 // A row that hit the per-cycle cap: it can go on simulating without the network
 __device__ __forceinline__ bool row_capped(const RowState& s) {
   return s.alive && !s.pending && s.move >= 0 && s.sims_left > 0;
@@ -224,7 +239,9 @@ __device__ __forceinline__ int burst_under_pass(int32_t (*park_row)[POS], int32_
   return done;
 }
 
-template <bool STAMPS>
+// PACKED: the network phase is the packed pass for slots_per_wg <= NET_PACKED_MAX rows.  It has no stealing partner: no
+// wave sits a pass out (the host keeps burst_under_net off for such an engine).
+template <bool STAMPS, bool PACKED = false>
 __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
   __shared__ __attribute__((aligned(16))) float lds[NET_LDS_FLOATS + POS * TTT_ACTIONS + POS];
   float* const inp = lds + NET_BUFFERS * ACT_FLOATS;
@@ -444,7 +461,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     row_pending = pending;
     row_cap = row_capped(st);
     }
-    if (p.burst_under_net != 0) {
+    if (!PACKED && p.burst_under_net != 0) {
       const int wave_cap = __builtin_amdgcn_ballot_w64(row_cap) != 0ull ? 1 : 0;
       if ((tid & 63) == 0) s_capped[tid >> 6] = wave_cap;
     }
@@ -467,7 +484,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     // when both have one; the other runs both halves of the SIMD's tile.  (s_capped is written again only after the
     // pass's barriers.)  Uniform per wave.
     int absent = 0, steal = 0;
-    if (p.burst_under_net != 0) {
+    if (!PACKED && p.burst_under_net != 0) {
       const int w = tid >> 6, lo = w & (NET_WAVES / 2 - 1);
       const int cap_lo = s_capped[lo], cap_hi = s_capped[lo + NET_WAVES / 2];
       const int out = p.burst_under_net == 2 ? lo : cap_lo ? lo : cap_hi ? lo + NET_WAVES / 2 : -1;   // 2: the test hook
@@ -483,7 +500,10 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     }
 
     // ------------------------------ net phase ----------------------------------
-    if (absent) {
+    if constexpr (PACKED) {
+      const SelfplayArgs& na = kernel_args();
+      net_phase_packed(na.prog, na.W, lds, inp, out_logits, out_value, na.p.slots_per_wg);
+    } else if (absent) {
       const int done = burst_under_pass(park_row, park_lane, tab, lds, out_value);
       if constexpr (STAMPS) {
         if (done > 0 && (tid & (LANES_PER_GAME - 1)) == 0) atomicAdd(&s_burst_sims, done);
@@ -533,11 +553,13 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
 int selfplay_blocks(int n_slots, int slots_per_wg) { return (n_slots + slots_per_wg - 1) / slots_per_wg; }
 
 void launch_selfplay(const TreeParams& p, const NetProgram* prog_dev, int n_layers, const float* weights,
-                     const double* noise, const double* uniforms, unsigned long long* stamps, hipStream_t s) {
+                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s) {
   const int blocks = selfplay_blocks(p.n_slots, p.slots_per_wg);
   (void)n_layers;
   const SelfplayArgs a{p, prog_dev, weights, noise, uniforms, stamps};
-  if (stamps != nullptr) hipLaunchKernelGGL(selfplay_kernel<true>, dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  if (packed && stamps != nullptr) hipLaunchKernelGGL((selfplay_kernel<true, true>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  else if (packed) hipLaunchKernelGGL((selfplay_kernel<false, true>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  else if (stamps != nullptr) hipLaunchKernelGGL(selfplay_kernel<true>, dim3(blocks), dim3(NET_THREADS), 0, s, a);
   else hipLaunchKernelGGL(selfplay_kernel<false>, dim3(blocks), dim3(NET_THREADS), 0, s, a);
 }
 

@@ -113,17 +113,30 @@ class SelfPlayEngine:
         check(lib.nz_engine_net_matrix_flops(self._h, byref(a), byref(b)), self._h)
         return a.value, b.value
 
-    def net_forward(self, states, want_probs=True):
+    def net_forward(self, states, want_probs=True, positions_per_pass=None):
         """Network_Manager.inference for a float32 [B, 2, 3, 3] batch on the GPU.
-        Returns (logits [B, 9], value [B], probs [B, 9] or None)."""
+        Returns (logits [B, 9], value [B], probs [B, 9] or None).  positions_per_pass = P (1 .. 8): the same outputs
+        from the packed pass, one workgroup per P positions (nz_net_forward_packed)."""
         x = torch.as_tensor(states, dtype=torch.float32).to(self.device).contiguous()
         b = x.shape[0]
         logits = torch.empty((b, 9), dtype=torch.float32, device=self.device)
         value = torch.empty((b,), dtype=torch.float32, device=self.device)
         probs = torch.empty((b, 9), dtype=torch.float32, device=self.device) if want_probs else None
         with torch.cuda.device(self.device):
-            check(lib.nz_net_forward(self._h, _ptr(x), b, _ptr(logits), _ptr(value), _ptr(probs), _stream()), self._h)
+            if positions_per_pass is None:
+                check(lib.nz_net_forward(self._h, _ptr(x), b, _ptr(logits), _ptr(value), _ptr(probs), _stream()), self._h)
+            else:
+                check(lib.nz_net_forward_packed(self._h, _ptr(x), b, int(positions_per_pass), _ptr(logits), _ptr(value),
+                                                _ptr(probs), _stream()), self._h)
         return logits, value, probs
+
+    @property
+    def positions_per_pass(self):
+        """Positions a network pass of play()'s kernel is sized for: 16, or the games per workgroup of an engine that
+        takes the packed pass (nz_engine_positions_per_pass)."""
+        v = c_int32(0)
+        check(lib.nz_engine_positions_per_pass(self._h, byref(v)), self._h)
+        return v.value
 
     def net_forward_stamps(self, states):
         """Diagnostic build: mean ticks wave 0 of a workgroup spends computing jobs / waiting at barriers."""
