@@ -1766,6 +1766,8 @@ __global__ __launch_bounds__(64) void compact_kernel(SearchParams p) {
       if (lane >= d) inc += o;
     }
     const int total = __shfl(inc, 63, 64);
+    // (cannot trigger: the subtree copied here is part of a tree that fits the other half, and the halves are the same
+    // size -- the searches' own checks report a full arena.  Kept as the bound on the stores below; no test reaches it.)
     if (count + total > p.half_cap) {                  // uniform
       if (lane == 0) atomicOr(p.error_flag, 1);
       return;

@@ -74,6 +74,34 @@ class Counters:
     def __init__(self):
         self.simulations = 0
         self.expansions = 0     # evaluate() calls on non-terminal leaves
+        # How deep the descents went and how large the kept tree grew (measures only: nothing in the search reads them).
+        # A path's length is its number of nodes, the root (level 0) included.
+        self.longest_path = 0
+        self.path_lengths = {}              # length -> simulations whose path had that length
+        self.terminal_path_lengths = {}     # length -> those of them that ended in a terminal leaf
+        # the live tree after a move's search, at its largest over the run: 1 + sum of len(children) over every
+        # expanded node reachable from the move's root
+        self.peak_nodes = 0
+
+    def record_path(self, length, terminal):
+        self.longest_path = max(self.longest_path, length)
+        self.path_lengths[length] = self.path_lengths.get(length, 0) + 1
+        if terminal:
+            self.terminal_path_lengths[length] = self.terminal_path_lengths.get(length, 0) + 1
+
+    def simulations_deeper_than(self, length, terminal=False):
+        hist = self.terminal_path_lengths if terminal else self.path_lengths
+        return sum(n for plen, n in hist.items() if plen > length)
+
+
+def live_nodes(root):
+    """1 + sum of len(children) over every expanded node reachable from `root`: the nodes of root's subtree."""
+    count, stack = 1, [root]
+    while stack:
+        node = stack.pop()
+        count += len(node.children)
+        stack.extend(c for c in node.children if c.children)
+    return count
 
 
 class Explorer:
@@ -104,6 +132,8 @@ class Explorer:
                 n.visit_count += 1
                 n.value_sum += value
             self.counters.simulations += 1
+            self.counters.record_path(len(path), node.terminal_value is not None)
+        self.counters.peak_nodes = max(self.counters.peak_nodes, live_nodes(root))
         bias = self.exploration_bias(root)
         action = self.select_action(game, root)
         return action, root.child(action), bias

@@ -81,7 +81,8 @@ ORACLE_NET_TOL = 1e-5
 def replay_game(args):
     """(config path, search config, seed, training, digests [n,8], probs [n,A], values [n], max_moves[, options]) ->
     trace dict.  options (optional): "per_game" (bool), "oracle_net" ((weights, arch, depth) of a feed-forward board
-    net: FeedForwardRef).  Top-level so it can run in a worker process (CPU only: nothing here touches the GPU)."""
+    net: FeedForwardRef).  The result also holds the run's path-depth measures and the live tree's peak node count.
+    Top-level so it can run in a worker process (CPU only: nothing here touches the GPU)."""
     config_path, search, seed, training, digests, probs, values, max_moves = args[:8]
     options = args[8] if len(args) > 8 and args[8] else {}
     from oracle import search as osearch
@@ -136,7 +137,11 @@ def replay_game(args):
     return {"trace": trace, "length": game.length, "terminal": bool(game.is_terminal()),
             "terminal_value": game.terminal_value if game.is_terminal() else None,
             "evaluations_used": cursor[0], "evaluations_recorded": len(values),
-            "oracle_net_worst": tuple(worst) if ref is not None else None}
+            "oracle_net_worst": tuple(worst) if ref is not None else None,
+            # how deep the descents went and how large the kept tree grew (oracle/search.py's Counters)
+            "longest_path": explorer.counters.longest_path, "path_lengths": dict(explorer.counters.path_lengths),
+            "terminal_path_lengths": dict(explorer.counters.terminal_path_lengths),
+            "peak_nodes": explorer.counters.peak_nodes}
 
 
 def replay_games(jobs, workers=None):

@@ -21,10 +21,13 @@ GOLDEN = os.path.join(HERE, "golden")
 from test_gpu_scs_configs import a1_search, _net, _same_games, _game_properties   # noqa: E402
 
 
-def _replay_recorded(path, search, seeds, r, recs, games, label, training=True):
+def _replay_recorded(path, search, seeds, r, recs, games, label, training=True, outs_to=None):
+    """outs_to (a list): also hand the replays' result dicts (path-depth measures, peak node counts) to the caller."""
     from scs_replay import replay_games, assert_trace_equals_device
     jobs = [(path, search, seeds[g], training) + recs[g] + (None,) for g in games]
     outs = replay_games(jobs)
+    if outs_to is not None:
+        outs_to.extend(outs)
     moves = 0
     for g, out in zip(games, outs):
         assert out["evaluations_used"] == out["evaluations_recorded"], (label, g)
@@ -34,7 +37,7 @@ def _replay_recorded(path, search, seeds, r, recs, games, label, training=True):
     return moves
 
 
-def _oracle_net_on_leaves(path, w, arch, depth, hexnet, r, g, recs, n_check):
+def _oracle_net_on_leaves(path, w, arch, depth, hexnet, r, g, recs, n_check, value_activation="tanh"):
     """Replay game g through the oracle rules and compare the recorded evaluation of each root position (the first
     evaluation of a move whose root is not yet expanded is the root itself: only move 0; so instead every recorded
     leaf is matched by digest against the positions along the game) -- simpler and sufficient: the root positions of
@@ -43,7 +46,7 @@ def _oracle_net_on_leaves(path, w, arch, depth, hexnet, r, g, recs, n_check):
     from oracle.net import FeedForwardRef, HexNetRef
     from oracle.scs import ScsConfig, ScsGame
     from scs_replay import image_mix_digest
-    ref = HexNetRef(w, arch, depth) if hexnet else FeedForwardRef(w, arch, depth)
+    ref = HexNetRef(w, arch, depth) if hexnet else FeedForwardRef(w, arch, depth, value_activation)
     dig, probs, values = recs[g]
     index = {(int(d[0]), int(d[1])): i for i, d in enumerate(dig)}
     og = ScsGame(ScsConfig(path))
