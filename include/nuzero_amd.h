@@ -690,6 +690,62 @@ nz_status nz_scs_agent_record(nz_scs_search* h, int32_t side, const int32_t* gam
 nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, int32_t slot, int32_t* count, uint64_t* digests_host,
                                    float* probs_host, float* values_host);
 
+/* ---- SCS evaluation matches from opening positions ---------------------------------------------------------------------
+ * Evaluation agents are deterministic (no noise, max action), so on ONE map nz_scs_match_play with two MCTS agents, or
+ * nz_scs_agent_match_play with MCTS against the bare policy, plays one game n_games times.  The remedy that leaves the
+ * game alone: start match g at the position a prefix of g's own actions leads to.  No reference counterpart (harness
+ * rules); Tic-Tac-Toe's twin is nz_engine_match_play_from.
+ * nz_scs_openings (host memory, copied before the call returns): actions int32 [n_games][max_plies], match g's prefix
+ * in its first n_plies[g] entries (the rest is not read); n_plies int32 [n_games], NULL: every match has max_plies.
+ * nz_scs_search_reset_to: nz_scs_search_reset, then one wavefront per match replays the prefix through the legal mask
+ * and the step.  Afterwards match g stands at its position, its tree is the unexpanded root (MctsAgent.new_game, then
+ * choose_action, on a game stepped there), and its records hold the prefix at the game's own decision numbers:
+ * actions [g][ply] of nz_scs_search_export, n_children and tree_size 0 for those plies (nobody searched them);
+ * nz_scs_search_last_actions gives the prefix's last action.  NULL openings or max_plies == 0 is nz_scs_search_reset
+ * itself.  Refused with NZ_ERR_ARG before any launch, the engine untouched: a NULL handle or actions, max_plies < 0 or
+ * above max_moves of nz_scs_search_limits, an n_plies[g] outside 0 .. max_plies, an action outside 0 .. A-1 within a
+ * match's plies (the message names match and ply).  The call then synchronises and reads one error word per match: an
+ * action that is not legal in its position, or a game that ended before its prefix did, returns NZ_ERR_ARG with the
+ * first such match, its ply, action and reason in nz_scs_search_last_error, and the engine is left as after
+ * nz_scs_search_reset: nothing of a refused call survives.
+ * nz_scs_match_play_from / nz_scs_agent_match_play_from: nz_scs_match_play / nz_scs_agent_match_play with every match
+ * started at its opening, the same openings in both engines of a match; the functions without _from are their NULL
+ * case and enqueue exactly what they always did.  Refused openings are refused before anything is reset.  max_moves
+ * counts the round's own decisions, not the opening's plies.  The mover rule is unchanged (agent 1 moves for player
+ * index 1), so a prefix decides who moves first.  A random side's stream starts fresh at its first own decision after
+ * the opening.  The match record, the engines' records and nz_scs_agent_match_decisions stay indexed by the game's
+ * decision number; the match record holds the opening's plies there (a scripted side's own record holds -1 / 0: it did
+ * not decide them), so the tally's check for gaps stands as it is.
+ * nz_scs_openings_draw: match g owns np.random.RandomState(seeds_host[g]) (uint32 [n_games]; a stream apart from the
+ * map's and the random agents') and plays the random agent's rule from the start -- k = rs.randint(n_legal), n_legal ==
+ * 1 draws nothing, the k-th legal action in ascending flat index -- for `plies` plies (1 .. max_moves) or to the
+ * game's end, on the match's own map where maps are per game.  Host outputs: actions_out int32 [n_games][plies] (-1 past
+ * a prefix's end), n_plies_out int32 [n_games].  Touches no game of the engine.  Synchronises.
+ * nz_scs_openings_expand: one level of the enumeration of all openings.  frontier_host int32 [n_prefixes][depth]
+ * (depth >= 0; depth 0: the start, frontier_host may be NULL): each prefix is replayed from the start.  counts_host
+ * int32 [n_prefixes] receives the number of legal actions after each prefix (0: the game is over there).  With
+ * children_host non-NULL (keys_host too) the call also writes, at the exclusive scan of the counts, the child prefixes
+ * children_host int32 [sum of counts][depth + 1] in ascending action order and keys_host uint64 [sum of counts][2],
+ * the 128-bit digest of each child position's planes (the digest nz_scs_search_record_read reports for a leaf; equal
+ * keys: positions the network and the rules cannot tell apart, so the two orders of placing two units of one type count
+ * once -- the inference cache's state hash would tell them apart) -- call once without them to size the arrays.  A prefix that is not a
+ * legal sequence is NZ_ERR_ARG naming prefix and ply.  Refused with NZ_ERR_STATE while per-game maps are set: one
+ * frontier belongs to one map.  Touches no game of the engine.  Synchronises. */
+typedef struct nz_scs_openings {
+  const int32_t* actions;
+  const int32_t* n_plies;
+  int32_t max_plies;
+} nz_scs_openings;
+nz_status nz_scs_search_reset_to(nz_scs_search* h, const nz_scs_openings* openings, void* stream);
+nz_status nz_scs_match_play_from(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
+                                 const nz_scs_openings* openings, int32_t max_moves, void* stream);
+nz_status nz_scs_agent_match_play_from(nz_scs_search* h, const nz_scs_agent* p1, const nz_scs_agent* p2,
+                                       const nz_scs_openings* openings, int32_t max_moves, void* stream);
+nz_status nz_scs_openings_draw(nz_scs_search* h, const uint32_t* seeds_host, int32_t plies, int32_t* actions_out,
+                               int32_t* n_plies_out, void* stream);
+nz_status nz_scs_openings_expand(nz_scs_search* h, const int32_t* frontier_host, int32_t n_prefixes, int32_t depth,
+                                 int32_t* counts_host, int32_t* children_host, uint64_t* keys_host, void* stream);
+
 /* ---- Tic-Tac-Toe evaluation matches played inside the library ---------------------------------------------------------
  * Tester.Test_using_agents on Tic-Tac-Toe: n_games matches between side 1 (moves for player 1, the first mover, as in
  * oracle/agents.py play_match) and side 2, each an NZ_AGENT_MCTS, NZ_AGENT_POLICY or NZ_AGENT_RANDOM.  The scripted

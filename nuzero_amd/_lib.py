@@ -80,6 +80,10 @@ class ScsAgent(Structure):
     _fields_ = [("kind", c_int32), ("net", c_void_p), ("seeds_host", c_void_p)]
 
 
+class ScsOpenings(Structure):
+    _fields_ = [("actions", c_void_p), ("n_plies", c_void_p), ("max_plies", c_int32)]
+
+
 class TttMatchResult(Structure):
     _fields_ = [("actions", c_void_p), ("lengths", c_void_p), ("outcomes", c_void_p), ("agent_actions", c_void_p * 2),
                 ("agent_n_legal", c_void_p * 2), ("tally4_host", POINTER(c_int64))]
@@ -192,6 +196,12 @@ SIGNATURES = {
     "nz_scs_agent_match_decisions": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_agent_record": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32]),
     "nz_scs_agent_record_read": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "nz_scs_search_reset_to": (c_int32, [c_void_p, POINTER(ScsOpenings), c_void_p]),
+    "nz_scs_match_play_from": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(ScsOpenings), c_int32, c_void_p]),
+    "nz_scs_agent_match_play_from": (c_int32, [c_void_p, POINTER(ScsAgent), POINTER(ScsAgent), POINTER(ScsOpenings), c_int32,
+                                               c_void_p]),
+    "nz_scs_openings_draw": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nz_scs_openings_expand": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_engine_match_play": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, POINTER(TttMatchResult),
                                        c_void_p]),
     "nz_engine_match_streams": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),

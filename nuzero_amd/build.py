@@ -26,6 +26,7 @@ UNITS = [
     ("scs_search.hip", ["-ffp-contract=off"]),
     ("scs_draw.hip", ["-ffp-contract=off"]),
     ("scs_agents.hip", ["-ffp-contract=off"]),
+    ("scs_openings.hip", ["-ffp-contract=off"]),
     ("ttt_agents.hip", ["-ffp-contract=off"]),
     ("boardnet.hip", []),
     ("replay.hip", ["-ffp-contract=off"]),

@@ -98,31 +98,6 @@ __global__ __launch_bounds__(64) void agent_image_kernel(AgentArgs a, int side) 
   }
 }
 
-// inclusive prefix sum over the wavefront
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// The index of the k-th set bit (k < the number of set bits) of the mask whose words `base + lane` the lanes hold in w,
-// or -1 when it lies past these 64 words (k is then reduced by their count): ballot and popcount prefix.
-__device__ __forceinline__ int kth_set_bit(uint32_t w, int base, int& k, int lane) {
-  const int c = __popc(w), inc = wave_scan(c, lane);
-  const int total = __shfl(inc, 63, 64);
-  if (k >= total) { k -= total; return -1; }
-  const int owner = __ffsll((long long)__ballot(inc > k)) - 1;       // the first lane whose words reach past k
-  int bit = -1;
-  if (lane == owner) {
-    uint32_t x = w;
-    for (int i = k - (inc - c); i > 0; --i) x &= x - 1;               // (at most 31 rounds)
-    bit = (base + lane) * 32 + __ffs((int)x) - 1;
-  }
-  return __shfl(bit, owner, 64);
-}
-
 __global__ __launch_bounds__(64) void agent_act_kernel(AgentArgs a) {
   __shared__ __align__(16) ScsRules R;
   __shared__ ScsState sc;

@@ -30,6 +30,7 @@
 #include "../../include/nuzero_amd.h"
 #include "scs_dev.hpp"
 #include "scs_agents.hpp"
+#include "scs_openings.hpp"
 #include "boardnet_internal.h"
 #include "hip_own.hpp"
 
@@ -1973,6 +1974,14 @@ struct AgentBufs {                // nz_scs_agent_match_play
   }
 };
 
+struct OpeningBufs {              // nz_scs_search_reset_to, nz_scs_openings_draw / _expand (grown, never shrunk)
+  DevBuf<int32_t> actions, n_plies, err;         // the matches' prefixes [G][max_plies], their lengths and error words [G]
+  DevBuf<uint32_t> seeds;                        // draw: [G]
+  DevBuf<int32_t> counts, offsets, children;     // expand: per prefix [n], the child prefixes [total][depth + 1]
+  DevBuf<uint64_t> keys;                         // expand: [total][2]
+  DevBuf<float> planes;                          // expand: a position's planes per prefix [n][channels][tiles]
+};
+
 }  // namespace
 
 struct nz_scs_search {
@@ -2017,6 +2026,7 @@ struct nz_scs_search {
   MatchBufs match;
   const nz_scs_search* match_peer = nullptr;    // agent 2 of the last round (compared, never followed)
   AgentBufs agents;
+  OpeningBufs openings;
 };
 
 namespace {
@@ -2049,6 +2059,39 @@ nz_status check_flag(nz_scs_search* h, hipStream_t s) {
   S_HIP(h, hipStreamSynchronize(s));
   if (f) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s)", f, FLAG_TEXT);
   return NZ_OK;
+}
+// What nz_scs_search_reset_to refuses before any launch (nuzero_amd.scs_positions.check_openings is its twin); false: the
+// message is in the handle.  NULL openings and max_plies == 0 are the plain reset.
+bool openings_ok(nz_scs_search* h, const nz_scs_openings* o) {
+  if (!o || o->max_plies == 0) return true;
+  const int G = h->n_games, P = o->max_plies, A = h->p.num_actions;
+  if (!o->actions) return sfail(h, NZ_ERR_ARG, "openings without actions") == NZ_OK;
+  if (P < 0 || P > h->p.max_moves)
+    return sfail(h, NZ_ERR_ARG, "openings of %d plies: 0 .. %d (the decisions a game's records hold)", P, h->p.max_moves) == NZ_OK;
+  for (int g = 0; g < G; ++g) {
+    const int np = o->n_plies ? o->n_plies[g] : P;
+    if (np < 0 || np > P)
+      return sfail(h, NZ_ERR_ARG, "match %d: an opening of %d plies, the openings hold 0 .. %d (ply %d is not there)", g, np, P,
+                   np < 0 ? np : P) == NZ_OK;
+    for (int ply = 0; ply < np; ++ply) {
+      const int a = o->actions[(size_t)g * P + ply];
+      if (a < 0 || a >= A) return sfail(h, NZ_ERR_ARG, "match %d, ply %d: action %d outside 0 .. %d", g, ply, a, A - 1) == NZ_OK;
+    }
+  }
+  return true;
+}
+const char* opening_reason(int32_t e) {
+  switch (nz::opening_err_reason(e)) {
+    case nz::OPENING_ERR_ILLEGAL: return "the action is not legal in this position";
+    case nz::OPENING_ERR_GAME_OVER: return "the game was over before the prefix ended";
+    case nz::OPENING_ERR_LENGTH: return "the prefix runs past the decisions the records hold";
+    case nz::OPENING_ERR_NO_LEGAL: return "a live position without a legal action";
+    case nz::OPENING_ERR_CAP: return "the randint rejection cap was reached";
+  }
+  return "unknown";
+}
+nz::OpeningGames opening_games(const nz_scs_search* h) {
+  return nz::OpeningGames{h->p.rules, h->p.rules_row, h->p.num_actions};
 }
 }  // namespace
 
@@ -3166,6 +3209,12 @@ __global__ void match_tally_kernel(MatchSide a, MatchSide b, int n, int max_move
 
 extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
                                        int32_t max_moves, void* stream) {
+  return nz_scs_match_play_from(a1, net1, a2, net2, nullptr, max_moves, stream);
+}
+
+// nz_scs_match_play with every match started at its opening (scs_openings.hip), the same one in both engines.
+extern "C" nz_status nz_scs_match_play_from(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
+                                            const nz_scs_openings* openings, int32_t max_moves, void* stream) {
   if (!a1 || !a2 || !net1 || !net2) return sfail(a1, NZ_ERR_ARG, "null argument");
   if (a1 == a2) return sfail(a1, NZ_ERR_ARG, "a match needs two engines: each agent keeps its own trees");
   a1->match_peer = nullptr;
@@ -3174,6 +3223,7 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
     return sfail(a1, NZ_ERR_ARG, "the two engines hold %d and %d games on devices %d and %d", a1->n_games, a2->n_games, a1->device, a2->device);
   if (memcmp(&a1->host_rules, &a2->host_rules, sizeof(ScsRules)) != 0)
     return sfail(a1, NZ_ERR_ARG, "the two engines were created with different game descriptions");
+  if (!openings_ok(a1, openings)) return NZ_ERR_ARG;      // (refused before anything is reset; a2 has a1's description)
   S_HIP(a1, hipSetDevice(a1->device));
   hipStream_t s1 = (hipStream_t)stream;
   const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
@@ -3217,9 +3267,14 @@ extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_
   hipStream_t s2 = two_streams ? m.stream.get() : s1;
   int32_t* const forced1 = m.forced.get();
   int32_t* const forced2 = m.forced.get() + G;
-  if (nz_status st = nz_scs_search_reset(a1, stream)) return st;
-  if (nz_status st = on2(nz_scs_search_reset(a2, stream))) return st;
+  if (nz_status st = nz_scs_search_reset_to(a1, openings, stream)) {
+    (void)nz_scs_search_reset(a2, stream);                // a refused opening leaves both engines at the start
+    return st;
+  }
+  if (nz_status st = on2(nz_scs_search_reset_to(a2, openings, stream))) return st;
   S_HIP(a1, hipMemsetAsync(m.actions.get(), 0xFF, (size_t)G * MAX_MOVES * sizeof(int32_t), s1));    // -1: not played
+  if (openings && openings->max_plies > 0)     // the opening's plies at their decision numbers: all a fresh engine's record holds
+    S_HIP(a1, hipMemcpyAsync(m.actions.get(), a1->p.rec_action, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s1));
   a1->waves = a2->waves = 0;
   a1->round_games = a2->round_games = 0;
   const MatchSide m1 = match_side(a1->p), m2 = match_side(a2->p);
@@ -3322,7 +3377,14 @@ void agent_args(nz_scs_search* h, AgentArgs* a) {
 
 extern "C" nz_status nz_scs_agent_match_play(nz_scs_search* h, const nz_scs_agent* p1, const nz_scs_agent* p2, int32_t max_moves,
                                              void* stream) {
+  return nz_scs_agent_match_play_from(h, p1, p2, nullptr, max_moves, stream);
+}
+
+// nz_scs_agent_match_play with every match started at its opening (scs_openings.hip).
+extern "C" nz_status nz_scs_agent_match_play_from(nz_scs_search* h, const nz_scs_agent* p1, const nz_scs_agent* p2,
+                                                  const nz_scs_openings* openings, int32_t max_moves, void* stream) {
   if (!h || !p1 || !p2) return sfail(h, NZ_ERR_ARG, "null argument");
+  if (!openings_ok(h, openings)) return NZ_ERR_ARG;       // (refused before anything is reset)
   const nz_scs_agent* const ag[2] = {p1, p2};
   h->agents.kinds[0] = h->agents.kinds[1] = -1;
   int mcts = -1;
@@ -3377,7 +3439,7 @@ extern "C" nz_status nz_scs_agent_match_play(nz_scs_search* h, const nz_scs_agen
       if (nz_boardnet_input_rows(ag[i]->net, &sd.net_rows, &sd.row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "agent %d: bad network handle", i + 1);
     }
   }
-  if (nz_status st = nz_scs_search_reset(h, stream)) return st;
+  if (nz_status st = nz_scs_search_reset_to(h, openings, stream)) return st;
   h->waves = 0;
   h->round_games = 0;
   h->match_peer = nullptr;
@@ -3517,5 +3579,122 @@ extern "C" nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, in
   if (digests_host) S_HIP(h, hipMemcpy(digests_host, sb.hook_digest.get() + 2 * at, n * 16, hipMemcpyDeviceToHost));
   if (probs_host) S_HIP(h, hipMemcpy(probs_host, sb.hook_probs.get() + at * A, n * A * 4, hipMemcpyDeviceToHost));
   if (values_host) S_HIP(h, hipMemcpy(values_host, sb.hook_value.get() + at, n * 4, hipMemcpyDeviceToHost));
+  return NZ_OK;
+}
+
+// ---- matches from opening positions (scs_openings.hip) -----------------------------------------------------------------
+// The host side of the three opening kernels: the checks that need no launch, the copies, and the error words read back.
+extern "C" nz_status nz_scs_search_reset_to(nz_scs_search* h, const nz_scs_openings* o, void* stream) {
+  if (!h) return NZ_ERR_ARG;
+  if (!o || o->max_plies == 0) return nz_scs_search_reset(h, stream);
+  if (!openings_ok(h, o)) return NZ_ERR_ARG;
+  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
+  S_HIP(h, hipSetDevice(h->device));
+  const hipStream_t s = (hipStream_t)stream;
+  const int G = h->n_games, P = o->max_plies;
+  OpeningBufs& b = h->openings;
+  if (!(b.actions.ensure((size_t)G * P) && b.n_plies.ensure(G) && b.err.ensure(G)))
+    return sfail(h, NZ_ERR_HIP, "device allocation failed (openings)");
+  std::vector<int32_t> np(G, P), err(G, 0);
+  if (o->n_plies) std::copy(o->n_plies, o->n_plies + G, np.begin());
+  S_HIP(h, hipMemcpyAsync(b.actions.get(), o->actions, (size_t)G * P * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  S_HIP(h, hipMemcpyAsync(b.n_plies.get(), np.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (nz_status st = nz_scs_search_reset(h, stream)) return st;
+  S_HIP(h, opening_apply_launch(opening_games(h), G, b.actions.get(), b.n_plies.get(), P, h->p.real, h->p.rec_action, h->p.max_moves,
+                                b.err.get(), s));
+  S_HIP(h, hipMemcpyAsync(err.data(), b.err.get(), (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipStreamSynchronize(s));             // (the openings are the caller's memory; the error words decide the status)
+  for (int g = 0; g < G; ++g) {
+    if (!err[g]) continue;
+    if (nz_status st = nz_scs_search_reset(h, stream)) return st;      // nothing of a refused call survives
+    S_HIP(h, hipStreamSynchronize(s));
+    const int ply = opening_err_ply(err[g]);
+    return sfail(h, NZ_ERR_ARG, "match %d, ply %d: action %d: %s", g, ply, ply < np[g] ? o->actions[(size_t)g * P + ply] : -1,
+                 opening_reason(err[g]));
+  }
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_openings_draw(nz_scs_search* h, const uint32_t* seeds_host, int32_t plies, int32_t* actions_out,
+                                          int32_t* n_plies_out, void* stream) {
+  if (!h || !seeds_host || !actions_out || !n_plies_out) return sfail(h, NZ_ERR_ARG, "null argument");
+  if (plies < 1 || plies > h->p.max_moves) return sfail(h, NZ_ERR_ARG, "openings of %d plies: 1 .. %d", plies, h->p.max_moves);
+  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
+  S_HIP(h, hipSetDevice(h->device));
+  const hipStream_t s = (hipStream_t)stream;
+  const int G = h->n_games;
+  if (h->n_game_rows > 0) {                      // every match on its own map, as the match calls set it
+    if (h->n_game_rows < G) return sfail(h, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)h->n_game_rows);
+    std::vector<int32_t> ident(G);
+    for (int g = 0; g < G; ++g) ident[g] = g;
+    S_HIP(h, hipStreamSynchronize(s));
+    S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  OpeningBufs& b = h->openings;
+  if (!(b.seeds.ensure(G) && b.actions.ensure((size_t)G * plies) && b.n_plies.ensure(G) && b.err.ensure(G)))
+    return sfail(h, NZ_ERR_HIP, "device allocation failed (openings)");
+  std::vector<int32_t> err(G, 0);
+  S_HIP(h, hipMemcpyAsync(b.seeds.get(), seeds_host, (size_t)G * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  S_HIP(h, opening_draw_launch(opening_games(h), G, b.seeds.get(), plies, b.actions.get(), b.n_plies.get(), b.err.get(), s));
+  S_HIP(h, hipMemcpyAsync(actions_out, b.actions.get(), (size_t)G * plies * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(n_plies_out, b.n_plies.get(), (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(err.data(), b.err.get(), (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  for (int g = 0; g < G; ++g)
+    if (err[g]) return sfail(h, NZ_ERR_OVERFLOW, "match %d, ply %d: %s", g, opening_err_ply(err[g]), opening_reason(err[g]));
+  return NZ_OK;
+}
+
+extern "C" nz_status nz_scs_openings_expand(nz_scs_search* h, const int32_t* frontier_host, int32_t n, int32_t depth,
+                                            int32_t* counts_host, int32_t* children_host, uint64_t* keys_host, void* stream) {
+  if (!h || n <= 0 || depth < 0 || !counts_host || (depth > 0 && !frontier_host) || ((children_host == nullptr) != (keys_host == nullptr)))
+    return sfail(h, NZ_ERR_ARG, "bad argument");
+  if (depth >= h->p.max_moves) return sfail(h, NZ_ERR_ARG, "prefixes of %d plies: 0 .. %d", depth, h->p.max_moves - 1);
+  if (h->n_game_rows > 0)
+    return sfail(h, NZ_ERR_STATE, "per-game maps are set: one frontier belongs to one map (draw openings per match instead)");
+  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
+  const int A = h->p.num_actions;
+  for (int f = 0; f < n; ++f)
+    for (int ply = 0; ply < depth; ++ply) {
+      const int a = frontier_host[(size_t)f * depth + ply];
+      if (a < 0 || a >= A) return sfail(h, NZ_ERR_ARG, "prefix %d, ply %d: action %d outside 0 .. %d", f, ply, a, A - 1);
+    }
+  S_HIP(h, hipSetDevice(h->device));
+  const hipStream_t s = (hipStream_t)stream;
+  OpeningBufs& b = h->openings;
+  if (!(b.actions.ensure(std::max<size_t>(1, (size_t)n * depth)) && b.counts.ensure(n) && b.offsets.ensure(n) && b.err.ensure(n)))
+    return sfail(h, NZ_ERR_HIP, "device allocation failed (openings)");
+  std::vector<int32_t> err(n, 0);
+  if (depth > 0) S_HIP(h, hipMemcpyAsync(b.actions.get(), frontier_host, (size_t)n * depth * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  const nz::OpeningGames og = opening_games(h);
+  S_HIP(h, opening_expand_launch(og, n, b.actions.get(), depth, h->p.max_moves, b.counts.get(), nullptr, 0, nullptr, nullptr, nullptr,
+                                 b.err.get(), s));
+  S_HIP(h, hipMemcpyAsync(counts_host, b.counts.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(err.data(), b.err.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  for (int f = 0; f < n; ++f)
+    if (err[f]) {
+      const int ply = opening_err_ply(err[f]);
+      return sfail(h, NZ_ERR_ARG, "prefix %d, ply %d: action %d: %s", f, ply, ply < depth ? frontier_host[(size_t)f * depth + ply] : -1,
+                   opening_reason(err[f]));
+    }
+  if (!children_host) return NZ_OK;
+  std::vector<int32_t> offsets(n);
+  int64_t total = 0;
+  for (int f = 0; f < n; ++f) {                  // the exclusive scan
+    offsets[f] = (int32_t)total;
+    total += counts_host[f];
+    if (total * (depth + 1) > (int64_t)1 << 30) return sfail(h, NZ_ERR_OVERFLOW, "more than 2^30 entries of child prefixes");
+  }
+  if (total == 0) return NZ_OK;
+  if (!(b.children.ensure((size_t)total * (depth + 1)) && b.keys.ensure((size_t)total * 2) &&
+        b.planes.ensure((size_t)n * h->host_rules.channels * h->host_rules.tiles)))
+    return sfail(h, NZ_ERR_HIP, "device allocation failed (%lld child prefixes)", (long long)total);
+  S_HIP(h, hipMemcpyAsync(b.offsets.get(), offsets.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  S_HIP(h, opening_expand_launch(og, n, b.actions.get(), depth, h->p.max_moves, b.counts.get(), b.offsets.get(), (int)total, b.children.get(),
+                                 b.keys.get(), b.planes.get(), b.err.get(), s));
+  S_HIP(h, hipMemcpyAsync(children_host, b.children.get(), (size_t)total * (depth + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipMemcpyAsync(keys_host, b.keys.get(), (size_t)total * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  S_HIP(h, hipStreamSynchronize(s));
   return NZ_OK;
 }

@@ -460,6 +460,29 @@ class ScsSelfPlay:
     def reset(self):
         self._check(lib.nz_scs_search_reset(self._h, self._stream()))
 
+    def _openings(self, start_actions, n_plies):
+        """start_actions / n_plies -> (nz_scs_openings or None, the arrays it points into); the host-side refusals are
+        scs_positions.check_openings' (ValueError, nothing launched)."""
+        if start_actions is None:
+            if n_plies is not None:
+                raise ValueError("n_plies without start_actions")
+            return None, None
+        from .scs_positions import check_openings
+        if len(start_actions) != self.n_games:
+            raise ValueError(f"{len(start_actions)} openings for {self.n_games} matches")
+        a, k = check_openings(start_actions, n_plies, self.cfg.num_actions, self.MAX_MOVES)
+        o = _lib.ScsOpenings(actions=a.ctypes.data, n_plies=k.ctypes.data, max_plies=a.shape[1])
+        return o, (a, k)
+
+    def reset_to(self, start_actions, n_plies=None):
+        """reset(), then game g replays its opening: start_actions int32 [G, max_plies] (flat action indices from the
+        start), n_plies [G] (None: every game has max_plies).  Every game then stands at its position with a fresh root,
+        status() and export() count the opening's plies as the game's own decisions, last_actions() gives each opening's
+        last action.  An action that is not legal where it is played, or a game that ends before its opening does, raises
+        NzError (NZ_ERR_ARG, naming match and ply) and leaves the engine as after reset()."""
+        o, keep = self._openings(start_actions, n_plies)
+        self._check(lib.nz_scs_search_reset_to(self._h, byref(o) if o is not None else None, self._stream()))
+
     def search(self, evaluator, noise=None):
         """Root noise (training engines; float64 [G, MAX_CHILDREN]) and the move's simulations for every live game;
         no action yet."""

@@ -8,9 +8,14 @@ engines search the position (on two streams), a hand-over kernel tells each engi
 counted there too.  Agent 1 moves when the game's player index is 1 (oracle/agents.py play_match); wins are the
 game's terminal values (+1: player 1).
 
-Evaluation agents are deterministic (no noise, max action), so matches on ONE map are copies of one game: a win rate
-means something on the reference's "Randomized" presets, `ScsGameConfig(path, per_game=True)`, one map per match
-drawn on the device from `seeds`.
+Evaluation agents are deterministic (no noise, max action), so matches on ONE map are copies of one game.  Two remedies:
+the reference's "Randomized" presets, `ScsGameConfig(path, per_game=True)`, one map per match drawn on the device from
+`seeds` -- which changes the game being evaluated -- or, on the map as it is, matches from opening positions:
+`play(..., start_actions=..., n_plies=...)` starts match i at the position a short prefix of its own actions leads to
+(nuzero_amd.scs_positions: every distinct position k plies into the game, or one opening per seed drawn by the random
+agent's rule), both agents from a fresh root there, and `ScsTester.test_from_openings` plays every such opening with
+both colour assignments and counts per agent (C ABI nz_scs_search_reset_to, nz_scs_match_play_from,
+nz_scs_agent_match_play_from, nz_scs_openings_draw, nz_scs_openings_expand).
 
 Cheaper opponents (C ABI nz_scs_agent_match_*): `ScsAgentMatch` plays the same rounds on ONE engine when at most one
 side is an MCTS agent and the others are the bare policy `("policy",)` or a random mover `("random",)` -- the
@@ -76,13 +81,18 @@ class ScsMatch:
         for a in self.agents:
             a.close()
 
-    def play(self, net1, net2, seeds=None, max_moves=None):
-        """One round: every match from the start to the end (or for `max_moves` decisions).  net1 / net2: the agents'
+    def play(self, net1, net2, seeds=None, max_moves=None, start_actions=None, n_plies=None):
+        """One round: every match from the start -- or, with `start_actions` (int32 [n_matches, max_plies], `n_plies`
+        per match or None: all max_plies; nuzero_amd.scs_positions), match i from the position its opening leads to,
+        both agents from a fresh root there -- to the end (or for `max_moves` decisions of the round's own; an opening's
+        plies are not counted).  The records stay by the game's decision number: "actions" holds the opening's plies,
+        "lengths" counts them.  net1 / net2: the agents'
         BoardNets (max_batch >= n_matches).  `seeds` (per_game configs: required, one per match): match i is played on
         the map `np.random.seed(seeds[i]); SCS_Game(config)` builds, drawn on the device in both engines (the draw is
         a pure function of the seed); `agents[0].game_maps` holds the maps for whoever replays a match.
         Returns a dict: "actions" int32 [N, T] (-1 past a match's end; T = the longest match), "lengths" [N],
-        "outcomes" [N] (terminal value from player 1's view; 0 while unfinished), "p1_wins", "p2_wins", "draws",
+        "outcomes" [N] (terminal value from player 1's view; 0 while unfinished), "finished" bool [N], "p1_wins",
+        "p2_wins", "draws" (player 1 is player index 0, the side AGENT 2 moves for: scs_positions.agent_results),
         "unfinished" (stopped at max_moves), "length_sum", "length_max"."""
         import torch
         from . import _lib
@@ -96,14 +106,18 @@ class ScsMatch:
             a1.set_games(seeds)
             a2.set_games(seeds)
         stream = c_void_p(torch.cuda.current_stream().cuda_stream)
-        a1._check(_lib.lib.nz_scs_match_play(a1._h, net1._h, a2._h, net2._h, int(max_moves or 0), stream))
+        o, keep = a1._openings(start_actions, n_plies)
+        if o is None:
+            a1._check(_lib.lib.nz_scs_match_play(a1._h, net1._h, a2._h, net2._h, int(max_moves or 0), stream))
+        else:
+            a1._check(_lib.lib.nz_scs_match_play_from(a1._h, net1._h, a2._h, net2._h, byref(o), int(max_moves or 0), stream))
         tally = _lib.ScsMatchTally()
         actions = torch.empty((self.n_matches, a1.MAX_MOVES), dtype=torch.int32, device=a1.device)
         a1._check(_lib.lib.nz_scs_match_result(a1._h, a2._h, byref(tally), c_void_p(actions.data_ptr()), stream))
         st = a1.status()
         out = {k: int(getattr(tally, k)) for k, _ in _lib.ScsMatchTally._fields_}
         out["actions"] = actions[:, :max(1, out["length_max"])].cpu().numpy()
-        out["lengths"], out["outcomes"] = st[:, 6].copy(), st[:, 5].copy()
+        out["lengths"], out["outcomes"], out["finished"] = st[:, 6].copy(), st[:, 5].copy(), st[:, 4] != 0
         return out
 
 
@@ -190,8 +204,10 @@ class ScsAgentMatch:
                 raise ValueError(f"{len(seeds)} seeds for {self.n_matches} matches")
         return seeds, per_side
 
-    def play(self, net1, net2, seeds=None, agent_seeds=None, max_moves=None):
-        """One round, as ScsMatch.play.  net1 / net2: the BoardNet of a policy or MCTS side (None for a random side).
+    def play(self, net1, net2, seeds=None, agent_seeds=None, max_moves=None, start_actions=None, n_plies=None):
+        """One round, as ScsMatch.play (`start_actions` / `n_plies`: match i from its opening; a random side's stream
+        starts fresh at its first own decision after it, and a scripted side's own record holds -1 / 0 at the
+        opening's plies: it did not decide them).  net1 / net2: the BoardNet of a policy or MCTS side (None for a random side).
         `agent_seeds` (random sides: required, one per match; with two random sides one list for both or a pair of
         lists): match i's random agent is RandomState(agent_seeds[i]), rebuilt every round.  Returns ScsMatch.play's
         dict plus "agent_actions" / "agent_n_legal": per side int32 [N, T] by decision number (-1 / 0 where the side
@@ -208,7 +224,11 @@ class ScsAgentMatch:
                             seeds_host=(s.ctypes.data if s is not None else None))
               for k, n, s in zip(self.kinds, nets, side_seeds)]
         stream = c_void_p(torch.cuda.current_stream().cuda_stream)
-        e._check(_lib.lib.nz_scs_agent_match_play(e._h, byref(ag[0]), byref(ag[1]), int(max_moves or 0), stream))
+        o, keep = e._openings(start_actions, n_plies)
+        if o is None:
+            e._check(_lib.lib.nz_scs_agent_match_play(e._h, byref(ag[0]), byref(ag[1]), int(max_moves or 0), stream))
+        else:
+            e._check(_lib.lib.nz_scs_agent_match_play_from(e._h, byref(ag[0]), byref(ag[1]), byref(o), int(max_moves or 0), stream))
         tally = _lib.ScsMatchTally()
         actions = torch.empty((self.n_matches, e.MAX_MOVES), dtype=torch.int32, device=e.device)
         e._check(_lib.lib.nz_scs_agent_match_result(e._h, byref(tally), c_void_p(actions.data_ptr()), stream))
@@ -216,7 +236,7 @@ class ScsAgentMatch:
         out = {k: int(getattr(tally, k)) for k, _ in _lib.ScsMatchTally._fields_}
         T = max(1, out["length_max"])
         out["actions"] = actions[:, :T].cpu().numpy()
-        out["lengths"], out["outcomes"] = st[:, 6].copy(), st[:, 5].copy()
+        out["lengths"], out["outcomes"], out["finished"] = st[:, 6].copy(), st[:, 5].copy(), st[:, 4] != 0
         out["agent_actions"], out["agent_n_legal"], out["agent_probs"] = [None, None], [None, None], [None, None]
         for i, kind in enumerate(self.kinds):
             if kind == "mcts":
@@ -264,24 +284,107 @@ class ScsTester:
 
     def __init__(self, config, device=0):
         self.config, self.device = config, device
-        self._match = None
+        self._match = None           # (key, ScsMatch or ScsAgentMatch) of the last call
+        self._exchanged = None       # the same pairing with the agents exchanged, while test_from_openings plays both
+        self.opening_rounds = None   # the play() results of the last test_from_openings (in the second, agent 1 is agent2)
+        self.openings = None         # its (start_actions, n_plies)
+
+    def close(self):
+        for m in (self._match, self._exchanged):
+            if m is not None:
+                m[1].close()
+        self._match = self._exchanged = None
+
+    def _match_of(self, agent1, agent2, n):
+        """The match of this pairing and size: the last one is kept, and beside it the one with the agents exchanged
+        (as TttTester._match_of); any other pairing closes both."""
+        (k1, c1), (k2, c2) = _agent_spec(agent1), _agent_spec(agent2)
+        scripted = (k1, k2) != ("mcts", "mcts")
+        key = (repr((k1, c1)), repr((k2, c2)), int(n)) if scripted else (repr(agent1), repr(agent2), int(n))
+        other = (repr((k2, c2)), repr((k1, c1)), int(n)) if scripted else (repr(agent2), repr(agent1), int(n))
+        if self._match is not None and self._match[0] == key:
+            return self._match[1]
+        if self._exchanged is not None and self._exchanged[0] == key:
+            self._match, self._exchanged = self._exchanged, self._match
+            return self._match[1]
+        if self._match is not None and self._match[0] == other and key != other:
+            if self._exchanged is not None:
+                self._exchanged[1].close()
+            self._exchanged, self._match = self._match, None
+        else:
+            self.close()
+        m = (ScsAgentMatch(self.config, (k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device)
+             if scripted else ScsMatch(self.config, c1, c2, n, device=self.device))
+        self._match = (key, m)
+        return m
 
     def test_using_agents(self, search_cfg_1, net1, search_cfg_2, net2, n, seeds=None, max_moves=None, agent_seeds=None):
-        (k1, c1), (k2, c2) = _agent_spec(search_cfg_1), _agent_spec(search_cfg_2)
-        scripted = (k1, k2) != ("mcts", "mcts")
-        key = (repr((k1, c1)), repr((k2, c2)), int(n)) if scripted else (repr(search_cfg_1), repr(search_cfg_2), int(n))
-        if self._match is None or self._match[0] != key:
-            if self._match is not None:
-                self._match[1].close()
-                self._match = None
-            m = (ScsAgentMatch(self.config, (k1, c1) if c1 else (k1,), (k2, c2) if c2 else (k2,), n, device=self.device)
-                 if scripted else ScsMatch(self.config, c1, c2, n, device=self.device))
-            self._match = (key, m)
-        if scripted:
-            r = self._match[1].play(net1, net2, seeds=seeds, agent_seeds=agent_seeds, max_moves=max_moves)
+        m = self._match_of(search_cfg_1, search_cfg_2, n)
+        if isinstance(m, ScsAgentMatch):
+            r = m.play(net1, net2, seeds=seeds, agent_seeds=agent_seeds, max_moves=max_moves)
         else:
-            r = self._match[1].play(net1, net2, seeds=seeds, max_moves=max_moves)
+            r = m.play(net1, net2, seeds=seeds, max_moves=max_moves)
         return r["p1_wins"], r["p2_wins"], r["draws"]
+
+    Test_using_agents = test_using_agents
+
+    def test_from_openings(self, agent1, net1, agent2, net2, plies=2, openings=None, opening_seeds=None, both_colours=True,
+                           max_moves=None, seeds=None, agent_seeds=None):
+        """Matches that differ from each other on one map, between agents that are deterministic: every match starts at
+        its own opening (nuzero_amd.scs_positions) --
+          * by default every distinct position `plies` plies into the game, once each (all_openings: 55 for two plies
+            of mirrored_5x5, the transposed placements counted once);
+          * `openings`: the caller's, an int array [n, max_plies] or a pair (actions, n_plies);
+          * `opening_seeds`: one opening per seed, drawn for `plies` plies by the random agent's rule (random_openings).
+        With `both_colours` a second round plays the same openings with the agents exchanged.  Per-game configs take
+        drawn openings only (`opening_seeds`, with the maps' `seeds`): a frontier belongs to one map.  `agent_seeds`
+        (a random agent): one per opening, used in both rounds.  Returns the tally counted per AGENT, not per side,
+        {"agent1_wins", "agent2_wins", "draws", "unfinished", "matches"} (scs_positions.agent_results: terminal value +1
+        is player index 0's win, and agent 1 of a round moves for player index 1).  The rounds' play() results are kept
+        in `opening_rounds` (in the second, agent 1 is `agent2`), the openings in `openings`."""
+        from .scs import ScsSelfPlay
+        from .scs_positions import agent_results, all_openings, random_openings
+        per_game = bool(getattr(self.config, "per_game", False))       # (a path is a one-map config)
+        if openings is not None and opening_seeds is not None:
+            raise ValueError("openings or opening_seeds, not both")
+        if per_game and opening_seeds is None:
+            raise ValueError("a per_game config takes drawn openings only (opening_seeds): every match has its own map")
+        n_plies = None
+        if openings is not None:
+            if isinstance(openings, tuple) and len(openings) == 2:
+                openings, n_plies = openings
+            start = np.asarray(openings)
+        elif opening_seeds is not None:
+            start = None                                    # drawn below, on the round's own engine
+            opening_seeds = list(opening_seeds)
+        else:
+            e = ScsSelfPlay(self.config, _NO_SEARCH, 1, training=False, device=self.device)
+            try:
+                start = all_openings(e, plies)
+            finally:
+                e.close()
+        n = len(opening_seeds) if start is None else len(start)
+        if n == 0:
+            raise ValueError("no opening to play")
+        rounds = []
+        pairs = (((agent1, net1), (agent2, net2)), ((agent2, net2), (agent1, net1)))
+        for (a, na), (b, nb) in pairs[:2 if both_colours else 1]:
+            m = self._match_of(a, b, n)
+            if start is None:
+                engine = m.engine if isinstance(m, ScsAgentMatch) else m.agents[0]
+                if per_game:
+                    engine.set_games(list(seeds) if seeds is not None else None)
+                start, n_plies = random_openings(engine, opening_seeds, plies)
+            kw = dict(seeds=seeds, max_moves=max_moves, start_actions=start, n_plies=n_plies)
+            if isinstance(m, ScsAgentMatch):
+                kw["agent_seeds"] = agent_seeds
+            rounds.append(m.play(na, nb, **kw))
+        self.opening_rounds, self.openings = tuple(rounds), (start, n_plies)
+        total = {"agent1_wins": 0, "agent2_wins": 0, "draws": 0, "unfinished": 0, "matches": 0}
+        for i, r in enumerate(rounds):                      # in round i == 1 agent1 sits in agent 2's seat: it moves for index 0
+            for k, v in agent_results(r["outcomes"], i == 1, r["finished"]).items():
+                total[k] += v
+        return total
 
     Test_using_agents = test_using_agents
 
