@@ -124,7 +124,14 @@ nz_status nz_engine_dims(const nz_engine* e, nz_dims* out);
  * Network_Manager.inference (Neural_Networks/Network_Manager.py:46-64) computes.
  * `weights[i]` are float32 tensors in the reference's state_dict order and
  * [C_out][C_in][3][3] layout (host or device memory); they are repacked for the
- * MFMA kernel and copied, so the caller may free them afterwards. */
+ * MFMA kernel and copied, so the caller may free them afterwards.
+ * Accepted shapes (anything else: NZ_ERR_ARG and a message): in_channels 2, policy_channels 1, no hex; width a multiple
+ * of 4 in (0, 64]; num_blocks >= 0; recurrent_iterations >= 0 (0: the projection conv and the heads; read for
+ * NZ_ARCH_RECURRENT only); kernel_size 1 or 3 for the ConvNet trunk only (the heads and the other trunks are 3x3;
+ * a 1x1 tensor is [C_out][C_in][1][1]); as many layers as fit one fused launch.  The three routes that run the network -- nz_net_forward, nz_net_forward_packed and
+ * nz_engine_play's kernel -- are pinned over these shapes to a float64 reference within 1e-5 and to each other bit for
+ * bit by tests/test_gpu_tttnet_edges.py (cases: tests/tttnet_cases.py: widths 4 to 64, 0 to 3 blocks, 0 to 5
+ * iterations, recall on and off, both value activations, k = 1 and 3). */
 nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const float* const* weights,
                                 int32_t n_tensors, int32_t recurrent_iterations);
 

@@ -1,13 +1,17 @@
-"""Errors of the fused loss kernel (nz_loss_forward_backward) on the hard inputs of tests/test_gpu_loss_edges.py, per case,
+"""Errors of the fused loss kernel (nz_loss_forward_backward) on the hard inputs of tests/test_gpu_loss_edges.py
 against the float64 restatement of the reference's loop (tests/loss_ref.py) -- next to the errors of that restatement
-run in float32, the reference's own arithmetic.  Runs the grid once through the raw ABI and records, per case,
+run in float32, the reference's own arithmetic.  Runs the grid once through the raw ABI and measures, per case,
 
     [loss rel, dlogits max abs, dvalues max abs]   of the kernel (under --label) and of the float32 restatement,
     [loss bound, dlogits bound, dvalues bound]     as the test computes them (loss_ref.gradient_bounds),
 
-all against float64.  --out is read first if it exists and only this label's figures are replaced, so one file holds the
-kernel before and after a change (build the library at each state, run with another --label).  No threshold is applied
-here; `outside_bounds` lists the cases a test would fail on.  Prints a one-line JSON summary.
+all against float64.  The file holds one record per (batch x actions, logit kind) -- 54 for the 1,664 cases: the number
+of cases, and for the kernel and the float32 restatement the worst error and the worst error / bound per column over
+the group's target kinds and loss forms, with the case that has the worst ratio.  --per-case writes one record per case
+instead (some 320 kB: for looking at, not for committing).  --out is read first if it exists and only this label's
+figures are replaced, so one file holds the kernel before and after a change (build the library at each state, run
+with another --label).  No threshold is applied here; `outside_bounds` lists the cases a test would fail on.  Prints a
+one-line JSON summary.
 
     python scripts/loss_edge_errors.py --label shifted_logits --kernel "xs = x - mx; logp = xs - logf(se)" \
         [--out profiles/loss_edge_errors.json]
@@ -59,10 +63,11 @@ def main():
     ap.add_argument("--label", required=True, help="name of the kernel state measured, e.g. lse_order / shifted_logits")
     ap.add_argument("--kernel", default="", help="one line on what the kernel computes at this state")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_edge_errors.json"))
+    ap.add_argument("--per-case", action="store_true", help="one record per case instead of one per (shape, logit kind)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("loss_edge_errors.py measures the kernel on the GPU; there is none")
-    doc = {"cases": {}, "runs": {}}
+    doc = {"cases": {}, "groups": {}, "runs": {}}
     if os.path.exists(a.out):
         with open(a.out) as f:
             doc = json.load(f)
@@ -71,7 +76,7 @@ def main():
     doc["bounds_rule"] = ("losses 2e-6 relative; dlogits max(2e-6 of the largest reference entry, 4 x float32 "
                           "restatement's error, 2e-6 x policy_scale); dvalues max(2e-6 of the largest entry, 4 x float32)")
 
-    outside, worst_ratio = [], [0.0, 0.0, 0.0]
+    outside, worst_ratio, groups = [], [0.0, 0.0, 0.0], {}
     by_logits = {lk: {"kernel": [0.0, 0.0], "float32": [0.0, 0.0]} for lk in loss_ref.LOGIT_KINDS}
     for B, A, lk, tks in loss_ref.GRID:
         for tk in tks:
@@ -85,9 +90,19 @@ def main():
                 bounds = [loss_ref.LOSS_BOUND, *loss_ref.gradient_bounds(ref64, ref32, B, norm)]
                 e_k, e_32 = errors(kernel(*dev, pname, vname, norm), ref64), errors(ref32, ref64)
                 cid = f"{B}x{A}/{lk}/{tk}/{pname}{'/logB' if norm else ''}/{vname}"
-                rec = doc["cases"].setdefault(cid, {})
-                rec["largest dlogits entry"] = float("%.3g" % np.abs(ref64[1]).max())
-                rec["bounds"], rec["float32"], rec[a.label] = sig(bounds), sig(e_32), sig(e_k)
+                if a.per_case:
+                    rec = doc["cases"].setdefault(cid, {})
+                    rec["largest dlogits entry"] = float("%.3g" % np.abs(ref64[1]).max())
+                    rec["bounds"], rec["float32"], rec[a.label] = sig(bounds), sig(e_32), sig(e_k)
+                grp = groups.setdefault(f"{B}x{A}/{lk}", {"cases": 0})
+                grp["cases"] += 1
+                for who, e in ((a.label, e_k), ("float32", e_32)):
+                    w = grp.setdefault(who, {"worst": [0.0] * 3, "worst_over_bound": [0.0] * 3, "at": None})
+                    ratio = [x / b for x, b in zip(e, bounds)]
+                    if w["at"] is None or max(ratio) > max(w["worst_over_bound"]):
+                        w["at"] = cid
+                    w["worst"] = [max(x, y) for x, y in zip(w["worst"], e)]
+                    w["worst_over_bound"] = [max(x, y) for x, y in zip(w["worst_over_bound"], ratio)]
                 if not all(np.isfinite(e) and e <= b for e, b in zip(e_k, bounds)):
                     outside.append(cid)
                 worst_ratio = [max(w, e / b) for w, e, b in zip(worst_ratio, e_k, bounds)]
@@ -107,14 +122,23 @@ def main():
                "worst_by_logits [loss rel, dlogits error / largest entry]": {k: {w: sig(e) for w, e in d.items()}
                                                                             for k, d in by_logits.items()}}
     doc["runs"][a.label] = summary
+    for gid, grp in groups.items():                   # this label's and the float32 figures replace the file's
+        rec = doc.setdefault("groups", {}).setdefault(gid, {})
+        rec["cases"] = grp["cases"]
+        for who in (a.label, "float32"):
+            rec[who] = {"worst": sig(grp[who]["worst"]), "worst_over_bound": sig(grp[who]["worst_over_bound"]),
+                        "at": grp[who]["at"]}
     print(json.dumps({a.label: summary}))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:                       # one case per line
-        f.write('{\n "columns": %s,\n "against": %s,\n "bounds_rule": %s,\n "runs": %s,\n "cases": {\n' % (
+    with open(a.out, "w") as f:                       # one group, or one case, per line
+        f.write('{\n "columns": %s,\n "against": %s,\n "bounds_rule": %s,\n "runs": %s,\n' % (
             json.dumps(doc["columns"]), json.dumps(doc["against"]), json.dumps(doc["bounds_rule"]),
             json.dumps(doc["runs"], indent=1).replace("\n", "\n ")))
-        f.write(",\n".join("  %s: %s" % (json.dumps(k), json.dumps(r)) for k, r in doc["cases"].items()))
-        f.write("\n }\n}\n")
+        for key in ("groups", "cases"):
+            f.write(' %s: {\n' % json.dumps(key))
+            f.write(",\n".join("  %s: %s" % (json.dumps(k), json.dumps(r)) for k, r in doc.get(key, {}).items()))
+            f.write("\n }%s\n" % ("," if key == "groups" else ""))
+        f.write("}\n")
 
 
 if __name__ == "__main__":

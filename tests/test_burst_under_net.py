@@ -28,18 +28,18 @@ NETS += [("recurrent", 32, 1, True, 2, "relu"), ("resnet", 64, 2, False, 1, "tan
 IDS = ["-".join(str(x) for x in n) for n in NETS]
 
 
-def _desc(arch, width, num_blocks, recall, value_activation):
+def _desc(arch, width, num_blocks, recall, value_activation, kernel_size=3):
     from nuzero_amd import _lib
     return _lib.NetDesc(in_channels=2, policy_channels=1, width=width, num_blocks=num_blocks, recall=int(recall),
                         value_activation=_lib.NZ_ACT_RELU if value_activation == "relu" else _lib.NZ_ACT_TANH,
                         arch={"recurrent": _lib.NZ_ARCH_RECURRENT, "resnet": _lib.NZ_ARCH_RESNET,
-                              "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=3)
+                              "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=kernel_size)
 
 
 def _steal_order(net, wave):
     from nuzero_amd import _lib
-    arch, width, num_blocks, recall, iters, vact = net
-    nd = _desc(arch, width, num_blocks, recall, vact)
+    arch, width, num_blocks, recall, iters, vact, *k = net          # (a seventh entry: the ConvNet trunk's kernel size)
+    nd = _desc(arch, width, num_blocks, recall, vact, *k)
     n, first = ctypes.c_int32(0), ctypes.c_int32(0)
     _lib.check(_lib.lib.nz_net_steal_order(ctypes.byref(nd), iters, wave, None, 0, ctypes.byref(n), ctypes.byref(first)))
     rows = np.zeros((n.value, _lib.NZ_NET_STEAL_FIELDS), np.int32)
@@ -51,8 +51,8 @@ def _steal_order(net, wave):
 
 def _program(net):
     from nuzero_amd import _lib
-    arch, width, num_blocks, recall, iters, vact = net
-    nd = _desc(arch, width, num_blocks, recall, vact)
+    arch, width, num_blocks, recall, iters, vact, *k = net          # (a seventh entry: the ConvNet trunk's kernel size)
+    nd = _desc(arch, width, num_blocks, recall, vact, *k)
     n = ctypes.c_int32(0)
     _lib.check(_lib.lib.nz_net_program(ctypes.byref(nd), iters, None, 0, ctypes.byref(n)))
     rows = np.zeros((n.value, _lib.NZ_NET_JOB_FIELDS), np.int32)

@@ -12,7 +12,7 @@ Bounds (tests/loss_ref.py LOSS_BOUND, gradient_bounds): losses 2e-6 relative to 
 itself meets that on these inputs (tests/test_loss_ref_host.py); gradients: max |error| <= max(2e-6 of the largest
 reference entry, 4 x the float32 restatement's own error on the case, 2e-6 x policy_scale).
 
-scripts/loss_edge_errors.py records the kernel's error per case of the same grid (profiles/loss_edge_errors.json);
+scripts/loss_edge_errors.py records the kernel's worst errors on the same grid (profiles/loss_edge_errors.json);
 DESIGN.md section 2 statement 12 says what has been measured.
 """
 import os

@@ -11,6 +11,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import tttnet_cases
+
 F = {k: i for i, k in enumerate(("wave", "stage", "og", "cells", "kgroups", "sslot", "src", "dst", "res", "act", "dtile",
                                  "extra", "progressive"))}
 DST_POLICY, DST_VALUE, DST_STRIP = 2, 3, 4
@@ -19,14 +21,17 @@ STRIP_AREA = 2                      # read/write areas: the two activation buffe
 # (arch, width, num_blocks, recall, iterations, value_activation)
 NETS = [("recurrent", w, 2, True, 2, va) for w in (16, 32, 48, 64) for va in ("tanh", "relu")]
 NETS += [("resnet", 64, 2, False, 1, "tanh"), ("convnet", 64, 2, False, 1, "tanh")]
+# the program shapes the host tests compile: those, and the shapes of tests/tttnet_cases.py (a seventh entry: the ConvNet
+# trunk's kernel size).  The GPU test below keeps NETS: it has its own weights and tolerance.
+PROGRAM_NETS = NETS + tttnet_cases.program_shapes()
 
 
-def _program(arch, width, num_blocks, recall, iters, value_activation):
+def _program(arch, width, num_blocks, recall, iters, value_activation, kernel_size=3):
     from nuzero_amd import _lib
     nd = _lib.NetDesc(in_channels=2, policy_channels=1, width=width, num_blocks=num_blocks, recall=int(recall),
                       value_activation=_lib.NZ_ACT_RELU if value_activation == "relu" else _lib.NZ_ACT_TANH,
                       arch={"recurrent": _lib.NZ_ARCH_RECURRENT, "resnet": _lib.NZ_ARCH_RESNET,
-                            "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=3)
+                            "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=kernel_size)
     n = ctypes.c_int32(0)
     _lib.check(_lib.lib.nz_net_program(ctypes.byref(nd), iters, None, 0, ctypes.byref(n)))
     rows = np.zeros((n.value, _lib.NZ_NET_JOB_FIELDS), np.int32)
@@ -49,7 +54,7 @@ def test_final_tap_table():
     assert lib.nz_net_final_tap(9) == -1 and lib.nz_net_final_tap(-1) == -1
 
 
-@pytest.mark.parametrize("net", NETS, ids=lambda n: "-".join(str(x) for x in n))
+@pytest.mark.parametrize("net", PROGRAM_NETS, ids=lambda n: "-".join(str(x) for x in n))
 def test_hazard_rule_on_compiled_programs(net):
     """A job flagged progressive writes an area that no job of its stage reads as an MFMA operand, has a cell that is
     final before tap 8, no input-plane step, and a buffer as destination."""
@@ -89,7 +94,7 @@ def test_trunk_residual_jobs_are_progressive():
     conv = _program("convnet", 64, 2, False, 1, "tanh")
     assert not conv[conv[:, F["act"]] == 3, F["progressive"]].any()
     # one- and two-K-group jobs, halves and quarters all occur among the flagged jobs of the test's networks
-    flagged = np.concatenate([r[r[:, F["progressive"]] == 1] for r in (_program(*n) for n in NETS)])
+    flagged = np.concatenate([r[r[:, F["progressive"]] == 1] for r in (_program(*n) for n in PROGRAM_NETS)])
     assert set(flagged[:, F["kgroups"]]) == {1, 2}
     assert {0x1D0, 0x0A0, 0x144} <= set(flagged[:, F["cells"]])
 

@@ -9,6 +9,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import tttnet_cases
+
 PS = list(range(1, 9))
 F = {k: i for i, k in enumerate(("wave", "stage", "tensor", "nt", "tile0", "tiles", "kgroups", "src", "dst", "res", "act",
                                  "extra", "stage_end", "conv_tiles"))}
@@ -16,6 +18,8 @@ F = {k: i for i, k in enumerate(("wave", "stage", "tensor", "nt", "tile0", "tile
 # (arch, width, num_blocks, recall, iterations, value_activation)
 NETS = [("recurrent", 64, 2, True, 2, "tanh"), ("resnet", 64, 2, False, 1, "tanh"), ("convnet", 64, 2, False, 1, "tanh"),
         ("recurrent", 16, 2, True, 2, "tanh"), ("recurrent", 24, 2, True, 2, "relu"), ("recurrent", 48, 2, True, 2, "tanh")]
+# and the shapes of tests/tttnet_cases.py (a seventh entry: the ConvNet trunk's kernel size)
+NETS += tttnet_cases.program_shapes()
 IDS = ["-".join(str(x) for x in n) for n in NETS]
 
 
@@ -31,18 +35,18 @@ def _columns(P):
     return pos, cell, src
 
 
-def _desc(arch, width, num_blocks, recall, value_activation):
+def _desc(arch, width, num_blocks, recall, value_activation, kernel_size=3):
     from nuzero_amd import _lib
     return _lib.NetDesc(in_channels=2, policy_channels=1, width=width, num_blocks=num_blocks, recall=int(recall),
                         value_activation=_lib.NZ_ACT_RELU if value_activation == "relu" else _lib.NZ_ACT_TANH,
                         arch={"recurrent": _lib.NZ_ARCH_RECURRENT, "resnet": _lib.NZ_ARCH_RESNET,
-                              "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=3)
+                              "convnet": _lib.NZ_ARCH_CONVNET}[arch], kernel_size=kernel_size)
 
 
 def _program(net, P):
     from nuzero_amd import _lib
-    arch, width, num_blocks, recall, iters, vact = net
-    nd = _desc(arch, width, num_blocks, recall, vact)
+    arch, width, num_blocks, recall, iters, vact, *k = net
+    nd = _desc(arch, width, num_blocks, recall, vact, *k)
     n = ctypes.c_int32(0)
     _lib.check(_lib.lib.nz_net_packed_program(ctypes.byref(nd), iters, P, None, 0, ctypes.byref(n)))
     rows = np.zeros((n.value, _lib.NZ_NET_PACKED_JOB_FIELDS), np.int32)
@@ -55,7 +59,7 @@ def _program(net, P):
 def _applications(net):
     """The conv tensors in execution order, stage by stage (state_dict order; RecurrentNet.py:82-99, ConvNet.py:20-40,
     the two heads side by side)."""
-    arch, _, blocks, recall, iters, _ = net
+    arch, _, blocks, recall, iters = net[:5]
     if arch == "convnet":
         trunk, n_trunk = [[i] for i in range(1 + blocks)], 1 + blocks
     else:

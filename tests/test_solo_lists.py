@@ -3,9 +3,10 @@
 Wave p walks its solo list when wave p ^ 4 sits the pass out: stage by stage p's jobs and then p ^ 4's, one barrier after
 both, and where the two are the two cell halves of one tile of one conv, ONE job of group 0 (all nine cells) in their
 place.  nz_net_solo_program returns the very rows the kernel walks; nz_net_steal_order the concatenated order they are
-made of.  Checked on the networks of tests/test_burst_under_net.py:
+made of.  Checked on the networks of tests/test_burst_under_net.py and the shapes of tests/tttnet_cases.py:
   - per stage the solo list covers exactly the (destination, tile, cell) units of the two lists, each once, and has a
-    group-0 job exactly where the pairing rule holds -- at width 64 in every trunk stage;
+    group-0 job exactly where the pairing rule holds -- with a four-tile trunk (widths 52 to 64) in every trunk stage,
+    and at widths 33 to 40 in the heads' first stage (HEAD_STAGE_FUSED);
   - one stage-end flag per stage, as many as each wave's own list carries (the sitting-out wave counts barriers off
     its own list);
   - the weight chain names the next job that reads weights;
@@ -23,7 +24,16 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from test_burst_under_net import NETS, IDS, S, J, OG_NONE, STRIP_AREA, _desc, _steal_order, _program   # noqa: E402
+from test_burst_under_net import NETS as BURST_NETS, S, J, OG_NONE, STRIP_AREA, _desc, _steal_order, _program   # noqa: E402
+import tttnet_cases   # noqa: E402
+
+# and the shapes of tests/tttnet_cases.py (a seventh entry: the ConvNet trunk's kernel size)
+NETS = BURST_NETS + tttnet_cases.program_shapes()
+IDS = ["-".join(str(x) for x in n) for n in NETS]
+# Where the two heads' first convs make four tiles (2 + 2: widths 33 to 40), add_stage cuts that stage's tiles in halves
+# and deals wave p and p ^ 4 the two halves of one tile: the pairing rule holds there, in a HEAD stage, and the solo
+# list has a whole-tile job with the value head's activation or the policy head's ReLU.  None of BURST_NETS has it.
+HEAD_STAGE_FUSED = {n: {0} for n in NETS if 32 < n[1] <= 40}
 
 # a solo row: the NZ_NET_JOB_FIELDS fields, then these
 W_OFF, W_AFTER, STAGE_END = len(J), len(J) + 1, len(J) + 2
@@ -47,8 +57,8 @@ def _switch(value):
 
 def _solo(net, wave, switch=None):
     from nuzero_amd import _lib
-    arch, width, num_blocks, recall, iters, vact = net
-    nd = _desc(arch, width, num_blocks, recall, vact)
+    arch, width, num_blocks, recall, iters, vact, *k = net
+    nd = _desc(arch, width, num_blocks, recall, vact, *k)
     n, first = ctypes.c_int32(0), ctypes.c_int32(0)
     with _switch(switch):
         _lib.check(_lib.lib.nz_net_solo_program(ctypes.byref(nd), iters, wave, None, 0, ctypes.byref(n), ctypes.byref(first)))
@@ -123,10 +133,11 @@ def test_solo_list_covers_both_lists_and_fuses_paired_halves(net):
                 assert [tuple(r[2:len(J)]) for r in jobs] == [tuple(r[2:len(J)]) for r, _ in a + b], (wave, s)
                 assert list(jobs[:, W_OFF]) == [w for _, w in a + b]
     width = net[1]
-    if width == 64:
-        assert fused_stages == set(range(n_stages - 4)), fused_stages        # every trunk stage; the four head stages come last
+    head_fused = {n_stages - 4 + s for s in HEAD_STAGE_FUSED.get(net, ())}    # (empty for every net of BURST_NETS)
+    if width > 48:                                                            # four tiles: 64, and 52 to 60 with padding
+        assert fused_stages == set(range(n_stages - 4)) | head_fused, fused_stages   # every trunk stage; the four head stages come last
     else:
-        assert not fused_stages                                               # narrow trunks are cut in quarters
+        assert fused_stages == head_fused, fused_stages                       # narrow trunks are cut in quarters
 
 
 @pytest.mark.parametrize("switch", (None, 0))
@@ -205,5 +216,8 @@ def test_jobs_of_a_solo_stage_are_independent(net):
                             (j[J["act"]] == 1 if j[J["res"]] >= 0 else j[J["act"]] in (1, 2)))
                     assert j[J["progressive"]] == (1 if form else 0), (s, j)
                     progressive_whole += int(j[J["progressive"]])
-    if net[1] == 64 and net[0] != "convnet":          # (ConvNet: ELU keeps the end-of-job epilogue)
+    # (ConvNet: ELU keeps the end-of-job epilogue; a net without residual blocks, or with zero iterations, has no trunk conv
+    # without the input-plane step -- every net of BURST_NETS has blocks and iterations)
+    has_block_convs = net[2] > 0 and (net[0] != "recurrent" or net[4] > 0)
+    if net[1] == 64 and net[0] != "convnet" and has_block_convs:
         assert progressive_whole > 0
