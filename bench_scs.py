@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--hex", action="store_true", help="hex=True nets (hexagdly.Conv2d(kernel_size=1) everywhere; parity "
                                                         "unpinned: hexagdly is not installed), native evaluator only")
     ap.add_argument("--evaluator", choices=["native", "torch"], default="native")
+    ap.add_argument("--precision", choices=["float32", "bf16"], default="float32",
+                    help="the board net's arithmetic (BoardNet(precision=)): bf16 = opt-in plain bf16, ConvNet / ResNet only")
     ap.add_argument("--loop", choices=["library", "python"], default="library",
                     help="library: nz_scs_search_play (native evaluator only); python: one host round trip per wave")
     ap.add_argument("--nodes-per-sim", type=int, default=0,
@@ -87,9 +89,12 @@ def main():
                 "recurrent": "RecurrentNet(%d filters, %d blocks"}[args.arch] % (args.filters, args.layers)
     if args.arch == "recurrent":
         net_name += ", %d iterations" % args.iters
+    if args.precision != "float32" and args.evaluator != "native":
+        raise SystemExit("--precision bf16 is the native board net's mode: it needs --evaluator native")
     if args.evaluator == "native":
         net = BoardNet(args.arch, cfg.channels, cfg.planes, cfg.rows, cfg.cols, width=args.filters,
-                       num_blocks=args.layers, kernel_size=3, max_batch=args.games, device=local, hex=args.hex)
+                       num_blocks=args.layers, kernel_size=3, max_batch=args.games, device=local, hex=args.hex,
+                       precision=args.precision)
         net.set_weights(w, args.iters)
         ev = net.evaluator()
     else:
@@ -152,7 +157,8 @@ def main():
             return torch.cuda.ExternalStream(st.value, device=local)
         for i in range(S):
             n_i = BoardNet(args.arch, cfg.channels, cfg.planes, cfg.rows, cfg.cols, width=args.filters,
-                           num_blocks=args.layers, kernel_size=3, max_batch=per, device=local, hex=args.hex)
+                           num_blocks=args.layers, kernel_size=3, max_batch=per, device=local, hex=args.hex,
+                           precision=args.precision)
             n_i.set_weights(w, args.iters)
             sets.append((ScsSelfPlay(cfg, search, per, device=local,
                                      nodes_per_game=(1 + args.sims * args.nodes_per_sim) if args.nodes_per_sim else None), n_i,
@@ -206,6 +212,7 @@ def main():
                                   "%s move loop" % (cfg.rows, cfg.cols, cfg.stacking, args.sims, args.games, net_name,
                                                     "hexagonal (unpinned)" if args.hex else "square",
                                                     args.evaluator, args.loop if native else "python"),
+                      "precision": args.precision if native else None,
                       "net_flops_per_position": net.flops_per_position if native else None,
                       "net_tflops": n_exp * net.flops_per_position / dt / 1e12 if native else None,
                       "waves": r.get("waves"), "n_gpus": world, "scaling": "weak", "streams": args.streams,

@@ -484,6 +484,41 @@ int64_t nz_boardnet_flops(const nz_boardnet* h);
 nz_status nz_boardnet_fused(nz_boardnet* h, int32_t enable, int32_t* available);
 nz_status nz_boardnet_dims(const nz_boardnet* h, int32_t* in_channels, int32_t* policy_channels, int32_t* rows,
                            int32_t* cols, int32_t* max_batch);
+/* The arithmetic of the one-launch BF16 program (fused16_net_kernel) and of the per-wavefront form of the persistent SCS
+ * kernel.  NZ_PREC_FLOAT32, the default, is the arithmetic described above: every float32 product from six bf16 MFMA terms
+ * on exact three-way splits, 1e-5 from the reference.  NZ_PREC_BF16 is opt-in plain bf16 for self-play that wants
+ * throughput over parity: weights, input planes and every stored activation are ONE bf16 (round to nearest even), a
+ * product is one v_mfma_f32_16x16x32_bf16 with float32 accumulation, the residual is the stored bf16 value, the logits, the
+ * softmax and the value stay float32.  Its outputs are 6e-3 .. 2e-2 from the reference (tests/test_bf16_ref_host.py).
+ *   set       NZ_PREC_FLOAT32 / NZ_PREC_BF16; -1 only reads.  Setting a DIFFERENT mode puts the handle back to "no weights
+ *             set" (NZ_ERR_STATE from every forward until the next nz_boardnet_set_weights, which builds in the new mode).
+ *   *current  (may be NULL) the handle's mode.
+ * The bf16 mode exists exactly where a Fused16Program can be built: ConvNet / ResNet, every layer of at most 64 padded
+ * channels, a workgroup's share of max_batch in LDS, square or hexagonal.  nz_boardnet_set_weights on any other network in
+ * bf16 mode is NZ_ERR_ARG and names the reason (a RecurrentNet, a layer wider than 64, LDS); nothing falls back to
+ * float32.  In bf16 mode nz_boardnet_fused(h, 0, ...) is NZ_ERR_STATE (the per-layer kernels are float32), and so is
+ * setting the mode while the one-launch form is switched off.
+ * An inference cache (nz_scs_search_cache) holds the evaluations of the network and mode it was filled with: after a
+ * change of mode empty it, nz_scs_search_cache(h, -1), as after a change of weights. */
+enum { NZ_PREC_FLOAT32 = 0, NZ_PREC_BF16 = 1 };
+nz_status nz_boardnet_precision(nz_boardnet* h, int32_t set, int32_t* current);
+/* Host only, no device needed: the bf16 mode's weight stream of one single-source conv layer as nz_boardnet_set_weights
+ * packs it -- [16-channel output tile][tap][32-channel input group][lane 0..63][4 words], a word = the bf16 (round to
+ * nearest even) of input channels (32 group + 8 (lane / 16) + 2 word, + 1) for output channel 16 tile + lane % 16, low half
+ * first; taps: 3 (dy + 1) + (dx + 1), a 1x1 kernel at tap 4; hexagonal N, centre, S, NW, SW, NE, SE.  w0, w1: host
+ * tensors as for set_weights (w1 = kernel1 of a hexagonal conv, else NULL).  Pinned by tests/test_bf16_ref_host.py. */
+nz_status nz_boardnet_bf16_stream(const float* w0, const float* w1, int32_t cout, int32_t cin, int32_t kernel_size, int32_t hex,
+                                  uint32_t* out, int64_t cap, int64_t* n_words);
+/* Test hook of the bf16 mode (NZ_ERR_STATE in float32 mode): nz_boardnet_forward that also copies what every layer
+ * stored in LDS to dump_dev, widened to float32.  Section 0 is the rounded input, section 1 + i layer i's output (layers in
+ * state_dict order: trunk, policy head, value head); section s is float[n][rows_per_position[s]][channels[s]], the sections
+ * back to back.  A bf16 buffer gives rows*cols rows and then its row of zeros (what an off-board tap reads); the float32
+ * rows of the logits and of the value plane give rows*cols rows.  Channels: the input's padded to whole 32-channel groups,
+ * a layer's the 16 per output tile it stored (its padded output channels included).  nz_boardnet_dump_layout fills the first `cap`
+ * entries of the two arrays (either may be NULL) and *n_sections; dump_floats is the size of dump_dev in floats. */
+nz_status nz_boardnet_dump_layout(nz_boardnet* h, int32_t* n_sections, int32_t* rows_per_position, int32_t* channels, int32_t cap);
+nz_status nz_boardnet_forward_dump(nz_boardnet* h, const float* images_dev, int32_t n, float* dump_dev, int64_t dump_floats,
+                                   const int32_t* n_dev, float* logits_dev, float* probs_dev, float* value_dev, void* stream);
 
 /* Gamer.play_game (Training/Gamer.py:52-92) for all G SCS games of `h` to the end, tree, rules,
  * masks AND network on the device: one simulation wave = one [expand + select] kernel followed

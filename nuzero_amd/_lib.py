@@ -21,6 +21,7 @@ NZ_OK, NZ_ERR_ARG, NZ_ERR_HIP, NZ_ERR_STATE, NZ_ERR_OVERFLOW = range(5)
 NZ_GAME_TIC_TAC_TOE = 0
 NZ_ACT_TANH, NZ_ACT_RELU = 0, 1
 NZ_ARCH_RECURRENT, NZ_ARCH_RESNET, NZ_ARCH_CONVNET = 0, 1, 2
+NZ_PREC_FLOAT32, NZ_PREC_BF16 = 0, 1
 NZ_LOSS_CE, NZ_LOSS_KLD, NZ_LOSS_MSE = 0, 1, 2
 NZ_LOSS_SE, NZ_LOSS_AE = 0, 1
 NZ_NET_JOB_FIELDS = 13
@@ -166,6 +167,12 @@ SIGNATURES = {
     "nz_boardnet_flops": (c_int64, [c_void_p]),
     "nz_boardnet_dims": (c_int32, [c_void_p] + [POINTER(c_int32)] * 5),
     "nz_boardnet_fused": (c_int32, [c_void_p, c_int32, POINTER(c_int32)]),
+    "nz_boardnet_precision": (c_int32, [c_void_p, c_int32, POINTER(c_int32)]),
+    "nz_boardnet_bf16_stream": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                          POINTER(c_int64)]),
+    "nz_boardnet_dump_layout": (c_int32, [c_void_p, POINTER(c_int32), c_void_p, c_void_p, c_int32]),
+    "nz_boardnet_forward_dump": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
     "nz_scs_search_play": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_search_play_moves": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "nz_scs_search_play_round": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -814,6 +814,10 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_net_kernel(const FusedPro
 // in LDS as pieces, [piece][row][channel] bf16, split ONCE by the layer that makes them; a row's 16-byte chunks (eight
 // channels) are stored at chunk ^ ((row >> 2) & 3), so that the sixteen rows of a tile -- 64-byte rows for 32 channels --
 // spread over all banks without padding.  The logits and the value plane stay float32 rows for the softmax.
+// The kernel has a second instantiation, PREC = PREC_BF16: the opt-in plain-bf16 mode (nz_boardnet_precision; the
+// arithmetic: fused16_dev.hpp) -- one rounded bf16 per number in piece plane 0 of the same layout, one operand read and
+// one MFMA per K step, a weight stream without the piece dimension -- and with it the layer dump of
+// nz_boardnet_forward_dump.
 constexpr int FUSED16_WREGS = 4;           // 16-byte chunks of the next layer's weights a thread carries (64 KB per layer)
 typedef const __attribute__((address_space(1))) u32x4* gptr4u;
 
@@ -842,7 +846,9 @@ __device__ __forceinline__ void store_weights16(const Fused16Op& op, float* wbuf
 // `fetch`: this job also issues the loads of the NEXT layer's weights, one 16-byte chunk per thread every STEPS / 4
 // steps -- sixteen wavefronts issuing all four at the layer's start queue up at the texture addresser for 1.7 k cycles
 // before the first MFMA.
-template <int NTAPS, int KGT, bool WLDS>
+// PREC = PREC_BF16 (the plain-bf16 mode, fused16_dev.hpp): a step is ONE operand read (piece plane 0), one 16-byte weight
+// chunk per lane (the stream has no piece dimension: a step is 1 KB of it, not 3) and one MFMA, in the same step order.
+template <int NTAPS, int KGT, bool WLDS, int PREC = PREC_F32>
 __device__ __forceinline__ void conv16_job(f32x4& acc, const float* __restrict__ lds, const int (&srow)[NTAPS], int off0,
                                            int cs0, int ps0, int kq, const float* __restrict__ wl,
                                            const uint32_t* __restrict__ wg, bool fetch, const Fused16Op& next,
@@ -850,6 +856,32 @@ __device__ __forceinline__ void conv16_job(f32x4& acc, const float* __restrict__
   constexpr int STEPS = NTAPS * KGT;
   static_assert(STEPS >= FUSED16_WREGS, "a chunk per STEPS / FUSED16_WREGS steps");
   constexpr int AHEAD = WLDS ? 0 : 3;         // weights read from L2: their loads run three steps ahead of the MFMAs
+  if constexpr (PREC == PREC_BF16) {
+    u32x4 bq1[AHEAD + 1];
+    if constexpr (!WLDS) {
+#pragma unroll
+      for (int st = 0; st < AHEAD && st < STEPS; ++st) bq1[st] = *((gptr4u)(wg + st * 256));
+    }
+#pragma unroll
+    for (int tap = 0; tap < NTAPS; ++tap) {
+      const int rbase = off0 + srow[tap] * cs0, sw = (srow[tap] >> 2) & 3;
+#pragma unroll
+      for (int kg = 0; kg < KGT; ++kg) {
+        const int st = tap * KGT + kg;
+        if constexpr (WLDS) {
+          if (st % (STEPS / FUSED16_WREGS) == 0 && st / (STEPS / FUSED16_WREGS) < FUSED16_WREGS && fetch)
+            fetch_weights16_chunk(next, wreg, tid, st / (STEPS / FUSED16_WREGS));
+        }
+        const u32x4 a = *reinterpret_cast<const u32x4*>(lds + rbase + (((kg * 4 + kq) ^ sw) << 2));
+        if constexpr (WLDS) {
+          step16_bf16(acc, a, *reinterpret_cast<const u32x4*>(wl + st * 256));
+        } else {
+          if (st + AHEAD < STEPS) bq1[(st + AHEAD) % (AHEAD + 1)] = *((gptr4u)(wg + (st + AHEAD) * 256));
+          step16_bf16(acc, a, bq1[st % (AHEAD + 1)]);
+        }
+      }
+    }
+  } else {
   u32x4 bq[AHEAD + 1][3];
   if constexpr (!WLDS) {
 #pragma unroll
@@ -886,13 +918,42 @@ __device__ __forceinline__ void conv16_job(f32x4& acc, const float* __restrict__
       }
     }
   }
+  }   // (float32 mode)
 }
-template <bool HEX>
+// The layers' stored values for nz_boardnet_forward_dump (the plain-bf16 instantiation's test hook).  Section 0 is the
+// rounded input, section 1 + i what layer i stored; a section is [position][rows_per_position][channels] float32:
+// a pieces buffer gives its hw rows and then its row of zeros, widened from bf16, a float32-rows buffer its hw rows;
+// the channels are those the layer's column tiles stored (16 per tile: the padded output channels included; what lies
+// past them in a buffer's K group is not the layer's), for the input every channel of a row (2 x cs).
+// (n = the call's batch size, n_host: a section is n x rows x channels floats whatever *n_dev says.)
+// this workgroup's share of one section: `np` positions from p0, from the buffer at (off, cs, ps)
+__device__ __forceinline__ void fused16_dump_section(float* __restrict__ out, size_t base, const float* lds, int off, int cs, int ps,
+                                                     int channels, int np, int p0, int hw, int zrow_index, int tid) {
+  const int rpp = ps != 0 ? hw + 1 : hw;
+  for (int i = tid; i < np * rpp * channels; i += FUSED_THREADS) {
+    const int c = i % channels, r = (i / channels) % rpp, pl = i / (channels * rpp);
+    const int row = r < hw ? pl * hw + r : zrow_index;
+    float v;
+    if (ps == 0) v = lds[off + row * cs + c];
+    else {
+      const uint32_t w = __builtin_bit_cast(uint32_t, lds[off + row * cs + ((((c >> 3) ^ ((row >> 2) & 3)) << 2) | ((c & 7) >> 1))]);
+      v = (c & 1) ? bf16_hi(w) : bf16_lo(w);
+    }
+    out[base + ((size_t)(p0 + pl) * rpp + r) * channels + c] = v;
+  }
+}
+// floats of one position in a section
+__host__ __device__ constexpr int fused16_dump_floats(int hw, int ps, int channels) { return (ps != 0 ? hw + 1 : hw) * channels; }
+
+// PREC = PREC_BF16: the plain-bf16 mode (fused16_dev.hpp); that instantiation alone takes one more argument, the dump's
+// float* (nullptr: none), and the float32 one's code does not know of it.
+template <bool HEX, int PREC = PREC_F32, typename... Dump>
 __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused16Program* __restrict__ prog,
                                                                     const float* __restrict__ in_rows, int in_channels,
                                                                     const int32_t* __restrict__ n_dev, int n_host,
                                                                     float* __restrict__ logits, float* __restrict__ probs,
-                                                                    float* __restrict__ value) {
+                                                                    float* __restrict__ value, Dump... dump_arg) {
+  static_assert(sizeof...(Dump) == (PREC == PREC_BF16 ? 1 : 0), "the dump belongs to the plain-bf16 instantiation");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -943,7 +1004,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       const size_t grow = ((size_t)(n >> 4) * hw + cell) * 16 + (n & 15);
       const float* src = in_rows + grow * in_channels + c8 * 8;
       u32x4 q0 = u32x4{0u, 0u, 0u, 0u}, q1 = q0, q2 = q0;
-      if (r < rows && c8 < chunks) split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
+      if (r < rows && c8 < chunks) {
+        // (plain-bf16: one rounded piece; planes 1 and 2 still get their zeros here -- trunk buffers move into this space)
+        if constexpr (PREC == PREC_BF16) q0 = round8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4));
+        else split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), q0, q1, q2);
+      }
       float* d = lds + h_in_off + r * cs + ((c8 ^ ((r >> 2) & 3)) << 2);
       *reinterpret_cast<u32x4*>(d) = q0;
       *reinterpret_cast<u32x4*>(d + ps) = q1;
@@ -962,6 +1027,16 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
   }
   __syncthreads();
   FSTAMP(tk_in);
+  [[maybe_unused]] float* dump = nullptr;
+  [[maybe_unused]] size_t dump_base = 0;
+  if constexpr (PREC == PREC_BF16) {
+    dump = (dump_arg, ...);
+    if (dump) {                                      // (uniform; a barrier of its own: the hook may cost what it likes)
+      fused16_dump_section(dump, 0, lds, h_in_off, h_in_cs, h_in_ps, 2 * h_in_cs, np, p0, hw, zrow_index, tid);
+      dump_base = (size_t)n_host * fused16_dump_floats(hw, h_in_ps, 2 * h_in_cs);
+      __syncthreads();
+    }
+  }
 
   int rt_cached = -1, srow[ntaps];
   // A layer's descriptor is fetched two layers ahead (a vector load; v_readlane makes the scalars a layer later): behind
@@ -1017,12 +1092,12 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
       const float* wl = wbuf + (size_t)ct * op.w_chunks * 4 + lane * 4;            // LDS copy of the column tile
       const uint32_t* wg = op.w + (size_t)ct * op.w_chunks * 4 + lane * 4;         // packed stream in L2
       // (spelled out, not for_kgroups: through the lambda the square kernel spills a second vector register)
-      if (op.w_lds && kgt == 1) conv16_job<ntaps, 1, true>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      else if (op.w_lds && kgt == 2) conv16_job<ntaps, 2, true>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      else if (kgt == 1) conv16_job<ntaps, 1, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      else if (kgt == 2) conv16_job<ntaps, 2, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      else if (kgt == 3) conv16_job<ntaps, 3, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
-      else conv16_job<ntaps, 4, false>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      if (op.w_lds && kgt == 1) conv16_job<ntaps, 1, true, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      else if (op.w_lds && kgt == 2) conv16_job<ntaps, 2, true, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      else if (kgt == 1) conv16_job<ntaps, 1, false, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      else if (kgt == 2) conv16_job<ntaps, 2, false, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      else if (kgt == 3) conv16_job<ntaps, 3, false, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
+      else conv16_job<ntaps, 4, false, PREC>(acc, lds, srow, op.off0, op.cs0, op.ps0, kq, wl, wg, to_fetch, next, wreg, tid);
       to_fetch = false;
 #ifdef NZ_FUSED_STAMPS
       asm volatile("" :: "v"(acc));
@@ -1037,13 +1112,18 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
         for (int r = 0; r < 4; ++r) v[r] = acc[r];
         if (op.offr >= 0) {
           const float* rp = lds + op.offr + orow * op.csr + chunk;
-          const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + op.psr),
-                      q2 = *reinterpret_cast<const uint2*>(rp + 2 * op.psr);
-          epi16_add_residual(v, q0, q1, q2);
+          if constexpr (PREC == PREC_BF16) epi16_add_residual_bf16(v, *reinterpret_cast<const uint2*>(rp));
+          else {
+            const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + op.psr),
+                        q2 = *reinterpret_cast<const uint2*>(rp + 2 * op.psr);
+            epi16_add_residual(v, q0, q1, q2);
+          }
         }
         epi16_activate<4>(v, op.act);
         if (op.psd == 0) {                                  // float32 rows (logits, value plane): 16 bytes
           *reinterpret_cast<f32x4*>(lds + op.offd + orow * op.csd + c0) = f32x4{v[0], v[1], v[2], v[3]};
+        } else if constexpr (PREC == PREC_BF16) {           // one rounded piece, into plane 0
+          *reinterpret_cast<uint2*>(lds + op.offd + orow * op.csd + chunk) = epi16_round(v);
         } else {
           uint2 q[3];
           epi16_split(v, q);
@@ -1063,6 +1143,13 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused16_net_kernel(const Fused1
     if (next_lds && next.w_after_barrier) {
       store_weights16(next, next_wbuf, wreg, tid);
       __syncthreads();
+    }
+    if constexpr (PREC == PREC_BF16) {
+      if (dump) {                                        // what this layer stored (nothing writes its destination before the next barrier)
+        fused16_dump_section(dump, dump_base, lds, op.offd, op.csd, op.psd, op.ntiles * 16, np, p0, hw, zrow_index, tid);
+        dump_base += (size_t)n_host * fused16_dump_floats(hw, op.psd, op.ntiles * 16);
+        __syncthreads();
+      }
     }
 #ifdef NZ_FUSED_STAMPS
     if (o < 32) FSTAMP(tk_bar[o]);
@@ -1138,6 +1225,7 @@ struct PackedConv {                         // move-only: it owns its streams
   DevBuf<float> dev;
   DevBuf<uint32_t> dev_split;               // wide layers only (conv_wide_kernel)
   DevBuf<uint32_t> dev16;                   // fused16_net_kernel's stream [col tile][tap][32-ch group][piece][lane][4]
+  DevBuf<uint32_t> dev16b;                  // plain-bf16 mode only: one rounded bf16 per weight, [col tile][tap][32-ch group][lane][4]
   int kg0_32 = 0, kg1_32 = 0;
   int c0p = 0, c1p = 0, coutp = 0, cout = 0, cin = 0;
 };
@@ -1145,8 +1233,10 @@ struct PackedConv {                         // move-only: it owns its streams
 // the kernel of a <true> / <false> pair for the network's taps (hexagonal / square), by the program it runs
 template <typename Program>
 using net_fn_t = void (*)(const Program*, const float*, int, const int32_t*, int, float*, float*, float*);
+typedef void (*net_dump_fn_t)(const Fused16Program*, const float*, int, const int32_t*, int, float*, float*, float*, float*);
 net_fn_t<FusedProgram> net_pick(bool hex, const FusedProgram&);      // (defined below the per-layer launches)
 net_fn_t<Fused16Program> net_pick(bool hex, const Fused16Program&);
+net_dump_fn_t net_pick_bf16(bool hex);                               // the plain-bf16 instantiation (one more argument: the dump)
 
 // `n` elements of host memory in a device block of their own; false, and empty, when that fails
 template <typename T>
@@ -1161,12 +1251,16 @@ template <typename Program>
 struct OneLaunch {
   DevBuf<Program> prog;
   net_fn_t<Program> fn = nullptr;
+  net_dump_fn_t fn_bf16 = nullptr;          // set instead of fn: a Fused16Program in the plain-bf16 mode
   int grid = 0;
   size_t lds_bytes = 0;
   bool built() const { return prog.get() != nullptr; }
-  bool set(const Program& pg, bool hex, int grid_, size_t bytes) {
-    fn = net_pick(hex, pg);
-    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+  bool set(const Program& pg, bool hex, int grid_, size_t bytes, int precision = NZ_PREC_FLOAT32) {
+    fn = nullptr; fn_bf16 = nullptr;
+    if (precision == NZ_PREC_BF16) fn_bf16 = net_pick_bf16(hex);
+    else fn = net_pick(hex, pg);
+    const void* const f = fn_bf16 ? (const void*)fn_bf16 : (const void*)fn;
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
@@ -1204,6 +1298,7 @@ struct nz_boardnet {
   int policy_buf = -1, value_buf = -1;
   bool ready = false;
   bool use_fused = true;
+  int precision = NZ_PREC_FLOAT32;          // nz_boardnet_precision: what the next set_weights builds, and what `w` was built in
   std::string error;
 };
 
@@ -1240,6 +1335,48 @@ int64_t taps_inside(const nz_boardnet* h, int k) {
   return taps;
 }
 
+// One conv's tensors on the host, as the packers index them.
+struct HostConv {
+  bool hex;
+  int k, cout, c0, c1;                       // kernel size (square), output channels, channels of the two sources
+  const float* wh;                           // square: [cout][c0 + c1][k][k]; hexagonal: kernel0 [cout][cin][3][1]
+  const float* wh1;                          // hexagonal: kernel1 [cout][cin][2][2]
+  // channel `ch` of the two sources' concat, the first source padded to `p0` channels -> tensor index (-1: padding)
+  int tensor_index(int ch, int p0) const {
+    if (ch < p0) return ch < c0 ? ch : -1;
+    ch -= p0;
+    return ch < c1 ? c0 + ch : -1;
+  }
+  float weight(int co, int ci, int tap) const {        // 0 for a padded output or input channel
+    const int cin = c0 + c1;
+    if (co >= cout || ci < 0) return 0.f;
+    if (hex) {
+      if (tap < 3) return wh[((size_t)co * cin + ci) * 3 + tap];
+      const int side = tap >= 5, lower = (tap - 3) & 1;                      // 3 NW, 4 SW, 5 NE, 6 SE
+      return wh1[(((size_t)co * cin + ci) * 2 + lower) * 2 + side];
+    }
+    if (k == 1) return tap == 4 ? wh[(size_t)co * cin + ci] : 0.f;
+    return wh[((size_t)co * cin + ci) * 9 + tap];
+  }
+};
+// The plain-bf16 mode's stream of a narrow layer: fused16's order without the piece dimension, [col tile][tap]
+// [32-channel group][lane][4], one bf16 per weight (round to nearest even), the even channel's in the low half of a word;
+// each source padded to whole 32-channel groups on its own (kg0_32 groups of the first)
+std::vector<uint32_t> bf16_stream(const HostConv& hc, int ntiles, int ntaps, int kg0_32, int kg32) {
+  std::vector<uint32_t> out((size_t)ntiles * ntaps * kg32 * 64 * 4, 0u);
+  for (int nt = 0; nt < ntiles; ++nt)
+    for (int tap = 0; tap < ntaps; ++tap)
+      for (int kg = 0; kg < kg32; ++kg)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int co = nt * 16 + (lane & 15), ch = kg * 32 + (lane >> 4) * 8 + 2 * j, p0 = kg0_32 * 32;
+            out[((((size_t)nt * ntaps + tap) * kg32 + kg) * 64 + lane) * 4 + j] =
+                (uint32_t)bf16_rne(hc.weight(co, hc.tensor_index(ch, p0), tap)) |
+                ((uint32_t)bf16_rne(hc.weight(co, hc.tensor_index(ch + 1, p0), tap)) << 16);
+          }
+  return out;
+}
+
 // weights -> the per-lane streams the kernels read.  Square: w0 = [cout][c0 + c1][k][k] (k = 1 or 3), w1 unused.
 // Hexagonal (hexagdly.Conv2d, kernel_size 1): w0 = kernel0 [cout][cin][3][1] (the cell's own column: N, centre, S),
 // w1 = kernel1 [cout][cin][2][2] ([upper, lower] x [left column, right column]).
@@ -1254,29 +1391,20 @@ bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, in
   std::vector<float> wh((size_t)cout * cin * (hex ? 3 : k * k)), wh1(hex ? (size_t)cout * cin * 4 : 0);
   if (hipMemcpy(wh.data(), w0, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return false;
   if (hex && hipMemcpy(wh1.data(), w1, wh1.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return false;
-  // channel `ch` of the two sources' concat, the first source padded to `p0` channels -> tensor index (-1: padding)
-  auto tensor_index = [&](int ch, int p0) {
-    if (ch < p0) return ch < c0 ? ch : -1;
-    ch -= p0;
-    return ch < c1 ? c0 + ch : -1;
-  };
-  auto weight = [&](int co, int ci, int tap) -> float {        // 0 for a padded output or input channel
-    if (co >= cout || ci < 0) return 0.f;
-    if (hex) {
-      if (tap < 3) return wh[((size_t)co * cin + ci) * 3 + tap];
-      const int side = tap >= 5, lower = (tap - 3) & 1;                      // 3 NW, 4 SW, 5 NE, 6 SE
-      return wh1[(((size_t)co * cin + ci) * 2 + lower) * 2 + side];
-    }
-    if (k == 1) return tap == 4 ? wh[(size_t)co * cin + ci] : 0.f;
-    return wh[((size_t)co * cin + ci) * 9 + tap];
-  };
+  const HostConv hc{hex, k, cout, c0, c1, wh.data(), wh1.data()};
+  auto tensor_index = [&](int ch, int p0) { return hc.tensor_index(ch, p0); };
+  auto weight = [&](int co, int ci, int tap) -> float { return hc.weight(co, ci, tap); };
   // the word of each piece for the channel pair (ch, ch + 1) of such a concat
   auto pair = [&](int co, int ch, int p0, int tap, uint32_t word[3]) {
     split3_pair(weight(co, tensor_index(ch, p0), tap), weight(co, tensor_index(ch + 1, p0), tap), word);
   };
+  // The plain-bf16 mode runs the one-launch BF16 program and the per-wavefront form only (nz_boardnet_fused(h, 0) is
+  // refused): the float32 mode's three streams are neither built nor uploaded, so a layer's weights take a third of
+  // the device memory too
+  const bool f32 = h->precision != NZ_PREC_BF16;
   // float32, conv_kernel and fused_net_kernel: [nt][tap (+ 1: zeros, see conv_kernel)][kg][lane][4], the padded concat
-  std::vector<float> host((size_t)ntiles * (ntaps + 1) * kgt * 256, 0.f);
-  for (int nt = 0; nt < ntiles; ++nt)
+  std::vector<float> host(f32 ? (size_t)ntiles * (ntaps + 1) * kgt * 256 : 0, 0.f);
+  for (int nt = 0; f32 && nt < ntiles; ++nt)
     for (int tap = 0; tap < ntaps; ++tap)
       for (int kg = 0; kg < kgt; ++kg)
         for (int lane = 0; lane < 64; ++lane)
@@ -1289,8 +1417,8 @@ bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, in
   if (pc.coutp <= 64) {
     pc.kg0_32 = (c0p + 31) / 32; pc.kg1_32 = (c1p + 31) / 32;
     const int kg32 = pc.kg0_32 + pc.kg1_32;
-    sp16.assign((size_t)ntiles * ntaps * kg32 * 3 * 64 * 4, 0u);
-    for (int nt = 0; nt < ntiles; ++nt)
+    if (f32) sp16.assign((size_t)ntiles * ntaps * kg32 * 3 * 64 * 4, 0u);
+    for (int nt = 0; f32 && nt < ntiles; ++nt)
       for (int tap = 0; tap < ntaps; ++tap)
         for (int kg = 0; kg < kg32; ++kg)
           for (int lane = 0; lane < 64; ++lane)
@@ -1301,9 +1429,12 @@ bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, in
                 sp16[(((((size_t)nt * ntaps + tap) * kg32 + kg) * 3 + piece) * 64 + lane) * 4 + j] = word[piece];
             }
   }
+  // the plain-bf16 mode's stream of such a layer
+  std::vector<uint32_t> sp16b;
+  if (pc.coutp <= 64 && !f32) sp16b = bf16_stream(hc, ntiles, ntaps, pc.kg0_32, pc.kg0_32 + pc.kg1_32);
   // wide layer, the split form for conv_wide_kernel: [ct][tap (+ 1)][kq][piece][8 tiles][lane][4], the padded concat
   std::vector<uint32_t> spw;
-  if (pc.coutp % 128 == 0 && c0p % 32 == 0 && c1p % 32 == 0) {
+  if (f32 && pc.coutp % 128 == 0 && c0p % 32 == 0 && c1p % 32 == 0) {
     const int kqt = (c0p + c1p) / 32, cts = pc.coutp / 128;
     spw.assign((size_t)cts * (ntaps + 1) * kqt * 3 * 8 * 64 * 4, 0u);
     for (int ct = 0; ct < cts; ++ct)
@@ -1318,8 +1449,9 @@ bool pack(nz_boardnet* h, const float* w0, const float* w1, int cout, int c0, in
                   spw[((((((size_t)ct * (ntaps + 1) + tap) * kqt + kq) * 3 + piece) * 8 + nt) * 64 + lane) * 4 + j] = word[piece];
               }
   }
-  if (!upload(&pc.dev, host.data(), host.size())) return false;
+  if (!host.empty() && !upload(&pc.dev, host.data(), host.size())) return false;
   if (!sp16.empty() && !upload(&pc.dev16, sp16.data(), sp16.size())) return false;
+  if (!sp16b.empty() && !upload(&pc.dev16b, sp16b.data(), sp16b.size())) return false;
   if (!spw.empty() && !upload(&pc.dev_split, spw.data(), spw.size())) return false;
   h->w.convs.push_back(std::move(pc));
   h->w.flops += 2 * taps_inside(h, k) * cin * cout;
@@ -1371,6 +1503,7 @@ void dispatch_conv(const ConvArgs& a, int ntiles, hipStream_t s) {
 
 net_fn_t<FusedProgram> net_pick(bool hex, const FusedProgram&) { return hex ? fused_net_kernel<true> : fused_net_kernel<false>; }
 net_fn_t<Fused16Program> net_pick(bool hex, const Fused16Program&) { return hex ? fused16_net_kernel<true> : fused16_net_kernel<false>; }
+net_dump_fn_t net_pick_bf16(bool hex) { return hex ? fused16_net_kernel<true, PREC_BF16, float*> : fused16_net_kernel<false, PREC_BF16, float*>; }
 }  // namespace
 
 
@@ -1430,16 +1563,16 @@ struct Places {
   }
 };
 
-// One layer of a Fused16Program: one source, the dev16 stream read from memory.  A builder that stages weights in LDS
-// says so afterwards (w_lds, w_slot, w_after_barrier).
-void fill_op16(Fused16Op* f, const PackedConv& pc, const ConvOp& op, Place src, Place dst, Place res, int ntaps) {
-  f->w = pc.dev16.get();
+// One layer of a Fused16Program: one source, the dev16 stream (plain-bf16 mode: dev16b, a third of it) read from memory.
+// A builder that stages weights in LDS says so afterwards (w_lds, w_slot, w_after_barrier).
+void fill_op16(Fused16Op* f, const PackedConv& pc, const ConvOp& op, Place src, Place dst, Place res, int ntaps, int precision) {
+  f->w = precision == NZ_PREC_BF16 ? pc.dev16b.get() : pc.dev16.get();
   f->off0 = src.off; f->cs0 = src.cs; f->ps0 = src.ps; f->kg0 = pc.kg0_32;
   f->off1 = -1; f->cs1 = 0; f->ps1 = 0; f->kg1 = 0;
   f->offd = dst.off; f->csd = dst.cs; f->psd = dst.ps;
   f->offr = res.off; f->csr = res.cs; f->psr = res.ps;
   f->ntiles = pc.coutp / 16; f->act = op.act;
-  f->w_chunks = ntaps * pc.kg0_32 * 3 * 64;
+  f->w_chunks = ntaps * pc.kg0_32 * prec_pieces(precision) * 64;
   f->w_lds = 0; f->w_slot = 0; f->w_after_barrier = 0;
 }
 
@@ -1544,21 +1677,25 @@ void build_fused(nz_boardnet* h, int trunk_out) {
 // buffer 0, which the trunk no longer needs by then.
 bool build_fused16_for(nz_boardnet* h, int p_max);
 bool build_fused16_resnet(nz_boardnet* h, int p_max);
-void build_fused16(nz_boardnet* h) {
+// Returns nullptr when the program was built, else why there is none (the plain-bf16 mode, which exists nowhere else,
+// refuses the weights with it).
+const char* build_fused16(nz_boardnet* h) {
   const nz_net_desc& nd = h->net;
-  if ((nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) || (int)h->w.ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return;
+  if (nd.arch != NZ_ARCH_CONVNET && nd.arch != NZ_ARCH_RESNET) return "a RecurrentNet has no one-launch BF16 program (ConvNet and ResNet only)";
+  if ((int)h->w.ops.size() > FUSED_MAX_OPS || h->inp % 8 != 0) return "too many layers for a one-launch program";
   const int n_ops = (int)h->w.ops.size(), n_trunk = n_ops - 6;     // first layer + num_blocks layers, then 2 + 4 head layers
-  if (n_trunk < 1) return;
+  if (n_trunk < 1) return "too few layers";
   for (const PackedConv& pc : h->w.convs)
-    if (!pc.dev16.get()) return;
+    if (!(h->precision == NZ_PREC_BF16 ? pc.dev16b.get() : pc.dev16.get())) return "a layer is wider than 64 padded channels";
   int n_cu = 0;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n_cu <= 0) return;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n_cu <= 0) return "no device attributes";
   if (const char* e = getenv("NZ_BOARDNET_CUS")) n_cu = std::max(1, std::min(n_cu, atoi(e)));   // a stream with a CU mask: its share of the chip
   // positions per workgroup: an even share of the largest batch over the CUs if that fits in LDS, else as many as fit (the
   // grid then has more workgroups than CUs: they take the CUs in turn)
   const int p_even = (h->max_batch + n_cu - 1) / n_cu;
   for (int p_max = p_even; p_max >= 1; --p_max)
-    if (nd.arch == NZ_ARCH_CONVNET ? build_fused16_for(h, p_max) : build_fused16_resnet(h, p_max)) return;
+    if (nd.arch == NZ_ARCH_CONVNET ? build_fused16_for(h, p_max) : build_fused16_resnet(h, p_max)) return nullptr;
+  return "LDS: not even one position's activations with a layer's staged weights fit a workgroup's 160 KB";
 }
 
 bool build_fused16_for(nz_boardnet* h, int p_max) {
@@ -1578,7 +1715,7 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
   size_t wslot = 0;
   for (int i = 1; i < n_trunk; ++i) {
     const PackedConv& pc = h->w.convs[i];
-    wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * 3 * 64 * 4);
+    wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * prec_pieces(h->precision) * 64 * 4);
   }
   if (wslot > (size_t)FUSED16_WREGS * FUSED_THREADS * 4) return false;
   const size_t in_floats = pieces.floats(h->inp);
@@ -1639,7 +1776,7 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
         default: src = h1_pl; dst = val_pl; break;
       }
     }
-    fill_op16(&f, pc, op, src, dst, NOWHERE, ntaps);
+    fill_op16(&f, pc, op, src, dst, NOWHERE, ntaps, h->precision);
     // the K groups a layer reads must exist in its source rows
     if (f.kg0 * 16 > f.cs0) return false;
     const size_t wf = (size_t)f.ntiles * f.w_chunks * 4;
@@ -1650,7 +1787,7 @@ bool build_fused16_for(nz_boardnet* h, int p_max) {
       f.w_lds = 1; f.w_slot = 1; f.w_after_barrier = 1;
     }
   }
-  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float));
+  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float), h->precision);
 }
 // The same for ResNets: three trunk buffers (a block reads its input again as the residual).  LDS, in floats:
 // [input pieces -- after the first layer: trunk buffers 2 and 3][the weight buffer][trunk buffer 1][logits][value plane];
@@ -1672,7 +1809,7 @@ bool build_fused16_resnet(nz_boardnet* h, int p_max) {
   size_t wslot = 0;
   for (int i = 1; i < n_ops; ++i) {
     const PackedConv& pc = h->w.convs[i];
-    wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * 3 * 64 * 4);
+    wslot = std::max(wslot, (size_t)(pc.coutp / 16) * ntaps * (pc.kg0_32 + pc.kg1_32) * prec_pieces(h->precision) * 64 * 4);
   }
   if (wslot > (size_t)FUSED16_WREGS * FUSED_THREADS * 4) return false;
   size_t off = 0;
@@ -1718,14 +1855,14 @@ bool build_fused16_resnet(nz_boardnet* h, int p_max) {
     const ConvOp& op = h->w.ops[i];
     const PackedConv& pc = h->w.convs[i];
     Fused16Op& f = pg.ops[i];
-    if (op.src1 >= 0 || !pc.dev16.get()) return false;
-    fill_op16(&f, pc, op, pl.of(op.src0, false), pl.of(op.dst, i == n_ops - 1), pl.of(op.res, false), ntaps);
+    if (op.src1 >= 0) return false;
+    fill_op16(&f, pc, op, pl.of(op.src0, false), pl.of(op.dst, i == n_ops - 1), pl.of(op.res, false), ntaps, h->precision);
     if (f.kg0 * 16 > f.cs0) return false;
     const size_t wf = (size_t)f.ntiles * f.w_chunks * 4;
     f.w_lds = i >= 1 && wf <= wslot ? 1 : 0;
     f.w_after_barrier = 1;
   }
-  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float));
+  return h->w.fused16.set(pg, nd.hex != 0, grid, off * sizeof(float), h->precision);
 }
 }  // namespace
 
@@ -1748,7 +1885,7 @@ bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* wh
   if (h->hw > 32) return no("boards of more than 32 cells do not fit two row tiles");
   if (h->inp % 8 != 0 || h->inp > 128) return no("input planes");
   for (const PackedConv& pc : g.convs)
-    if (!pc.dev16.get() || pc.coutp > 64 || pc.kg0_32 > 4) return no("a layer is wider than 64 channels");
+    if (!(h->precision == NZ_PREC_BF16 ? pc.dev16b.get() : pc.dev16.get()) || pc.coutp > 64 || pc.kg0_32 > 4) return no("a layer is wider than 64 channels");
   const int rows = h->hw;
   const Pieces pieces{rows, true};
   const int W = nd.width;
@@ -1795,7 +1932,7 @@ bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* wh
     if (op.src1 >= 0) return no("a layer with two sources");
     if (i > 0 && (op.src0 == 0 || op.res == 0)) return no("the input is read after the first layer");
     const Place dst = pl.of(op.dst, i == n_ops - 1);
-    fill_op16(&f, g.convs[i], op, pl.of(op.src0, false), dst, pl.of(op.res, false), ntaps);   // weights: never staged
+    fill_op16(&f, g.convs[i], op, pl.of(op.src0, false), dst, pl.of(op.res, false), ntaps, h->precision);   // weights: never staged
     if (f.kg0 * 48 > f.cs0) return no("internal: K groups beyond the source rows");
     if (dst.ps != 0 && (f.ntiles + 1) / 2 * 48 > dst.cs) return no("internal: output tiles beyond the destination rows");
   }
@@ -1809,7 +1946,8 @@ bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* wh
   w.hw = h->hw; w.rows = h->rows; w.cols = h->cols; w.planes = nd.policy_channels; w.hex = nd.hex ? 1 : 0; w.n_ops = n_ops;
   w.flops = g.flops;
   w.mfmas = 0;
-  for (int i = 0; i < n_ops; ++i) w.mfmas += (int64_t)2 * pg.ops[i].ntiles * ntaps * pg.ops[i].kg0 * 6;
+  for (int i = 0; i < n_ops; ++i) w.mfmas += (int64_t)2 * pg.ops[i].ntiles * ntaps * pg.ops[i].kg0 * (h->precision == NZ_PREC_BF16 ? 1 : 6);
+  w.precision = h->precision;
   g.wave_state = 1;
   *out = w;
   return true;
@@ -1930,8 +2068,12 @@ static nz_status fill_weights(nz_boardnet* h, const float* const* weights, int32
   }
   if (!ok) return bfail(h, NZ_ERR_HIP, "weight upload failed");
   h->policy_buf = 5; h->value_buf = vsrc;
+  if (h->precision == NZ_PREC_BF16) {        // the mode IS the one-launch BF16 program: no float32 form stands in for it
+    if (const char* why = build_fused16(h)) return bfail(h, NZ_ERR_ARG, "no plain-bf16 form of this network: %s", why);
+    return NZ_OK;
+  }
   build_fused(h, cur);
-  build_fused16(h);
+  (void)build_fused16(h);
   return NZ_OK;
 }
 
@@ -1969,8 +2111,28 @@ nz_status nz_boardnet_wide_stamps(uint64_t* out8) {
 #endif
 }
 
+// The arithmetic mode.  A change empties the weights group as a failed set_weights does (the streams and programs are the
+// old mode's); the next set_weights builds in the new mode.
+nz_status nz_boardnet_precision(nz_boardnet* h, int32_t set, int32_t* current) {
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_precision: null handle");
+  if (set != -1 && set != NZ_PREC_FLOAT32 && set != NZ_PREC_BF16) return bfail(h, NZ_ERR_ARG, "nz_boardnet_precision: unknown mode %d", set);
+  if (set != -1 && set != h->precision) {
+    if (set == NZ_PREC_BF16 && !h->use_fused)
+      return bfail(h, NZ_ERR_STATE, "the plain-bf16 mode runs the one-launch form only: nz_boardnet_fused(h, 1) first");
+    B_HIP(h, hipSetDevice(h->device));
+    B_HIP(h, hipDeviceSynchronize());        // (the owners do not wait for a forward that still reads them)
+    h->ready = false;
+    h->w = Weights{};
+    h->precision = set;
+  }
+  if (current) *current = h->precision;
+  return NZ_OK;
+}
+
 nz_status nz_boardnet_fused(nz_boardnet* h, int32_t enable, int32_t* available) {
   if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_fused: null handle");
+  if (enable == 0 && h->precision == NZ_PREC_BF16)
+    return bfail(h, NZ_ERR_STATE, "the per-layer kernels are float32: the plain-bf16 mode has the one-launch form only");
   if (enable >= 0) h->use_fused = enable != 0;
   if (available) *available = h->w.fused.built() || h->w.fused16.built() ? 1 : 0;
   return NZ_OK;
@@ -1988,7 +2150,7 @@ nz_status nz_boardnet_dims(const nz_boardnet* h, int32_t* in_channels, int32_t* 
 }
 
 static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n, const int32_t* n_dev,
-                               float* logits_dev, float* probs_dev, float* value_dev, void* stream) {
+                               float* logits_dev, float* probs_dev, float* value_dev, void* stream, float* dump_dev = nullptr) {
   if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_forward: null handle");
   if (!value_dev) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward: value_dev is NULL");
   if (!h->ready) return bfail(h, NZ_ERR_STATE, "no weights set");
@@ -2007,6 +2169,14 @@ static nz_status forward_impl(nz_boardnet* h, const float* images_dev, int32_t n
     hipLaunchKernelGGL(f.fn, dim3(f.grid), dim3(FUSED_THREADS), f.lds_bytes, s, f.prog.get(), h->buffers[0].get(), h->inp,
                        n_dev, n, logits_dev, probs_dev, value_dev);
   };
+  if (h->precision == NZ_PREC_BF16) {       // (set_weights succeeded: the program is there)
+    const auto& f = h->w.fused16;
+    if (!f.built() || !f.fn_bf16) return bfail(h, NZ_ERR_STATE, "internal: plain-bf16 mode without its program");
+    hipLaunchKernelGGL(f.fn_bf16, dim3(f.grid), dim3(FUSED_THREADS), f.lds_bytes, s, f.prog.get(), h->buffers[0].get(), h->inp,
+                       n_dev, n, logits_dev, probs_dev, value_dev, dump_dev);
+    B_HIP(h, hipGetLastError());
+    return NZ_OK;
+  }
   if (h->use_fused && (h->w.fused16.built() || h->w.fused.built())) {
     if (h->w.fused16.built()) one_launch(h->w.fused16);
     else one_launch(h->w.fused);
@@ -2043,6 +2213,54 @@ nz_status nz_boardnet_forward(nz_boardnet* h, const float* images_dev, int32_t n
                               float* logits_dev, float* probs_dev, float* value_dev, void* stream) {
   if (!images_dev) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward: images_dev is NULL");
   return forward_impl(h, images_dev, n, n_dev, logits_dev, probs_dev, value_dev, stream);
+}
+
+// Host only (no device is touched): the plain-bf16 mode's weight stream of ONE single-source conv as set_weights packs it,
+// for tests/test_bf16_ref_host.py.  w0 / w1: host tensors as in nz_boardnet_set_weights (w1: hexagonal kernel1, else
+// NULL); *n_words: the stream's size; out (may be NULL): its first min(cap, *n_words) words.
+nz_status nz_boardnet_bf16_stream(const float* w0, const float* w1, int32_t cout, int32_t cin, int32_t kernel_size, int32_t hex,
+                                  uint32_t* out, int64_t cap, int64_t* n_words) {
+  if (!w0 || !n_words || cout <= 0 || cin <= 0 || (hex && !w1) || (!hex && kernel_size != 1 && kernel_size != 3))
+    return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_bf16_stream: bad argument");
+  if (pad16(cout) > 64) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_bf16_stream: a layer wider than 64 padded channels has no such stream");
+  const HostConv hc{hex != 0, kernel_size, cout, cin, 0, w0, w1};
+  const int kg32 = (pad16(cin) + 31) / 32;
+  const std::vector<uint32_t> s = bf16_stream(hc, pad16(cout) / 16, hex ? 7 : 9, kg32, kg32);
+  *n_words = (int64_t)s.size();
+  if (out) memcpy(out, s.data(), (size_t)std::min<int64_t>(cap, *n_words) * 4);
+  return NZ_OK;
+}
+
+// The plain-bf16 mode's test hook: a forward that also copies out what every layer stored (fused16_dump_section).
+nz_status nz_boardnet_dump_layout(nz_boardnet* h, int32_t* n_sections, int32_t* rows_per_position, int32_t* channels, int32_t cap) {
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_dump_layout: null handle");
+  if (!n_sections) return bfail(h, NZ_ERR_ARG, "nz_boardnet_dump_layout: null argument");
+  if (!h->ready) return bfail(h, NZ_ERR_STATE, "no weights set");
+  if (h->precision != NZ_PREC_BF16) return bfail(h, NZ_ERR_STATE, "the layer dump exists in the plain-bf16 mode only");
+  B_HIP(h, hipSetDevice(h->device));
+  Fused16Program pg;
+  B_HIP(h, hipMemcpy(&pg, h->w.fused16.prog.get(), sizeof(pg), hipMemcpyDeviceToHost));
+  *n_sections = pg.n_ops + 1;
+  for (int s = 0; s <= pg.n_ops && s < cap; ++s) {
+    const bool pieces = s == 0 || pg.ops[s - 1].psd != 0;
+    if (rows_per_position) rows_per_position[s] = pieces ? pg.hw + 1 : pg.hw;
+    if (channels) channels[s] = s == 0 ? 2 * pg.in_cs : pg.ops[s - 1].ntiles * 16;
+  }
+  return NZ_OK;
+}
+nz_status nz_boardnet_forward_dump(nz_boardnet* h, const float* images_dev, int32_t n, float* dump_dev, int64_t dump_floats,
+                                   const int32_t* n_dev, float* logits_dev, float* probs_dev, float* value_dev, void* stream) {
+  if (!h) return bfail(nullptr, NZ_ERR_ARG, "nz_boardnet_forward_dump: null handle");
+  if (!images_dev || !dump_dev) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward_dump: null argument");
+  if (h->precision != NZ_PREC_BF16) return bfail(h, NZ_ERR_STATE, "the layer dump exists in the plain-bf16 mode only");
+  if (!h->ready) return bfail(h, NZ_ERR_STATE, "no weights set");
+  int32_t ns = 0, rpp[FUSED_MAX_OPS + 1], ch[FUSED_MAX_OPS + 1];
+  const nz_status st = nz_boardnet_dump_layout(h, &ns, rpp, ch, FUSED_MAX_OPS + 1);
+  if (st != NZ_OK) return st;
+  int64_t need = 0;
+  for (int s = 0; s < ns; ++s) need += (int64_t)n * rpp[s] * ch[s];
+  if (dump_floats < need) return bfail(h, NZ_ERR_ARG, "nz_boardnet_forward_dump: the dump needs %lld floats, got %lld", (long long)need, (long long)dump_floats);
+  return forward_impl(h, images_dev, n, n_dev, logits_dev, probs_dev, value_dev, stream, dump_dev);
 }
 
 nz_status nz_boardnet_input_rows(nz_boardnet* h, float** rows_dev, int32_t* row_stride) {

@@ -20,7 +20,9 @@ struct WaveNet {
   int32_t inp, in_channels;       // padded / real input planes
   int32_t hw, rows, cols, planes, hex, n_ops;
   int64_t flops;                  // algorithmic float32 FLOPs per position
-  int64_t mfmas;                  // v_mfma_f32_16x16x32_bf16 issued per position (two row tiles, six split terms, padding included)
+  int64_t mfmas;                  // v_mfma_f32_16x16x32_bf16 issued per position (two row tiles, six split terms -- one in the
+                                  // plain-bf16 mode --, padding included)
+  int32_t precision;              // NZ_PREC_*: the arithmetic the program was built for (its weight streams, its interpreter)
 };
 
 // false (with the reason): this network has no per-wavefront form (architecture, board size, widths, LDS)

@@ -85,6 +85,29 @@ __device__ __forceinline__ void step16(f32x4& acc, const u32x4 (&a)[3], const u3
   acc = mfma_bf16(b[1], a[0], acc);
   acc = mfma_bf16(b[0], a[0], acc);
 }
+// ---- plain-bf16 arithmetic (NZ_PREC_BF16) ----------------------------------------------------------------------------------
+// One bf16 per number instead of three: weights, input planes and every stored activation are rounded to nearest even
+// ONCE, where the float32 mode splits them; a K step is one MFMA on (stored bf16 activations, bf16 weights) with the same
+// float32 accumulator and the same tap / K-group order; the epilogue adds the residual (the stored bf16 value, widened),
+// activates as the float32 mode does and stores one bf16 into piece plane 0 of the destination.  Piece planes 1 and 2 of
+// a layer's destination are neither written nor read; float32 rows (logits, value plane), the softmax and the value
+// are the float32 mode's.  The program, its LDS layout and the weight stream's order ([col tile][tap][32-channel
+// group][lane][4], without the piece dimension) are otherwise unchanged.
+constexpr int PREC_F32 = 0, PREC_BF16 = 1;     // = NZ_PREC_FLOAT32, NZ_PREC_BF16 (include/nuzero_amd.h)
+__host__ __device__ constexpr int prec_pieces(int prec) { return prec == PREC_BF16 ? 1 : 3; }
+// (x0, x1) -> bf16(x0) | bf16(x1) << 16, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint32_t pack_rne16(float x0, float x1) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
+}
+// 8 float32 -> 8 bf16 (the input planes, where split8 splits them)
+__device__ __forceinline__ u32x4 round8(const f32x4& lo, const f32x4& hi) {
+  return u32x4{pack_rne16(lo[0], lo[1]), pack_rne16(lo[2], lo[3]), pack_rne16(hi[0], hi[1]), pack_rne16(hi[2], hi[3])};
+}
+// one K step: the one product term (weights first, as step16)
+__device__ __forceinline__ void step16_bf16(f32x4& acc, const u32x4& a, const u32x4& b) { acc = mfma_bf16(b, a, acc); }
+
 // exp(x) - 1 for x <= 0 to an absolute error of ~1e-7 (v_exp_f32; libm's expm1f keeps the RELATIVE error small near zero,
 // thirty instructions the activations' 1e-5 tolerance has no use for)
 __device__ __forceinline__ float fast_expm1(float x) { return __expf(x) - 1.0f; }
@@ -92,7 +115,7 @@ __device__ __forceinline__ float fast_expm1(float x) { return __expf(x) - 1.0f; 
 // ---- the program ----------------------------------------------------------------------------------------------------------
 constexpr int FUSED_MAX_OPS = 176;
 struct Fused16Op {
-  const uint32_t* w;                       // [col tile][tap][32-channel group][piece][lane][4 dwords = 8 bf16]
+  const uint32_t* w;                       // [col tile][tap][32-channel group][piece][lane][4 dwords = 8 bf16] (plain-bf16 mode: no piece dimension)
   int32_t off0, cs0, ps0, kg0;             // source 0: float offset, floats per row and per piece, piece stride, K groups
   int32_t off1, cs1, ps1, kg1;             // source 1 (off1 = -1: none)
   int32_t offd, csd, psd;                  // destination (psd = 0: float32 rows [row][csd])
@@ -195,6 +218,15 @@ __device__ __forceinline__ void epi16_split(const float* v, uint2 (&q)[3]) {
     }
   }
 }
+
+// the plain-bf16 mode's residual (`q`: the stored bf16 values of the lane's four channels) and its one-piece store
+__device__ __forceinline__ void epi16_add_residual_bf16(float* v, const uint2& q) {
+  v[0] += bf16_lo(q.x);
+  v[1] += bf16_hi(q.x);
+  v[2] += bf16_lo(q.y);
+  v[3] += bf16_hi(q.y);
+}
+__device__ __forceinline__ uint2 epi16_round(const float* v) { return uint2{pack_rne16(v[0], v[1]), pack_rne16(v[2], v[3])}; }
 
 // ---- the two outputs ------------------------------------------------------------------------------------------------------
 // Lanes walk the actions i = first, first + stride, ... < A as f(i, cell, plane, j) -- action i = plane * hw + cell, the

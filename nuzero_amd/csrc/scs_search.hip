@@ -816,6 +816,8 @@ __global__ __launch_bounds__(64) void wave_kernel(SearchParams p, int mode, cons
 // fused16_net_kernel (boardnet.hip) for one position: 25 cells = two row tiles, every layer's weights streamed from L2,
 // activations in the wavefront's own block of LDS -- softmax, expansion, backup, next simulation.  No barrier, no other
 // game, no host until the move's simulations are used up.  Four games (wavefronts) per workgroup share the rules block.
+// A network handle in the plain-bf16 mode (nz_boardnet_precision) runs the PREC_BF16 instantiation: the same pass on one
+// rounded bf16 per number (fused16_dev.hpp), one pair of MFMAs per K step; the search around it is the same code.
 struct PersistArgs {
   const Fused16Program* prog;
   int32_t net_floats, stage_off, stage_floats, inp, in_channels;
@@ -860,6 +862,10 @@ __device__ __forceinline__ uint64_t cache_check_word(uint64_t acc, float value, 
 // loads running AHEAD steps in front (an L2 round trip is several steps long; three or six steps measured no faster,
 // DESIGN §5c).
 constexpr int WAVE_AHEAD = 2;
+// The plain-bf16 mode (PREC = PREC_BF16, fused16_dev.hpp): a step is one pair of MFMAs, a sixth of the float32 mode's, so
+// the weights run six steps ahead to stay the same time in front; a step's weights are one piece (1 KB of the stream).
+constexpr int WAVE_AHEAD_BF16 = 6;
+template <int PREC> constexpr int wave_ahead() { return PREC == PREC_BF16 ? WAVE_AHEAD_BF16 : WAVE_AHEAD; }
 #ifndef NZ_PERSIST_SYNC_DRAIN
 #define NZ_PERSIST_SYNC_DRAIN 0   // 1: a meeting waits for this wavefront's LDS stores before it posts its number
 #endif
@@ -877,18 +883,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_weights_rsrc(const uint32
 // one step's three pieces; the stream position is ONE running vector register (the step's 3 KB added after its loads, the
 // pieces as immediate offsets): a scalar offset per (step, piece) was forty scalar registers of constants held across
 // the whole pass, and the layer's own scalars went to spill lanes for them
-__device__ __forceinline__ void wave_weights_step(u32x4 (&dst)[3], __amdgpu_buffer_rsrc_t rs, int& wv) {
+template <int NP>
+__device__ __forceinline__ void wave_weights_step(u32x4 (&dst)[NP], __amdgpu_buffer_rsrc_t rs, int& wv) {
 #pragma unroll
-  for (int piece = 0; piece < 3; ++piece)
+  for (int piece = 0; piece < NP; ++piece)
     dst[piece] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, wv + piece * 1024, 0, 0));
-  wv += 3072;
+  wv += NP * 1024;
   asm volatile("" : "+v"(wv));
 }
-__device__ __forceinline__ void wave_weights_prologue(u32x4 (&bq)[WAVE_AHEAD + 1][3], __amdgpu_buffer_rsrc_t rs, int& wv, int lane) {
+template <int AHEAD, int NP>
+__device__ __forceinline__ void wave_weights_prologue(u32x4 (&bq)[AHEAD + 1][NP], __amdgpu_buffer_rsrc_t rs, int& wv, int lane) {
   wv = lane * 16;
   asm volatile("" : "+v"(wv));
 #pragma unroll
-  for (int st = 0; st < WAVE_AHEAD; ++st) wave_weights_step(bq[st], rs, wv);
+  for (int st = 0; st < AHEAD; ++st) wave_weights_step(bq[st], rs, wv);
 }
 // Pieces buffers in a game's LDS block: [row][32-channel group][piece][four 16-byte chunks], a row every `cs` floats
 // (48 per group, + 16 when the groups are even in number: rows 256 bytes apart would share their banks), chunk q of row
@@ -922,14 +930,15 @@ __device__ __forceinline__ void wave_tap_rows(TapRows<NTAPS>& t, int row, int ro
   }
 }
 
-template <int NTAPS, int KGT, int RT = 2>
+template <int NTAPS, int KGT, int RT = 2, int PREC = PREC_F32>
 __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS> (&srow)[RT], uint32_t src, uint32_t cs4,
-                                          __amdgpu_buffer_rsrc_t wrs, int& wv, u32x4 (&bq)[WAVE_AHEAD + 1][3],
+                                          __amdgpu_buffer_rsrc_t wrs, int& wv, u32x4 (&bq)[wave_ahead<PREC>() + 1][prec_pieces(PREC)],
                                           unsigned long long* tkn = nullptr, unsigned long long* tsn = nullptr) {
   constexpr int STEPS = NTAPS * KGT;
-  constexpr int AHEAD = WAVE_AHEAD;
+  constexpr int AHEAD = wave_ahead<PREC>();
+  constexpr int NP = prec_pieces(PREC);
   static_assert(STEPS >= AHEAD, "the prologue is always AHEAD steps");
-  u32x4 a[2][RT][3];
+  u32x4 a[2][RT][NP];
   // a tap's operand address: source buffer + row x row stride + this lane's chunk (LDS byte address); two taps' worth are
   // alive at a time
   uint32_t ad[2][RT];
@@ -943,7 +952,7 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
   };
   address(0);
 #pragma unroll
-  for (int piece = 0; piece < 3; ++piece)
+  for (int piece = 0; piece < NP; ++piece)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) a[0][rt][piece] = read(0, rt, piece);
   if (STEPS > 1 && 1 / KGT != 0) address(1 / KGT);
@@ -955,7 +964,24 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
     *tsn = now;
   }
 #endif
-  if constexpr (RT == 2) {
+  if constexpr (RT == 2 && PREC == PREC_BF16) {
+    // The plain-bf16 step: ONE pair of MFMAs (row tile 0, row tile 1) on piece plane 0, in the float32 mode's step order.
+    // Its two slots: behind the first MFMA the next step's operand read for row tile 0 and the weights of AHEAD steps on,
+    // behind the second the read for row tile 1 and the address of the tap after next.
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+      const bool more = st + 1 < STEPS;
+      __builtin_amdgcn_sched_barrier(0);
+      acc[0] = mfma_bf16(bq[st % (AHEAD + 1)][0], a[st & 1][0][0], acc[0]);
+      if (more) a[(st + 1) & 1][0][0] = read(st + 1, 0, 0);
+      if (st + AHEAD < STEPS) wave_weights_step(bq[(st + AHEAD) % (AHEAD + 1)], wrs, wv);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[1] = mfma_bf16(bq[st % (AHEAD + 1)][0], a[st & 1][1][0], acc[1]);
+      if (more) a[(st + 1) & 1][1][0] = read(st + 1, 1, 0);
+      if (st + 2 < STEPS && (st + 2) / KGT != (st + 1) / KGT) address((st + 2) / KGT);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (RT == 2) {
     // A step as six SLOTS, each one pair of MFMAs (row tile 0, row tile 1; step16's term order) with loads in its shadow
     // (an MFMA's gap hides eight cycles of other vector issue, no more): slots 0..2 the next step's operand reads in the
     // order the next step's pairs want them (pieces 1, 2, 0: every read has a whole step to arrive), slot 3 the weights of
@@ -1000,13 +1026,16 @@ __device__ __forceinline__ void wave_conv(f32x4 (&acc)[RT], const TapRows<NTAPS>
     for (int st = 0; st < STEPS; ++st) {
       if (st + 1 < STEPS) {
 #pragma unroll
-        for (int piece = 0; piece < 3; ++piece)
+        for (int piece = 0; piece < NP; ++piece)
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) a[(st + 1) & 1][rt][piece] = read(st + 1, rt, piece);
       }
       if (st + AHEAD < STEPS) wave_weights_step(bq[(st + AHEAD) % (AHEAD + 1)], wrs, wv);
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) step16(acc[rt], a[st & 1][rt], bq[st % (AHEAD + 1)]);
+      for (int rt = 0; rt < RT; ++rt) {
+        if constexpr (PREC == PREC_BF16) step16_bf16(acc[rt], a[st & 1][rt][0], bq[st % (AHEAD + 1)][0]);
+        else step16(acc[rt], a[st & 1][rt], bq[st % (AHEAD + 1)]);
+      }
       if (st + 2 < STEPS && (st + 2) / KGT != (st + 1) / KGT) address((st + 2) / KGT);
       __builtin_amdgcn_sched_barrier(0);          // (the scheduler would hoist every later step's loads up here: spills)
     }
@@ -1020,6 +1049,7 @@ __device__ __forceinline__ int pieces_chunk(int ct, int lane, int row) {
 
 // A layer's epilogue for one tile: residual, activation, split into pieces (or float32 rows), store.  The values are
 // fused16_dev.hpp's epi16_* (fused16_net_kernel calls the same); the addresses are this layout's.
+template <int PREC = PREC_F32>
 __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restrict__ net, const Fused16Op& op, int rt, int ct,
                                               int lane, int rows) {
   const int orow = rt * 16 + (lane & 15), c0 = ct * 16 + (lane >> 4) * 4;
@@ -1030,13 +1060,18 @@ __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restric
   for (int r = 0; r < 4; ++r) v[r] = acc[r];
   if (op.offr >= 0) {
     const float* rp = net + op.offr + orow * op.csr + chunk;
-    const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
-                q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
-    epi16_add_residual(v, q0, q1, q2);
+    if constexpr (PREC == PREC_BF16) epi16_add_residual_bf16(v, *reinterpret_cast<const uint2*>(rp));
+    else {
+      const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
+                  q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
+      epi16_add_residual(v, q0, q1, q2);
+    }
   }
   epi16_activate<4>(v, op.act);
   if (op.psd == 0) {
     *reinterpret_cast<f32x4*>(net + op.offd + orow * op.csd + c0) = f32x4{v[0], v[1], v[2], v[3]};
+  } else if constexpr (PREC == PREC_BF16) {
+    *reinterpret_cast<uint2*>(net + op.offd + orow * op.csd + chunk) = epi16_round(v);
   } else {
     uint2 q[3];
     epi16_split(v, q);
@@ -1050,6 +1085,7 @@ __device__ __forceinline__ void wave_epilogue(const f32x4& acc, float* __restric
 // wave-uniform switch, independent chains the scheduler interleaves), the residual reads and the stores are predicated
 // per row tile.  (Kept beside wave_epilogue: one template over the number of row tiles cost the persistent kernel 1.4 %,
 // profiles/r09_fused16_shared.txt.)
+template <int PREC = PREC_F32>
 __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __restrict__ net, const Fused16Op& op, int ct,
                                                int lane, int rows) {
   const int c0 = ct * 16 + (lane >> 4) * 4;
@@ -1069,9 +1105,12 @@ __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __r
     for (int rt = 0; rt < 2; ++rt) {
       if (ok[rt]) {
         const float* rp = net + op.offr + orow[rt] * op.csr + chunk[rt];
-        const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
-                    q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
-        epi16_add_residual(v[rt], q0, q1, q2);
+        if constexpr (PREC == PREC_BF16) epi16_add_residual_bf16(v[rt], *reinterpret_cast<const uint2*>(rp));
+        else {
+          const uint2 q0 = *reinterpret_cast<const uint2*>(rp), q1 = *reinterpret_cast<const uint2*>(rp + PIECE_FLOATS),
+                      q2 = *reinterpret_cast<const uint2*>(rp + 2 * PIECE_FLOATS);
+          epi16_add_residual(v[rt], q0, q1, q2);
+        }
       }
     }
   }
@@ -1080,6 +1119,12 @@ __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __r
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
       if (ok[rt]) *reinterpret_cast<f32x4*>(net + op.offd + orow[rt] * op.csd + c0) = f32x4{v[rt][0], v[rt][1], v[rt][2], v[rt][3]};
+    return;
+  }
+  if constexpr (PREC == PREC_BF16) {           // one rounded piece per row tile, into plane 0
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+      if (ok[rt]) *reinterpret_cast<uint2*>(net + op.offd + orow[rt] * op.csd + chunk[rt]) = epi16_round(v[rt]);
     return;
   }
   uint2 q[2][3];
@@ -1095,17 +1140,17 @@ __device__ __forceinline__ void wave_epilogue2(const f32x4 (&acc)[2], float* __r
   }
 }
 
-template <int NTAPS, int KGT, int RT = 2>
+template <int NTAPS, int KGT, int RT = 2, int PREC = PREC_F32>
 __device__ __forceinline__ void wave_layer_kloop(f32x4 (&acc)[RT], const float* __restrict__ net, const Fused16Op& op,
                                                  const TapRows<NTAPS> (&srow)[RT], int ct, int lane,
-                                                 u32x4 (&bq)[WAVE_AHEAD + 1][3], int& wv, unsigned long long* tkn = nullptr,
-                                                 unsigned long long* tsn = nullptr) {
+                                                 u32x4 (&bq)[wave_ahead<PREC>() + 1][prec_pieces(PREC)], int& wv,
+                                                 unsigned long long* tkn = nullptr, unsigned long long* tsn = nullptr) {
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const uint32_t src = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)(net + op.off0);
   const uint32_t cs4 = (uint32_t)op.cs0 * 4u;
   const __amdgpu_buffer_rsrc_t wrs = wave_weights_rsrc(op.w + (size_t)ct * op.w_chunks * 4, op.w_chunks);
-  wave_conv<NTAPS, KGT, RT>(acc, srow, src, cs4, wrs, wv, bq, tkn, tsn);
+  wave_conv<NTAPS, KGT, RT, PREC>(acc, srow, src, cs4, wrs, wv, bq, tkn, tsn);
 }
 
 // The two wavefronts of a game meet (the leader runs the tree and half of every layer, the helper the other half): each
@@ -1138,7 +1183,7 @@ __device__ __forceinline__ void pair_sync(int* flags, int me, int& seq, int lane
 // layer.  Head layers (from solo_at on): the leader runs the policy head's chain, the helper the value head's, every tile
 // of every layer, with no meeting -- the CALLER holds the last one (the leader after its softmax, which needs the
 // logits only).
-template <bool HEX>
+template <bool HEX, int PREC = PREC_F32>
 __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __restrict__ net, int lane, int half, int* flags, int& seq,
                                              unsigned long long* tkn = nullptr) {
   unsigned long long tsn = 0;                  // (the stamps' clock; tkn is null outside the diagnostic builds)
@@ -1161,9 +1206,9 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
   uint32_t cur = n_mine > 0 ? fused16_op_dword(wn.prog, layer_at(0), lane) : 0u;
   uint32_t nxt = n_mine > 1 ? fused16_op_dword(wn.prog, layer_at(1), lane) : 0u;
   int wv = 0;
-  u32x4 bq[WAVE_AHEAD + 1][3];
+  u32x4 bq[wave_ahead<PREC>() + 1][prec_pieces(PREC)];
   auto job_weights = [&](const Fused16Op& x, int ct) {
-    wave_weights_prologue(bq, wave_weights_rsrc(x.w + (size_t)ct * x.w_chunks * 4, x.w_chunks), wv, lane);
+    wave_weights_prologue<wave_ahead<PREC>()>(bq, wave_weights_rsrc(x.w + (size_t)ct * x.w_chunks * 4, x.w_chunks), wv, lane);
   };
   for (int i = 0; i < n_mine; ++i) {
     const Fused16Op op = fused16_unpack(cur);
@@ -1179,9 +1224,9 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
       f32x4 acc[2];
       WSTAMP(4);                    // (the layer's header: descriptor words, addresses)
       job_weights(op, ct);
-      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn); });
+      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value, 2, PREC>(acc, net, op, srow, ct, lane, bq, wv, tkn, &tsn); });
       WSTAMP(0);
-      wave_epilogue2(acc, net, op, ct, lane, rows);
+      wave_epilogue2<PREC>(acc, net, op, ct, lane, rows);
       WSTAMP(1);
     }
     if (odd) {
@@ -1195,9 +1240,9 @@ __device__ __forceinline__ void wave_network(const WaveNetArgs& wn, float* __res
       f32x4 acc[1];
       WSTAMP(4);
       job_weights(op, ct);
-      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value, 1>(acc, net, op, srow1, ct, lane, bq, wv); });
+      for_kgroups(kgt, [&](auto kg) { wave_layer_kloop<ntaps, decltype(kg)::value, 1, PREC>(acc, net, op, srow1, ct, lane, bq, wv); });
       WSTAMP(0);
-      wave_epilogue(acc[0], net, op, half, ct, lane, rows);
+      wave_epilogue<PREC>(acc[0], net, op, half, ct, lane, rows);
       WSTAMP(1);
     }
     if (shared) pair_sync(flags, half, seq, lane);     // the layer is whole before either half reads it (or overwrites its source)
@@ -1213,6 +1258,9 @@ __device__ __forceinline__ int legal_list_wave(const ScsRules& R, const ScsState
 }
 // This wavefront's half (`half` = 0 leader, 1 helper) of turning the staged float32 planes into the input pieces (every
 // row of the input region, its row of zeros included) ...
+// (plain-bf16 mode: piece 0 is the planes rounded to nearest even, pieces 1 and 2 are stored as zeros -- the space is the
+// logits', the value plane's and a hidden buffer's afterwards, and what their K groups' padding reads must be numbers)
+template <int PREC = PREC_F32>
 __device__ __forceinline__ void split_planes_half(float* __restrict__ net, const PersistArgs& q, const WaveNetArgs& wn, int lane,
                                                   int half) {
   const int hw = wn.rows, in_off = wn.in_off, in_cs = wn.in_cs;
@@ -1229,7 +1277,8 @@ __device__ __forceinline__ void split_planes_half(float* __restrict__ net, const
         if (c8 * 8 + j >= q.in_channels) lo4[j] = 0.f;
         if (c8 * 8 + 4 + j >= q.in_channels) hi4[j] = 0.f;
       }
-      split8(lo4, hi4, q0, q1, q2);
+      if constexpr (PREC == PREC_BF16) q0 = round8(lo4, hi4);
+      else split8(lo4, hi4, q0, q1, q2);
     }
     float* d = net + in_off + r * in_cs + (c8 >> 2) * GROUP_FLOATS + (((c8 & 3) ^ ((r >> 2) & 3)) << 2);
     *reinterpret_cast<u32x4*>(d) = q0;
@@ -1244,7 +1293,7 @@ __device__ __forceinline__ void zero_stage_half(float* __restrict__ net, const P
 }
 
 // the search of one game's move: the leader wavefront's body (returns when the move's simulations are used up)
-template <bool HEX, int CH = MAXC_CHUNKS>
+template <bool HEX, int CH = MAXC_CHUNKS, int PREC = PREC_F32>
 __device__ __forceinline__ void persist_leader(const SearchParams& p, const PersistArgs& q, const ScsRules& R, unsigned char* wb,
                                                int g, const int lane_in, int* flags, int* go) {
   int lane = lane_in;
@@ -1423,7 +1472,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
         }
       }
       if (!hit) {
-      split_planes_half(net, q, wna, lane, 0);
+      split_planes_half<PREC>(net, q, wna, lane, 0);
       scs_sync<false>();
       pair_sync(flags, 0, seq, lane);             // (both halves of the pieces are made: the staging space can go)
       zero_stage_half(net, q, lane, 0);
@@ -1431,9 +1480,9 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
       pair_sync(flags, 0, seq, lane);
       PSTAMP(3);                                // split, staging cleared (halves)
 #ifdef NZ_PERSIST_STAMPS
-      wave_network<HEX>(wna, net, lane, 0, flags, seq, tk + 10);
+      wave_network<HEX, PREC>(wna, net, lane, 0, flags, seq, tk + 10);
 #else
-      wave_network<HEX>(wna, net, lane, 0, flags, seq);
+      wave_network<HEX, PREC>(wna, net, lane, 0, flags, seq);
 #endif
       PSTAMP(4);                                // network
 
@@ -1540,7 +1589,7 @@ __device__ __forceinline__ void persist_leader(const SearchParams& p, const Pers
   }
 }
 
-template <bool HEX, int CH = MAXC_CHUNKS>
+template <bool HEX, int CH = MAXC_CHUNKS, int PREC = PREC_F32>
 __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p, PersistArgs q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
@@ -1569,7 +1618,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
   int* const go = flags + 4;
   const int g = blockIdx.x * PERSIST_GAMES + slot;
   if (leader) {
-    if (g < p.n_games) persist_leader<HEX, CH>(p, q, R, wb, g, lane, flags, go);
+    if (g < p.n_games) persist_leader<HEX, CH, PREC>(p, q, R, wb, g, lane, flags, go);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if (lane == 0) __hip_atomic_store(go, PERSIST_EXIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     return;
@@ -1594,20 +1643,20 @@ __global__ __launch_bounds__(PERSIST_THREADS) void persist_kernel(SearchParams p
     pair_sync(flags, 1, seq, lane);
     const int job = flags[5], base = flags[7];
     if (job == 0 || k > p.maxc || base + k > p.half_cap) continue;     // (a hit, or the leader is raising the overflow flag)
-    split_planes_half(net, q, wna, lane, 1);
+    split_planes_half<PREC>(net, q, wna, lane, 1);
     scs_sync<false>();
     pair_sync(flags, 1, seq, lane);
     zero_stage_half(net, q, lane, 1);
     scs_sync<false>();
     pair_sync(flags, 1, seq, lane);
-    wave_network<HEX>(wna, net, lane, 1, flags, seq);
+    wave_network<HEX, PREC>(wna, net, lane, 1, flags, seq);
     pair_sync(flags, 1, seq, lane);               // (the value plane is whole; the leader has done its softmax meanwhile)
   }
 }
 
 // Diagnostic: the network part of persist_kernel alone -- every game slot of every workgroup runs `iters` passes on an
 // all-zero input (leader + helper exactly as in the search), out[block * PERSIST_GAMES + slot] = shader ticks per pass.
-template <bool HEX>
+template <bool HEX, int PREC = PREC_F32>
 __global__ __launch_bounds__(PERSIST_THREADS) void netbench_kernel(PersistArgs q, int iters, unsigned long long* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
@@ -1634,7 +1683,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void netbench_kernel(PersistArgs q
   const int active = (iters >> 16) & 0xff ? (iters >> 16) & 0xff : PERSIST_GAMES, n_it = iters & 0xffff;
   if (slot < active)
     for (int it = 0; it < n_it; ++it) {
-      wave_network<HEX>(wna, net, lane, leader ? 0 : 1, flags, seq, tkn);
+      wave_network<HEX, PREC>(wna, net, lane, leader ? 0 : 1, flags, seq, tkn);
       pair_sync(flags, leader ? 0 : 1, seq, lane);
     }
   unsigned long long rep = __builtin_amdgcn_s_memtime() - t0;
@@ -1792,7 +1841,11 @@ __global__ __launch_bounds__(64) void compact_kernel(SearchParams p) {
 // the persistent kernel for a network (square / hexagonal taps), wavefronts per game and the game's children bound
 // (at most 64 legal actions per position: the expansion handles one chunk of children instead of four)
 typedef void (*persist_fn_t)(SearchParams, PersistArgs);
-persist_fn_t persist_pick(bool hex, bool one_chunk) {
+persist_fn_t persist_pick(bool hex, bool one_chunk, int precision) {
+  if (precision == NZ_PREC_BF16) {
+    if (hex) return one_chunk ? persist_kernel<true, 1, PREC_BF16> : persist_kernel<true, MAXC_CHUNKS, PREC_BF16>;
+    return one_chunk ? persist_kernel<false, 1, PREC_BF16> : persist_kernel<false, MAXC_CHUNKS, PREC_BF16>;
+  }
   if (hex) return one_chunk ? persist_kernel<true, 1> : persist_kernel<true, MAXC_CHUNKS>;
   return one_chunk ? persist_kernel<false, 1> : persist_kernel<false, MAXC_CHUNKS>;
 }
@@ -2456,7 +2509,7 @@ nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, voi
       persist_lds = (size_t)(q.rules_per_game ? PERSIST_GAMES : 1) * PERSIST_RULES_BYTES + (size_t)PERSIST_GAMES * q.wave_bytes;
       if (persist_lds > 160 * 1024) h->persist_why = "four games' blocks do not fit in LDS";
       else {
-        h->persist_fn = persist_pick(wn.hex != 0, h->p.maxc <= 64);
+        h->persist_fn = persist_pick(wn.hex != 0, h->p.maxc <= 64, wn.precision);
         const hipError_t e = hipFuncSetAttribute((const void*)h->persist_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds);
         if (e != hipSuccess) { (void)hipGetLastError(); h->persist_why = "hipFuncSetAttribute failed"; }
         else { persist = true; h->persist_why.clear(); }
@@ -3050,11 +3103,12 @@ nz_status nz_scs_netbench(nz_boardnet* net, int32_t blocks, int32_t iters, uint6
   const size_t lds = (size_t)PERSIST_RULES_BYTES + (size_t)PERSIST_GAMES * q.wave_bytes;
   DevBuf<unsigned long long> ticks;
   if (!ticks.ensure((size_t)blocks * PERSIST_GAMES)) return sfail(nullptr, NZ_ERR_HIP, "device allocation failed");
-  hipError_t e = wn.hex ? hipFuncSetAttribute((const void*)netbench_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                        : hipFuncSetAttribute((const void*)netbench_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  typedef void (*netbench_fn_t)(PersistArgs, int, unsigned long long*);
+  const netbench_fn_t fn = wn.precision == NZ_PREC_BF16 ? (wn.hex ? netbench_kernel<true, PREC_BF16> : netbench_kernel<false, PREC_BF16>)
+                                                        : (wn.hex ? netbench_kernel<true> : netbench_kernel<false>);
+  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e == hipSuccess) {
-    if (wn.hex) hipLaunchKernelGGL(netbench_kernel<true>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, ticks.get());
-    else hipLaunchKernelGGL(netbench_kernel<false>, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, ticks.get());
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(PERSIST_THREADS), lds, nullptr, q, iters, ticks.get());
     e = hipDeviceSynchronize();
   }
   if (e == hipSuccess) e = hipMemcpy(ticks_host, ticks.get(), (size_t)blocks * PERSIST_GAMES * 8, hipMemcpyDeviceToHost);

@@ -30,6 +30,15 @@ inline void split3_pair(float even, float odd, uint32_t word[3]) {
   for (int piece = 0; piece < 3; ++piece) word[piece] = (uint32_t)lo[piece] | ((uint32_t)hi[piece] << 16);
 }
 
+// a float32 weight as ONE bf16, round to nearest even (the plain-bf16 mode's stream; the device rounds activations with
+// v_cvt_pk_bf16_f32, the same rule).  Infinities and NaNs keep their upper half.
+inline uint16_t bf16_rne(float a) {
+  uint32_t bits;
+  memcpy(&bits, &a, 4);
+  if ((bits & 0x7F800000u) == 0x7F800000u) return (uint16_t)(bits >> 16) | ((bits & 0xFFFFu) ? 0x40u : 0u);
+  return (uint16_t)((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
+}
+
 // channels after each layer of a head that goes from `width` to `out` in `layers` steps (blocks.py:56-66,144-153)
 inline std::vector<int> head_channels(int width, int out, int layers) {
   std::vector<int> ch{width};

@@ -134,16 +134,22 @@ def game_stats(r, g):
 class Gamer:
     def __init__(self, buffer, shared_storage, game_class, game_args, game_index, search_config,
                  recurrent_iterations, cache_choice="disabled", size_estimate=10000,
-                 num_games=1, concurrent_games=None, device=0, base_seed=0, records=True):
+                 num_games=1, concurrent_games=None, device=0, base_seed=0, records=True, net_precision="float32"):
         """Arguments up to `size_estimate` are the reference's (Gamer.py:20).
         `shared_storage` is anything with ``get()`` returning a Network_Manager (or
         the Network_Manager itself); `buffer` anything with ``save_game(game, i)``
         or None.  `game_class` is Tic_Tac_Toe or SCS_Game (recognised by name); for SCS `game_args[0]` is
-        the game config file and all `num_games` games of a round run concurrently."""
+        the game config file and all `num_games` games of a round run concurrently.  `net_precision` (SCS only): the
+        board net's arithmetic, "float32" or the opt-in "bf16" (BoardNet(precision=))."""
+        if net_precision not in ("float32", "bf16"):
+            raise ValueError(f"bad net_precision {net_precision!r}")
+        self.net_precision = net_precision
         name = getattr(game_class, "__name__", str(game_class)).lower()
         self.is_scs = "scs" in name
         if not self.is_scs and "tic" not in name and "ttt" not in name:
             raise NotImplementedError(f"game {name!r}: Tic_Tac_Toe and SCS_Game run on the GPU engine")
+        if not self.is_scs and net_precision != "float32":
+            raise ValueError("net_precision='bf16' exists for the SCS board nets only: the Tic-Tac-Toe network is float32")
         if cache_choice not in ("disabled", None, "dict", "keyless"):
             raise ValueError(f"bad cache_choice {cache_choice!r}")          # general_utils.py:14-24
         self.cache_choice = cache_choice if cache_choice else "disabled"
@@ -253,7 +259,8 @@ class Gamer:
             if self._board_net is not None:
                 self._board_net.close()
             c = self.scs_config
-            self._board_net = nm.board_net(c.rows, c.cols, self.concurrent, self.recurrent_iterations, self.device)
+            self._board_net = nm.board_net(c.rows, c.cols, self.concurrent, self.recurrent_iterations, self.device,
+                                           precision=self.net_precision)
             self._loaded = (id(nm), nm.version)
         if self.cache_choice != "disabled":
             self.engine.cache_clear()                  # a new round: new caches (AlphaZero.py:525-537)

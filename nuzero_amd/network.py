@@ -145,14 +145,14 @@ class Network_Manager:
         b = logits.shape[0]
         return logits.reshape(b, self._spec.policy_channels, 3, 3), value.reshape(b, 1)
 
-    def board_net(self, rows, cols, max_batch, recurrent_iterations=1, device=0):
+    def board_net(self, rows, cols, max_batch, recurrent_iterations=1, device=0, precision="float32"):
         """The model as a nuzero_amd.boardnet.BoardNet for rows x cols boards (SCS): the network the
-        SCS self-play path evaluates on the device."""
+        SCS self-play path evaluates on the device.  precision: BoardNet's ("float32", or the opt-in "bf16")."""
         from .boardnet import BoardNet
         s = self._spec
         net = BoardNet(s.arch, s.in_channels, s.policy_channels, rows, cols, width=s.width, num_blocks=s.num_blocks,
                        recall=s.recall, value_activation=s.value_activation, kernel_size=s.kernel_size,
-                       max_batch=max_batch, device=device, hex=s.hex)
+                       max_batch=max_batch, device=device, hex=s.hex, precision=precision)
         net.set_weights(self._sd, recurrent_iterations or 1)
         return net
 
