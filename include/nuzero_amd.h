@@ -329,6 +329,49 @@ nz_status nz_net_packed_columns(int32_t P, int32_t* col_pos, int32_t* col_cell, 
 nz_status nz_net_packed_program(const nz_net_desc* net, int32_t recurrent_iterations, int32_t P, int32_t* jobs,
                                 int32_t max_jobs, int32_t* n_jobs);
 
+/* For each row of nz_net_program, in the same order, the conv tensor (state_dict order) the job applies (host only):
+ * with the row's stage, destination, tile and cells this names the layer that wrote any stored activation. */
+nz_status nz_net_program_convs(const nz_net_desc* net, int32_t recurrent_iterations, int32_t* conv_of_job, int32_t max_jobs,
+                               int32_t* n_jobs);
+
+/* ---- the plain-bf16 mode of the Tic-Tac-Toe network (opt-in; the board nets' rule, nz_boardnet_precision below) ----
+ * NZ_PREC_FLOAT32, the default, is the arithmetic above.  NZ_PREC_BF16: weights and input-plane weights rounded once on
+ * the host (to nearest even), raw input planes rounded where the kernel reads them, every stored activation rounded
+ * once in the epilogue that makes it; a conv accumulates in float32 with ONE bf16 MFMA per (input cell, tap) pair and K
+ * group in the float32 mode's order, adds the residual as the stored bf16 value, applies the float32 mode's activation
+ * functions and stores one bf16.  Logits, the value's per-cell staging, tanh(mean) and the softmax stay float32.  Job
+ * lists and LDS layout are unchanged; the weight stream has no piece dimension and is the only one built in the mode.
+ * `mode`: NZ_PREC_FLOAT32 / NZ_PREC_BF16, -1 only reads; anything else is NZ_ERR_ARG.  Setting a DIFFERENT mode drops
+ * the engine's weights (nz_net_forward, nz_engine_play* and the other network routes return NZ_ERR_STATE until the next
+ * nz_engine_set_weights; a table set with nz_engine_set_table stays) and re-derives the pass choice: the mode exists
+ * for the 16-column pass on a wave's own job list only, so a bf16 engine plays with burst_under_net off and never
+ * takes the packed pass, whatever NZ_BURST_UNDER_NET / NZ_NET_PACKED say (both are results-neutral: this costs speed
+ * at small engines, not games); nz_engine_positions_per_pass reports 16, nz_net_forward_packed and
+ * nz_net_forward_stamps return NZ_ERR_STATE.  Nothing falls back to float32.  The persistent kernel, the lock-step
+ * route, nz_engine_move / _search, nz_engine_match_play*, nz_engine_policy_actions and nz_net_forward all follow the
+ * mode; nz_engine_net_matrix_flops reports one bf16 term per product in it.  (NZ_PREC_*: declared with
+ * nz_boardnet_precision; the values are 0 and 1.) */
+nz_status nz_engine_precision(nz_engine* e, int32_t mode, int32_t* current);
+/* The mode's weight stream of one conv tensor w [cout][cin][k][k] (k 1 or 3; host only, as nz_engine_set_weights packs
+ * it): *n_main words [output tile][K group of 32][tap][lane][4], a word two rounded bf16 of neighbouring input
+ * channels < cin_main, then *n_extra words, the float32 bits of the rounded input-plane weights [output tile][tap][lane]
+ * (channels cin_main .. cin - 1; none when cin == cin_main).  Writes at most max_words words. */
+nz_status nz_net_bf16_stream(const float* w, int32_t cout, int32_t cin, int32_t cin_main, int32_t k, uint32_t* words,
+                             int64_t max_words, int64_t* n_main, int64_t* n_extra);
+/* The test hook of the mode (NZ_ERR_STATE in float32 mode): nz_net_forward's outputs and, per position, what the device
+ * itself held, widened to float32.  With R = 16 * ceil(batch / 16) rows (all 16 of every tile, live or not):
+ *   planes_dev float[R][9 cells][4]      the rounded input planes (planes 2, 3: zero)
+ *   acts_dev   float[max_stages][R][NZ_NET_DUMP_ROW]   after stage s (nz_net_program's stage index): piece plane 0 of
+ *              activation buffer 0, of buffer 1 ([cell][64 channels] each), then of the strip ([cell][16 channels]);
+ *              stages past max_stages are not written
+ *   vcells_dev float[R][9]               the value head's per-cell staging before the mean
+ * *n_stages (may be NULL): the program's stages.  It runs a kernel instantiation of its own with one more barrier
+ * after each stage; the plain bf16 kernel carries none of it. */
+#define NZ_NET_DUMP_ROW (2 * 9 * 64 + 9 * 16)
+nz_status nz_net_forward_dump(nz_engine* e, const float* states_dev, int32_t batch, float* logits_dev, float* value_dev,
+                              float* probs_dev, float* planes_dev, float* acts_dev, int32_t max_stages, float* vcells_dev,
+                              int32_t* n_stages, void* stream);
+
 /* Diagnostic build of the network kernel: mean shader-clock ticks wave 0 of a
  * workgroup spends in [0] the K-group loops (LDS reads + MFMA), [1] the
  * input-plane step, [2] the epilogues, [3] at the stage barriers.  Synchronises. */

@@ -28,6 +28,7 @@ NZ_NET_JOB_FIELDS = 13
 NZ_NET_STEAL_FIELDS = 11
 NZ_NET_SOLO_FIELDS = NZ_NET_JOB_FIELDS + 3
 NZ_NET_PACKED_MAX = 8
+NZ_NET_DUMP_ROW = 2 * 9 * 64 + 9 * 16
 NZ_NET_PACKED_JOB_FIELDS = 14
 
 
@@ -128,6 +129,12 @@ SIGNATURES = {
                                       POINTER(c_int32)]),
     "nz_net_final_tap": (c_int32, [c_int32]),
     "nz_net_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_engine_precision": (c_int32, [c_void_p, c_int32, POINTER(c_int32)]),
+    "nz_net_forward_dump": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_void_p, POINTER(c_int32), c_void_p]),
+    "nz_net_bf16_stream": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, POINTER(c_int64),
+                                     POINTER(c_int64)]),
+    "nz_net_program_convs": (c_int32, [POINTER(NetDesc), c_int32, c_void_p, c_int32, POINTER(c_int32)]),
     "nz_net_forward_packed": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_engine_positions_per_pass": (c_int32, [c_void_p, POINTER(c_int32)]),
     "nz_net_packed_columns": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32)]),

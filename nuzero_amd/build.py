@@ -20,6 +20,7 @@ COMMON += os.environ.get("NZ_EXTRA_CXXFLAGS", "").split()   # timing-only ablati
 UNITS = [
     ("tree.hip", ["-ffp-contract=off"]),
     ("net.hip", ["-ffp-contract=off"]),
+    ("net_bf16.hip", ["-ffp-contract=off"]),
     ("selfplay.hip", ["-ffp-contract=off"]),
     ("engine.hip", ["-ffp-contract=off"]),
     ("scs.hip", ["-ffp-contract=off"]),

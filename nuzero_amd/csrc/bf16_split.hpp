@@ -27,4 +27,14 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4& w, const u32x4& x, const
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
 }
 
+// ---- plain-bf16 arithmetic (NZ_PREC_BF16): the rule is stated in fused16_dev.hpp; net_dev.hpp follows it too ----------
+constexpr int PREC_F32 = 0, PREC_BF16 = 1;     // = NZ_PREC_FLOAT32, NZ_PREC_BF16 (include/nuzero_amd.h)
+__host__ __device__ constexpr int prec_pieces(int prec) { return prec == PREC_BF16 ? 1 : 3; }
+// (x0, x1) -> bf16(x0) | bf16(x1) << 16, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint32_t pack_rne16(float x0, float x1) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
+}
+
 }  // namespace nz

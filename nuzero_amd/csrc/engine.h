@@ -115,13 +115,16 @@ int selfplay_blocks(int n_slots, int slots_per_wg);
 // stamps != nullptr selects the diagnostic build ([blocks][4] phase ticks, see selfplay.hip); `packed`: prog_dev is a
 // packed program for p.slots_per_wg positions (net_packed_dev.hpp) and the kernel's packed instantiation runs it
 void launch_selfplay(const TreeParams& p, const struct NetProgram* prog_dev, int n_layers, const float* weights,
-                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s);
+                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s,
+                     int prec = NZ_PREC_FLOAT32);   // NZ_PREC_BF16: the plain-bf16 program and stream; never packed, no burst
 
 // ---- network ----------------------------------------------------------------
 // Arithmetic of the fused network: net_dev.hpp.  K groups are 32 channels; the packed weights of
 // one K group of one 16-channel output tile are [tap][piece][lane][8 bf16].
 constexpr int NET_KG_CHANNELS = 32;
 constexpr int NET_KG_DWORDS = 9 * 3 * 64 * 4;
+// plain-bf16 mode (nz_engine_precision): one rounded bf16 per weight, [tap][lane][8 bf16], a third of the dwords
+constexpr int NET_KG_DWORDS_BF16 = 9 * 64 * 4;
 constexpr int NET_ACT_BUFFERS = 2;                 // activation buffers in LDS (ping-pong)
 constexpr int NET_DST_POLICY = NET_ACT_BUFFERS;    // NetJob::dst: policy logits out
 constexpr int NET_DST_VALUE = NET_ACT_BUFFERS + 1; // NetJob::dst: value out
@@ -133,6 +136,7 @@ constexpr int NET_SSLOT_SPLIT = -1;                // NetJob::sslot: K group rea
 // jobs of a stage are independent, a workgroup barrier separates stages.
 struct NetJob {
   int32_t w_off;       // dword offset of this (layer, n-tile)'s packed main weights [kgroup][tap][piece][lane][8 bf16]
+                       // (plain-bf16 mode: of that mode's stream, [kgroup][tap][lane][8 bf16]; so next_w_off, first_w_off, wx_off)
   int32_t wx_off;      // float offset of its packed input-plane weights [tap][lane]
   int32_t next_w_off;  // w_off of the next job of this wave that reads weights, or -1 (prefetch target)
   int8_t kgroups;      // 32-channel K groups read from the source activation buffer
@@ -210,7 +214,17 @@ __host__ __device__ constexpr int net_packed_tap_source(int cell, int tap) {
 
 void launch_net(const NetProgram* prog_dev, int n_layers, const float* packed_weights,
                 const uint32_t* boards, const float* states, const int32_t* count_dev, int max_positions,
-                float* logits, float* value, float* probs, unsigned long long* stamps, hipStream_t s);
+                float* logits, float* value, float* probs, unsigned long long* stamps, hipStream_t s,
+                int prec = NZ_PREC_FLOAT32);     // NZ_PREC_BF16: prog_dev and packed_weights are the plain-bf16 mode's
+// (net.hip <-> net_bf16.hip) the softmax of launch_net for 9 logits a position; the network kernel of NZ_PREC_BF16
+void launch_softmax9(const float* logits, float* probs, int batch, hipStream_t s);
+void launch_net_bf16(const NetProgram* prog_dev, const float* bf16_weights, const uint32_t* boards, const float* states,
+                     const int32_t* count_dev, int max_positions, float* logits, float* value, unsigned long long* stamps,
+                     hipStream_t s);
+// plain-bf16 only, the test hook (net_bf16.hip net_dump_kernel): launch_net's outputs and what the device held; the arrays
+// hold 16 * ceil(batch / 16) rows
+void launch_net_dump(const NetProgram* prog_dev, const float* bf16_weights, const float* states, int batch, float* logits,
+                     float* value, float* probs, float* planes, float* acts, int max_stages, float* vcells, hipStream_t s);
 // the same outputs from the packed pass: one workgroup per P positions, `prog_dev` a packed program for P
 void launch_net_packed(const NetProgram* prog_dev, int P, const float* packed_weights, const float* states, int batch,
                        float* logits, float* value, float* probs, hipStream_t s);

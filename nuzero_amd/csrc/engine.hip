@@ -67,6 +67,7 @@ struct MatchArrays {
 struct PackedConv {
   int cout, cin, cin_main, kgroups, ntiles, extra;
   int32_t w_off, wx_off;
+  int kg_dwords;       // dwords of one K group of one output tile in the stream: NET_KG_DWORDS, or NET_KG_DWORDS_BF16
 };
 }  // namespace
 
@@ -89,6 +90,11 @@ struct nz_engine {
   // the packed pass (net_packed_dev.hpp): whether nz_engine_play's kernel takes it (decided at create), and the
   // programs compiled so far for the current weights, by positions per pass (packed_program below)
   bool packed = false;
+  // the arithmetic mode (nz_engine_precision).  NZ_PREC_BF16 exists for the 16-column pass on a wave's own job list
+  // only: `packed` and tp.burst_under_net are off while it holds, and what nz_engine_create chose for float32 waits here
+  int prec = NZ_PREC_FLOAT32;
+  bool f32_packed = false;
+  int f32_burst = 0, f32_sims_per_cycle = 0;
   std::vector<PackedConv> convs;              // the packed tensors' layout, as nz_engine_set_weights made it
   DevBuf<NetProgram> packed_prog[NZ_NET_PACKED_MAX + 1];
   bool packed_ready[NZ_NET_PACKED_MAX + 1] = {};
@@ -162,9 +168,14 @@ struct Span {
 // tile nt a contiguous weight stream main[nt][kgroup of 32 ch][tap][piece][lane][8 bf16] (the
 // three exact bf16 pieces of every weight) and, for the two convs that also read the raw
 // input planes, extra[nt][tap][lane] in float32.
+// prec NZ_PREC_BF16 (the plain-bf16 mode; the only stream built in that mode): every weight rounded once to nearest
+// even (weight_pack.hpp bf16_rne), the main stream without the piece dimension, main[nt][kgroup][tap][lane][8 bf16], and
+// the input-plane weights the rounded values as float32.
 // (struct PackedConv: above, the engine keeps the layout)
-PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vector<float>& out) {
+PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vector<float>& out, int prec = NZ_PREC_FLOAT32) {
+  const bool plain = prec == NZ_PREC_BF16;
   PackedConv pc{};
+  pc.kg_dwords = plain ? NET_KG_DWORDS_BF16 : NET_KG_DWORDS;
   pc.cout = cout; pc.cin = cin; pc.cin_main = cin_main;
   pc.ntiles = (cout + 15) / 16;
   pc.kgroups = (cin_main + NET_KG_CHANNELS - 1) / NET_KG_CHANNELS;
@@ -175,12 +186,13 @@ PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vecto
   for (int nt = 0; nt < pc.ntiles; ++nt)
     for (int kg = 0; kg < pc.kgroups; ++kg)
       for (int t = 0; t < 9; ++t)
-        for (int piece = 0; piece < 3; ++piece)
+        for (int piece = 0; piece < (plain ? 1 : 3); ++piece)
           for (int lane = 0; lane < 64; ++lane)
             for (int pr = 0; pr < 4; ++pr) {       // lane holds channels 32 kg + 8 (lane >> 4) + 0..7 as 4 bf16 pairs
               const int co = nt * 16 + (lane & 15), ci = kg * 32 + (lane >> 4) * 8 + 2 * pr;
               uint32_t word[3];
-              split3_pair(weight(co, ci, t), weight(co, ci + 1, t), word);
+              if (plain) word[0] = (uint32_t)bf16_rne(weight(co, ci, t)) | ((uint32_t)bf16_rne(weight(co, ci + 1, t)) << 16);
+              else split3_pair(weight(co, ci, t), weight(co, ci + 1, t), word);
               float f;
               memcpy(&f, &word[piece], 4);
               out.push_back(f);
@@ -192,7 +204,12 @@ PackedConv pack_conv(const float* w, int cout, int cin, int cin_main, std::vecto
         for (int lane = 0; lane < 64; ++lane) {
           const int co = nt * 16 + (lane & 15);
           const int ci = cin_main + (lane >> 4);
-          out.push_back(co < cout && ci < cin ? w[((size_t)co * cin + ci) * 9 + t] : 0.f);
+          float v = co < cout && ci < cin ? w[((size_t)co * cin + ci) * 9 + t] : 0.f;
+          if (plain) {
+            const uint32_t bits = (uint32_t)bf16_rne(v) << 16;
+            memcpy(&v, &bits, 4);
+          }
+          out.push_back(v);
         }
   return pc;
 }
@@ -209,8 +226,10 @@ struct StageConv {
 const int og_taps[7] = {49, 13, 12, 12, 12, 26, 23};   // (input cell, tap) pairs per output-cell group (net_dev.hpp og_mask)
 const int BURST_LONG_STAGE = 160;   // add_stage cost units from which a stage counts as long for the burst budget
 const int JOB_OVERHEAD = 12;   // a job's epilogue and start-up beyond its MFMAs, in the cost units of add_stage (32 cycles)
-bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::vector<StageConv>& stage) {
-  struct Unit { NetJob job; int cost; };
+// `tensor_of[w]` (optional): the conv tensor of every job appended to pg.jobs[w], -1 for a barrier-only job.
+bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::vector<StageConv>& stage,
+               std::vector<int>* tensor_of = nullptr) {
+  struct Unit { NetJob job; int cost; int tensor; };
   struct Tile { const StageConv* sc; int nt; };
   std::vector<Tile> tiles;
   for (const StageConv& sc : stage) {
@@ -228,7 +247,7 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
       const bool q = (quarters >> t) & 1;
       for (int og = q ? 1 : 5; og <= (q ? 4 : 6); ++og) {
         NetJob j{};
-        j.w_off = pc.w_off + nt * pc.kgroups * NET_KG_DWORDS;
+        j.w_off = pc.w_off + nt * pc.kgroups * pc.kg_dwords;
         j.wx_off = pc.wx_off + nt * 9 * 64;
         j.kgroups = (int8_t)pc.kgroups;
         j.sslot = (int8_t)sc.sslot;
@@ -238,7 +257,8 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
         j.src = (int8_t)sc.src; j.dst = (int8_t)sc.dst; j.res = (int8_t)sc.res; j.act = (int8_t)sc.act;
         j.dtile = (int8_t)(sc.dtile + nt);
         if (sc.dst < NET_ACT_BUFFERS && j.dtile >= 4) { j.dst = NET_DST_STRIP; j.dtile = (int8_t)(j.dtile - 4); }
-        units.push_back({j, og_taps[og] * (3 * pc.kgroups + pc.extra) + JOB_OVERHEAD});   // ~time in units of 32 cycles
+        // ~time in units of 32 cycles (of the float32 mode; the plain-bf16 mode keeps its job lists)
+        units.push_back({j, og_taps[og] * (3 * pc.kgroups + pc.extra) + JOB_OVERHEAD, sc.tensor});
       }
     }
     std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.cost > b.cost; });
@@ -304,6 +324,7 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
     const int w = who[u];
     if (pg.n_jobs[w] >= NET_MAX_JOBS) return false;
     pg.jobs[w][pg.n_jobs[w]++] = units[u].job;
+    if (tensor_of) tensor_of[w].push_back(units[u].tensor);
   }
   for (int w = 0; w < NET_WAVES_HOST; ++w) {
     if (pg.n_jobs[w] == first[w]) {            // nothing to do in this stage: barrier only
@@ -311,6 +332,7 @@ bool add_stage(NetProgram& pg, const std::vector<PackedConv>& convs, const std::
       NetJob j{};
       j.og = OG_NONE;
       pg.jobs[w][pg.n_jobs[w]++] = j;
+      if (tensor_of) tensor_of[w].push_back(-1);
     }
     pg.jobs[w][pg.n_jobs[w] - 1].flags |= NET_JOB_STAGE_END;
   }
@@ -523,7 +545,7 @@ std::string compile_net_packed(const nz_net_desc* net, const NetLayout& L, const
 // The network as per-wave job lists (`convs`: the packed tensors' layout); `flops`: in-bounds taps only, 2 * Cout * Cin *
 // 49 per 3x3 conv application (9 for 1x1).  "" or why it does not fit one fused launch.
 std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::vector<PackedConv>& convs, NetProgram& pg,
-                        double& flops) {
+                        double& flops, std::vector<int>* tensor_of = nullptr) {
   const std::vector<ConvShape>& shapes = L.shapes;
   const int trunk_tensors = L.trunk_tensors, iterations = L.iterations;
   flops = 0.0;
@@ -535,7 +557,7 @@ std::string compile_net(const nz_net_desc* net, const NetLayout& L, const std::v
   auto stage = [&](std::vector<StageConv> convs_in_stage) {
     for (const StageConv& sc : convs_in_stage)
       flops += 2.0 * shapes[sc.tensor].cout * shapes[sc.tensor].cin * (shapes[sc.tensor].k == 3 ? 49.0 : 9.0);
-    ok = ok && add_stage(pg, convs, convs_in_stage);
+    ok = ok && add_stage(pg, convs, convs_in_stage, tensor_of);
   };
   for (const StageConv& sc : trunk_stages(net, L, cur)) stage({sc});
   const int ph = trunk_tensors, vh = ph + 2;
@@ -802,6 +824,9 @@ nz_status nz_engine_create_ex(nz_engine** out, const nz_search_cfg* cfg, const n
   }
   if (p.burst_under_net == 1 && p.slots_per_wg == 16) p.sims_per_cycle = 6;
   if (const char* v = getenv("NZ_SIMS_PER_CYCLE")) p.sims_per_cycle = std::max(1, atoi(v));   // tuning experiments
+  e->f32_packed = e->packed;
+  e->f32_burst = p.burst_under_net;
+  e->f32_sims_per_cycle = p.sims_per_cycle;
   {   // every cycle finishes at least one simulation or one move of every live row of the workgroup
     const double games_per_slot = std::ceil((double)p.n_games / (double)p.n_slots) + 2.0;
     const double bound = 16.0 * games_per_slot * TTT_MAX_MOVES * ((double)cfg->mcts_simulations + 2.0);
@@ -881,7 +906,7 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
   std::vector<float> packed;
   std::vector<PackedConv> convs(n_tensors);
   for (int i = 0; i < n_tensors; ++i) {
-    convs[i] = pack_conv(host[i].data(), shapes[i].cout, shapes[i].cin, L.cin_main(i, net->in_channels), packed);
+    convs[i] = pack_conv(host[i].data(), shapes[i].cout, shapes[i].cin, L.cin_main(i, net->in_channels), packed, e->prec);
   }
 
   NetProgram& pg = e->prog_host;
@@ -890,13 +915,14 @@ nz_status nz_engine_set_weights(nz_engine* e, const nz_net_desc* net, const floa
   if (!deep.empty()) return fail(e, NZ_ERR_ARG, "%s", deep.c_str());
   e->algorithmic_flops_per_position = flops;
   {   // what the matrix cores execute for one tile of 16 positions (net_dev.hpp): six bf16 MFMAs per
-      // (input cell, tap) pair and 32-channel K group, one float32 MFMA per pair for the input planes
+      // (input cell, tap) pair and 32-channel K group (plain-bf16 mode: one), one float32 MFMA per pair for the input planes
+    const double terms = e->prec == NZ_PREC_BF16 ? 1.0 : 6.0;
     double bf16 = 0.0, f32 = 0.0;
     for (int w = 0; w < NET_WAVES_HOST; ++w)
       for (int j = 0; j < pg.n_jobs[w]; ++j) {
         const NetJob& job = pg.jobs[w][j];
         if (job.og == OG_NONE) continue;
-        bf16 += (double)og_taps[job.og] * job.kgroups * 6.0 * (2.0 * 16 * 16 * 32);
+        bf16 += (double)og_taps[job.og] * job.kgroups * terms * (2.0 * 16 * 16 * 32);
         f32 += (double)og_taps[job.og] * job.extra * (2.0 * 16 * 16 * 4);
       }
     e->executed_bf16_flops_per_position = bf16 / 16.0;
@@ -1177,7 +1203,8 @@ static nz_status search_lockstep(nz_engine* e, const double* noise_dev, hipStrea
       {
         Span sp(e, s, 1);
         launch_net(e->dev.prog.get(), 0, net_weights(e), p.leaf_boards, nullptr,
-                   p.leaf_count + (it & 1), e->n_games, e->dev.leaf_logits.get(), e->dev.leaf_value.get(), nullptr, nullptr, s);
+                   p.leaf_count + (it & 1), e->n_games, e->dev.leaf_logits.get(), e->dev.leaf_value.get(), nullptr, nullptr, s,
+                   e->prec);
       }
     }
   }
@@ -1340,6 +1367,7 @@ static nz_status replay_desynced(nz_engine* e, const std::vector<int>& games, ui
   }
   nz_engine* f = e->fallback;
   f->borrowed_weights = e->weights_dev.get();
+  f->prec = e->prec;                    // (the lock-step route runs the network kernel of the same mode)
   f->tp.table = e->tp.table;
   f->have_net = e->have_net;
   f->have_table = e->have_table;
@@ -1424,7 +1452,7 @@ nz_status nz_engine_play_next(nz_engine* e, uint64_t base_seed, int32_t have_nex
     const bool packed = e->packed && e->have_net && e->packed_ready[e->tp.slots_per_wg];
     launch_selfplay(e->tp, packed ? e->packed_prog[e->tp.slots_per_wg].get() : e->dev.prog.get(), 0, net_weights(e),
                     c.training ? e->dev.game_noise.get() : nullptr, c.training ? e->dev.game_uniforms.get() : nullptr,
-                    e->stamps ? e->dev.stamps.get() : nullptr, packed, s);
+                    e->stamps ? e->dev.stamps.get() : nullptr, packed, s, e->prec);
   }
   NZ_HIP(e, hipGetLastError());
   if (c.training && have_next) {                            // the next round's draws, while the kernel runs
@@ -1583,7 +1611,7 @@ nz_status nz_net_forward(nz_engine* e, const float* states_dev, int32_t batch, f
   NZ_HIP(e, hipSetDevice(e->device));
   Span sp(e, as_stream(stream), 1);
   launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, states_dev, nullptr, batch, logits_dev,
-             value_dev, probs_dev, nullptr, as_stream(stream));
+             value_dev, probs_dev, nullptr, as_stream(stream), e->prec);
   NZ_HIP(e, hipGetLastError());
   return NZ_OK;
 }
@@ -1592,6 +1620,8 @@ nz_status nz_net_forward_packed(nz_engine* e, const float* states_dev, int32_t b
                                 float* logits_dev, float* value_dev, float* probs_dev, void* stream) {
   if (!e || !states_dev || !logits_dev || !value_dev) return NZ_ERR_ARG;
   if (!e->have_net) return fail(e, NZ_ERR_STATE, "no network: call nz_engine_set_weights first");
+  if (e->prec == NZ_PREC_BF16)
+    return fail(e, NZ_ERR_STATE, "the packed pass is float32 only: this engine is in plain-bf16 mode (nz_engine_precision)");
   if (batch <= 0) return NZ_OK;
   NZ_HIP(e, hipSetDevice(e->device));
   const NetProgram* prog = nullptr;
@@ -1608,6 +1638,8 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
                                 float* value_dev, double* ticks4_host) {
   if (!e || !states_dev || !logits_dev || !value_dev || !ticks4_host) return NZ_ERR_ARG;
   if (!e->have_net) return fail(e, NZ_ERR_STATE, "no network: call nz_engine_set_weights first");
+  if (e->prec == NZ_PREC_BF16)
+    return fail(e, NZ_ERR_STATE, "the stamped network kernel is float32 only: this engine is in plain-bf16 mode (nz_engine_precision)");
   NZ_HIP(e, hipSetDevice(e->device));
   const int blocks = (batch + 15) / 16;
   DevBuf<unsigned long long> stamps;
@@ -1622,6 +1654,89 @@ nz_status nz_net_forward_stamps(nz_engine* e, const float* states_dev, int32_t b
     for (int b = 0; b < blocks; ++b) sum += (double)h[(size_t)b * 4 + i];
     ticks4_host[i] = sum / blocks;
   }
+  return NZ_OK;
+}
+
+// ---- the plain-bf16 mode ----------------------------------------------------------------------------------------------
+nz_status nz_engine_precision(nz_engine* e, int32_t mode, int32_t* current) {
+  if (!e) return NZ_ERR_ARG;
+  if (mode != -1 && mode != NZ_PREC_FLOAT32 && mode != NZ_PREC_BF16)
+    return fail(e, NZ_ERR_ARG, "precision mode %d: NZ_PREC_FLOAT32, NZ_PREC_BF16, or -1 to read", mode);
+  if (mode != -1 && mode != e->prec) {
+    e->prec = mode;
+    // the pass choice: the plain-bf16 pass is the 16-column pass on a wave's own job list, so no wave sits a pass out
+    // and no engine takes the packed pass, whatever nz_engine_create derived; float32 gets that back
+    const bool plain = mode == NZ_PREC_BF16;
+    e->packed = plain ? false : e->f32_packed;
+    e->tp.burst_under_net = plain ? 0 : e->f32_burst;
+    e->tp.sims_per_cycle = e->f32_sims_per_cycle;
+    if (plain && !getenv("NZ_SIMS_PER_CYCLE")) e->tp.sims_per_cycle = 16;       // nz_engine_create's cap without the switch
+    // the weights were packed for the other mode's stream: the engine is back to "no weights" (a table stays)
+    if (e->have_net) {
+      e->have_net = false;
+      for (bool& ready : e->packed_ready) ready = false;
+    }
+  }
+  if (current) *current = e->prec;
+  return NZ_OK;
+}
+
+nz_status nz_net_forward_dump(nz_engine* e, const float* states_dev, int32_t batch, float* logits_dev, float* value_dev,
+                              float* probs_dev, float* planes_dev, float* acts_dev, int32_t max_stages, float* vcells_dev,
+                              int32_t* n_stages, void* stream) {
+  if (!e || !states_dev || !logits_dev || !value_dev || !planes_dev || !acts_dev || !vcells_dev || max_stages < 0) return NZ_ERR_ARG;
+  if (e->prec != NZ_PREC_BF16)
+    return fail(e, NZ_ERR_STATE, "nz_net_forward_dump exists in plain-bf16 mode only (nz_engine_precision)");
+  if (!e->have_net) return fail(e, NZ_ERR_STATE, "no network: call nz_engine_set_weights first");
+  if (n_stages) *n_stages = e->prog_host.n_stages;
+  if (batch <= 0) return NZ_OK;
+  NZ_HIP(e, hipSetDevice(e->device));
+  launch_net_dump(e->dev.prog.get(), net_weights(e), states_dev, batch, logits_dev, value_dev, probs_dev, planes_dev,
+                  acts_dev, max_stages, vcells_dev, as_stream(stream));
+  NZ_HIP(e, hipGetLastError());
+  return NZ_OK;
+}
+
+nz_status nz_net_bf16_stream(const float* w, int32_t cout, int32_t cin, int32_t cin_main, int32_t k, uint32_t* words,
+                             int64_t max_words, int64_t* n_main, int64_t* n_extra) {
+  if (!w || !n_main || !n_extra || (!words && max_words > 0)) return NZ_ERR_ARG;
+  if (cout <= 0 || cout > 64 || cin <= 0 || cin_main < 0 || cin_main > 64 || cin < cin_main || cin > cin_main + 4 || (k != 1 && k != 3)) {
+    g_create_error = "nz_net_bf16_stream: a conv of at most 64 output and 64 main input channels, at most 4 input planes, k 1 or 3";
+    return NZ_ERR_ARG;
+  }
+  std::vector<float> host((size_t)cout * cin * 9, 0.f), packed;
+  for (size_t j = 0; j < (size_t)cout * cin; ++j)
+    for (int t = 0; t < 9; ++t) host[j * 9 + t] = k == 3 ? w[j * 9 + t] : (t == 4 ? w[j] : 0.f);
+  const PackedConv pc = pack_conv(host.data(), cout, cin, cin_main, packed, NZ_PREC_BF16);
+  *n_main = pc.wx_off - pc.w_off;
+  *n_extra = (int64_t)packed.size() - pc.wx_off;
+  const int64_t n = std::min<int64_t>(max_words, (int64_t)packed.size() - pc.w_off);
+  if (n > 0) memcpy(words, packed.data() + pc.w_off, (size_t)n * 4);
+  return NZ_OK;
+}
+
+nz_status nz_net_program_convs(const nz_net_desc* net, int32_t recurrent_iterations, int32_t* conv_of_job, int32_t max_jobs,
+                               int32_t* n_jobs) {
+  if (!net || !n_jobs || (!conv_of_job && max_jobs > 0)) return NZ_ERR_ARG;
+  NetLayout L;
+  std::vector<PackedConv> convs;
+  std::unique_ptr<NetProgram> pg(new NetProgram);
+  std::vector<int> tensor_of[NET_WAVES_HOST];
+  std::string bad = layout_only(net, recurrent_iterations, L, convs);
+  double flops = 0.0;
+  if (bad.empty()) bad = compile_net(net, L, convs, *pg, flops, tensor_of);
+  if (!bad.empty()) {
+    g_create_error = bad;
+    return NZ_ERR_ARG;
+  }
+  int32_t n = 0;
+  for (int w = 0; w < NET_WAVES_HOST; ++w)          // nz_net_program's rows: the jobs with work, wave by wave
+    for (int j = 0; j < pg->n_jobs[w]; ++j) {
+      if (pg->jobs[w][j].og == OG_NONE) continue;
+      if (n < max_jobs) conv_of_job[n] = tensor_of[w][j];
+      ++n;
+    }
+  *n_jobs = n;
   return NZ_OK;
 }
 
@@ -1726,7 +1841,7 @@ nz_status nz_engine_match_play_from(nz_engine* side1, int32_t kind1, nz_engine* 
         if (!table) {                                        // the stand-alone network route (nz_net_forward)
           ttt_state_image_launch(a, s);
           launch_net(pe->dev.prog.get(), 0, net_weights(pe), nullptr, a.states, nullptr, n, m.logits.get(), m.value.get(),
-                     m.probs.get(), nullptr, s);
+                     m.probs.get(), nullptr, s, pe->prec);
         }
       }
       ttt_agent_move_launch(a, mv, kind[mv], table, s);
@@ -1797,7 +1912,7 @@ nz_status nz_engine_policy_actions(nz_engine* e, const uint32_t* boards_host, in
   if (!table) {
     ttt_state_image_launch(a, s);
     launch_net(e->dev.prog.get(), 0, net_weights(e), nullptr, a.states, nullptr, n, m.logits.get(), m.value.get(), m.probs.get(),
-               nullptr, s);
+               nullptr, s, e->prec);
   }
   // The mover runs as side 0 whoever is to move: only a.forced is read here.  Its by-ply rows (agent_actions[0] /
   // agent_n_legal[0]) are written too, into a match state declared overwritten above.  A playable position has an

@@ -93,14 +93,7 @@ __device__ __forceinline__ void step16(f32x4& acc, const u32x4 (&a)[3], const u3
 // a layer's destination are neither written nor read; float32 rows (logits, value plane), the softmax and the value
 // are the float32 mode's.  The program, its LDS layout and the weight stream's order ([col tile][tap][32-channel
 // group][lane][4], without the piece dimension) are otherwise unchanged.
-constexpr int PREC_F32 = 0, PREC_BF16 = 1;     // = NZ_PREC_FLOAT32, NZ_PREC_BF16 (include/nuzero_amd.h)
-__host__ __device__ constexpr int prec_pieces(int prec) { return prec == PREC_BF16 ? 1 : 3; }
-// (x0, x1) -> bf16(x0) | bf16(x1) << 16, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pack_rne16(float x0, float x1) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-}
+// (PREC_F32 / PREC_BF16, prec_pieces and pack_rne16: bf16_split.hpp, shared with net_dev.hpp)
 // 8 float32 -> 8 bf16 (the input planes, where split8 splits them)
 __device__ __forceinline__ u32x4 round8(const f32x4& lo, const f32x4& hi) {
   return u32x4{pack_rne16(lo[0], lo[1]), pack_rne16(lo[2], lo[3]), pack_rne16(hi[0], hi[1]), pack_rne16(hi[2], hi[3])};

@@ -28,6 +28,9 @@
 // activations once per element in the epilogue that produces them: LDS holds the three bf16
 // pieces, the K loop reads them and issues MFMAs, nothing else.  The (<= 4) raw input planes of
 // the projection / recall convs go through one v_mfma_f32_16x16x4_f32 per pair.
+// That is the default mode, PREC_F32.  The opt-in plain-bf16 mode (PREC_BF16, nz_engine_precision; the rule is stated once,
+// in fused16_dev.hpp) keeps ONE rounded bf16 per weight and stored activation -- piece plane 0 of the same layout -- and
+// issues one MFMA per pair and K group; see PiecesT below.  It exists for the 16-column pass on a wave's own job list.
 //
 // Orientation.  The weights are the MFMA's A operand (rows = 16 output channels), the
 // activations its B operand (columns = 16 positions): lane l supplies W[cout = l & 15]
@@ -51,6 +54,8 @@
 // strip[piece][cell][pos][16 ch] (16-byte slot index XOR-ed with (pos >> 2) & 1) for the one head tile that finds no
 // room in them: the two heads' first convs run as one stage, and their 48 + 32 output channels exceed one buffer's 64.
 #pragma once
+#include <type_traits>
+
 #include "bf16_split.hpp"
 #include "engine.h"
 
@@ -74,6 +79,10 @@ constexpr int STRIP_FLOATS = 3 * STRIP_PIECE_BYTES / 4;
 constexpr int NET_LDS_FLOATS = NET_BUFFERS * ACT_FLOATS + INP_FLOATS + VAL_FLOATS + STRIP_FLOATS;
 constexpr int TAP_DWORDS = 3 * 64 * 4;                      // one tap of one K group: [piece][lane][8 bf16]
 constexpr int W_RING = 3;                                   // taps in flight: the weight stream runs three taps ahead of the MFMAs
+// the same of the plain-bf16 stream (PREC_BF16; bf16_split.hpp): no piece dimension, [lane][8 bf16] a tap
+constexpr int tap_dwords(int prec) { return prec_pieces(prec) * 64 * 4; }
+constexpr int kg_dwords(int prec) { return 9 * tap_dwords(prec); }
+static_assert(tap_dwords(PREC_F32) == TAP_DWORDS && kg_dwords(PREC_BF16) == NET_KG_DWORDS_BF16, "host packing and kernel agree");
 static_assert(NET_WAVES == NET_WAVES_HOST, "job lists are per wave");
 static_assert(NET_KG_DWORDS == 9 * TAP_DWORDS && NET_KG_CHANNELS == 32, "host packing (engine.hip) and kernel agree");
 
@@ -170,19 +179,28 @@ constexpr int refill_step() {
   return wanted > earliest ? wanted : earliest;
 }
 
-struct Pieces {           // the three bf16 pieces of 8 channels (one lane's share of a 32-channel K group)
-  u32x4 p[3];
+// PREC (PREC_F32 / PREC_BF16, bf16_split.hpp) is a template parameter of everything that holds or multiplies operands;
+// the float32 mode is the default and what the names without it mean.  Plain-bf16 mode: ONE rounded bf16 per weight and
+// stored activation (piece plane 0 of the same LDS layout; planes 1 and 2 are neither written nor read), one MFMA per
+// (input cell, tap) pair and K group in the same order, the same float32 accumulator and activation functions, the
+// residual added as the stored bf16 value, end-of-job epilogues only, no whole-tile job (the rule: fused16_dev.hpp).
+template <int PREC>
+struct PiecesT {          // the bf16 pieces (three; PREC_BF16: one) of 8 channels (one lane's share of a 32-channel K group)
+  u32x4 p[prec_pieces(PREC)];
 };
-struct FragS {            // the wavefront's weight stream, W_RING taps ahead of the MFMAs
-  Pieces rb[W_RING];
+template <int PREC>
+struct FragST {           // the wavefront's weight stream, W_RING taps ahead of the MFMAs
+  PiecesT<PREC> rb[W_RING];
 };
+typedef PiecesT<PREC_F32> Pieces;
+typedef FragST<PREC_F32> FragS;
 
 // A job's activation operands of one K group.  Every group but the whole tile keeps the three pieces of each used input
 // cell in registers for the K group.  The whole-tile job (0x1FF; solo lists only) holds all nine cells and all nine
 // accumulators, and a third resident piece would not fit the register file beside the weight ring: piece 2, which
 // only one of a pair's six MFMAs reads, is fetched from LDS per (input cell, tap) pair instead, LATE_AHEAD pairs ahead
 // into a ring of as many registers -- the same bits from the same address, 49 reads a K group in place of nine.
-constexpr int resident_pieces(int omask) { return omask == 0x1FF ? 2 : 3; }
+constexpr int resident_pieces(int omask, int prec = PREC_F32) { return prec == PREC_BF16 ? 1 : omask == 0x1FF ? 2 : 3; }
 constexpr int LATE_AHEAD = 2;
 // the n-th (input cell, tap) pair of the group in issue order, as 9 * tap + cell (-1: past the last)
 constexpr int nth_pair(int omask, int n) {
@@ -193,10 +211,11 @@ constexpr int nth_pair(int omask, int n) {
     }
   return -1;
 }
-template <int OMASK>
+template <int OMASK, int PREC = PREC_F32>
 struct Operands {
-  static constexpr int NP = resident_pieces(OMASK), PAIRS = pairs_before(OMASK, 9, 0);
-  Pieces x[CELLS];
+  static_assert(PREC == PREC_F32 || OMASK != 0x1FF, "no whole-tile job in plain-bf16 mode");
+  static constexpr int NP = resident_pieces(OMASK, PREC), PAIRS = pairs_before(OMASK, 9, 0);
+  PiecesT<PREC> x[CELLS];
   // NP == 2 only: the ring of piece 2, the source buffer, the slot addresses of this K group and of the job's next
   u32x4 late[LATE_AHEAD];
   const unsigned char* src;
@@ -212,7 +231,7 @@ struct Operands {
   // piece 2 for pair N of this K group, or (N >= PAIRS, PART 1) for pair N - PAIRS of the next; nothing past the job's end
   template <int N, int PART>
   __device__ __forceinline__ void fetch_third() {
-    if constexpr (NP < 3 && (N < PAIRS || PART == 1)) {
+    if constexpr (NP == 2 && (N < PAIRS || PART == 1)) {
       constexpr int I = nth_pair(OMASK, N % PAIRS) % 9;
       late[through<PART>(N) % LATE_AHEAD] =
           *reinterpret_cast<const u32x4*>(src + 2 * PIECE_BYTES + I * (POS * 128) + (N < PAIRS ? cur : nxt));
@@ -237,9 +256,14 @@ struct NoEpi {
   template <int G>
   __device__ __forceinline__ void slot(const f32x4 (&)[CELLS]) {}
 };
-template <int OMASK, int I, int TAP, int PART, typename E>
-__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, const Pieces& w, E& e) {
-  if constexpr (pair_used<OMASK, I, TAP>()) {
+template <int OMASK, int I, int TAP, int PART, typename E, int PREC>
+__device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], Operands<OMASK, PREC>& xs, const PiecesT<PREC>& w, E& e) {
+  if constexpr (PREC == PREC_BF16) {             // the one product term; the pairs of a tap are independent accumulators
+    if constexpr (pair_used<OMASK, I, TAP>()) {
+      constexpr int o = TapMap<I, TAP>::o;
+      acc[o] = mfma_bf16(w.p[0], xs.x[I].p[0], acc[o]);
+    }
+  } else if constexpr (pair_used<OMASK, I, TAP>()) {
     constexpr int o = TapMap<I, TAP>::o;
     constexpr int n = pairs_before(OMASK, TAP, I), g = 6 * n;
     const Pieces (&x)[CELLS] = xs.x;
@@ -258,28 +282,34 @@ __device__ __forceinline__ void pair_mfma(f32x4 (&acc)[CELLS], Operands<OMASK>& 
   }
 }
 // all (input cell, TAP) pairs of the job's output cells: independent accumulators
-template <int OMASK, int TAP, int PART, typename E>
-__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, const Pieces& w, E& e) {
+template <int OMASK, int TAP, int PART, typename E, int PREC>
+__device__ __forceinline__ void tap_mfma(f32x4 (&acc)[CELLS], Operands<OMASK, PREC>& xs, const PiecesT<PREC>& w, E& e) {
   pair_mfma<OMASK, 0, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 1, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 2, TAP, PART>(acc, xs, w, e);
   pair_mfma<OMASK, 3, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 4, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 5, TAP, PART>(acc, xs, w, e);
   pair_mfma<OMASK, 6, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 7, TAP, PART>(acc, xs, w, e); pair_mfma<OMASK, 8, TAP, PART>(acc, xs, w, e);
+  if constexpr (PREC == PREC_BF16) __builtin_amdgcn_sched_barrier(0);   // a tap's MFMAs stay together, ahead of the ring's refill
 }
 
-template <int OMASK, int I>
-__device__ __forceinline__ void load_cell(Pieces (&x)[CELLS], const unsigned char* __restrict__ src, int a0) {
+template <int OMASK, int I, int PREC>
+__device__ __forceinline__ void load_cell(PiecesT<PREC> (&x)[CELLS], const unsigned char* __restrict__ src, int a0) {
 #ifdef NZ_ABLATE_A   // timing-only build: no LDS reads of the activation operands (outputs are wrong)
-  if constexpr (input_used<OMASK, I>()) { const uint32_t v = 0x3C003C00u + a0 + I; x[I].p[0] = x[I].p[1] = x[I].p[2] = u32x4{v, v, v, v}; asm volatile("" :: "v"(src)); }
+  if constexpr (input_used<OMASK, I>()) {
+    const uint32_t v = 0x3C003C00u + a0 + I;
+#pragma unroll
+    for (int piece = 0; piece < prec_pieces(PREC); ++piece) x[I].p[piece] = u32x4{v, v, v, v};
+    asm volatile("" :: "v"(src));
+  }
 #else
   if constexpr (input_used<OMASK, I>()) {
 #pragma unroll
-    for (int piece = 0; piece < resident_pieces(OMASK); ++piece)
+    for (int piece = 0; piece < resident_pieces(OMASK, PREC); ++piece)
       x[I].p[piece] = *reinterpret_cast<const u32x4*>(src + piece * PIECE_BYTES + I * (POS * 128) + a0);
   }
 #endif
 }
 // this lane's activation operands of one K group (slot address a0) for every used input cell
-template <int OMASK>
-__device__ __forceinline__ void load_cells(Pieces (&x)[CELLS], const unsigned char* __restrict__ src, int a0) {
+template <int OMASK, int PREC>
+__device__ __forceinline__ void load_cells(PiecesT<PREC> (&x)[CELLS], const unsigned char* __restrict__ src, int a0) {
   load_cell<OMASK, 0>(x, src, a0); load_cell<OMASK, 1>(x, src, a0); load_cell<OMASK, 2>(x, src, a0);
   load_cell<OMASK, 3>(x, src, a0); load_cell<OMASK, 4>(x, src, a0); load_cell<OMASK, 5>(x, src, a0);
   load_cell<OMASK, 6>(x, src, a0); load_cell<OMASK, 7>(x, src, a0); load_cell<OMASK, 8>(x, src, a0);
@@ -287,16 +317,16 @@ __device__ __forceinline__ void load_cells(Pieces (&x)[CELLS], const unsigned ch
 // A K group split over two areas (NET_SSLOT_SPLIT): quads 0-1 read slots 6-7 of `src`, quads 2-3 slots 0-1 of the strip.
 // The strip's strides are the buffer's shifted right by two, so one per-lane base and shift address both: the lanes
 // supply the same channels as from one buffer, and the MFMAs see the same operands.
-template <int OMASK, int I>
-__device__ __forceinline__ void load_cell_split(Pieces (&x)[CELLS], const unsigned char* base, unsigned sh) {
+template <int OMASK, int I, int PREC>
+__device__ __forceinline__ void load_cell_split(PiecesT<PREC> (&x)[CELLS], const unsigned char* base, unsigned sh) {
   if constexpr (input_used<OMASK, I>()) {
 #pragma unroll
-    for (int piece = 0; piece < 3; ++piece)
+    for (int piece = 0; piece < prec_pieces(PREC); ++piece)
       x[I].p[piece] = *reinterpret_cast<const u32x4*>(base + ((unsigned)(piece * STRIP_PIECE_BYTES + I * (POS * 32)) << sh));
   }
 }
-template <int OMASK>
-__device__ __forceinline__ void load_cells_split(Pieces (&x)[CELLS], const unsigned char* __restrict__ src,
+template <int OMASK, int PREC>
+__device__ __forceinline__ void load_cells_split(PiecesT<PREC> (&x)[CELLS], const unsigned char* __restrict__ src,
                                                  const unsigned char* __restrict__ strip, int pos, int quad) {
   const bool in_src = quad < 2;
   const unsigned char* base = in_src ? src + slot_addr(0, pos, 6 + quad) : strip + strip_addr(0, pos, quad - 2);
@@ -305,10 +335,12 @@ __device__ __forceinline__ void load_cells_split(Pieces (&x)[CELLS], const unsig
   load_cell_split<OMASK, 3>(x, base, sh); load_cell_split<OMASK, 4>(x, base, sh); load_cell_split<OMASK, 5>(x, base, sh);
   load_cell_split<OMASK, 6>(x, base, sh); load_cell_split<OMASK, 7>(x, base, sh); load_cell_split<OMASK, 8>(x, base, sh);
 }
-__device__ __forceinline__ void load_tap(Pieces& t, const float* __restrict__ w, int lane) {
+template <int PREC>
+__device__ __forceinline__ void load_tap(PiecesT<PREC>& t, const float* __restrict__ w, int lane) {
 #ifdef NZ_ABLATE_B   // timing-only build: no global loads of the weight operands (outputs are wrong)
   const uint32_t v = 0x3C003C00u + lane;
-  t.p[0] = t.p[1] = t.p[2] = u32x4{v, v, v, v};
+#pragma unroll
+  for (int piece = 0; piece < prec_pieces(PREC); ++piece) t.p[piece] = u32x4{v, v, v, v};
   asm volatile("" :: "v"(w));
 #else
   // uniform base + unsigned 32-bit lane offset: the loads take their base from scalar registers (no 64-bit address per
@@ -319,24 +351,28 @@ __device__ __forceinline__ void load_tap(Pieces& t, const float* __restrict__ w,
   unsigned long long b = reinterpret_cast<unsigned long long>(w);
   asm volatile("" : "+s"(b));                              // the tap's base stays a scalar: base + lane offset + immediate
   t.p[0] = *reinterpret_cast<gptr>(b + off);
-  t.p[1] = *reinterpret_cast<gptr>(b + off + 1024);
-  t.p[2] = *reinterpret_cast<gptr>(b + off + 2048);
+  if constexpr (PREC == PREC_F32) {
+    t.p[1] = *reinterpret_cast<gptr>(b + off + 1024);
+    t.p[2] = *reinterpret_cast<gptr>(b + off + 2048);
+  }
 #endif
 }
-__device__ __forceinline__ void load_b(FragS& f, const float* __restrict__ w, int lane) {   // a whole K group
+template <int PREC>
+__device__ __forceinline__ void load_b(FragST<PREC>& f, const float* __restrict__ w, int lane) {   // a whole K group
 #pragma unroll
-  for (int i = 0; i < W_RING; ++i) load_tap(f.rb[i], w + i * TAP_DWORDS, lane);
+  for (int i = 0; i < W_RING; ++i) load_tap(f.rb[i], w + i * tap_dwords(PREC), lane);
 }
-__device__ __forceinline__ void zero_b(FragS& f) {
+template <int PREC>
+__device__ __forceinline__ void zero_b(FragST<PREC>& f) {
 #pragma unroll
   for (int t = 0; t < W_RING; ++t)
 #pragma unroll
-    for (int piece = 0; piece < 3; ++piece) f.rb[t].p[piece] = u32x4{0u, 0u, 0u, 0u};
+    for (int piece = 0; piece < prec_pieces(PREC); ++piece) f.rb[t].p[piece] = u32x4{0u, 0u, 0u, 0u};
 }
 
 // the second K group's operands of every cell whose refill_step is STEP (slot address a1)
-template <int OMASK, int STEP>
-__device__ __forceinline__ void refill(Pieces (&x)[CELLS], const unsigned char* __restrict__ src, int a1) {
+template <int OMASK, int STEP, int PREC>
+__device__ __forceinline__ void refill(PiecesT<PREC> (&x)[CELLS], const unsigned char* __restrict__ src, int a1) {
   if constexpr (refill_step<OMASK, 0>() == STEP) load_cell<OMASK, 0>(x, src, a1);
   if constexpr (refill_step<OMASK, 1>() == STEP) load_cell<OMASK, 1>(x, src, a1);
   if constexpr (refill_step<OMASK, 2>() == STEP) load_cell<OMASK, 2>(x, src, a1);
@@ -354,12 +390,13 @@ __device__ __forceinline__ void refill(Pieces (&x)[CELLS], const unsigned char* 
 // two-group job -- the activation operands of the second group are read in place (LDS slot address a1) at their
 // refill_step, some after a tap of the first group, the others before a tap of the second; PART 0: a one-group job.
 // `e`: the epilogue scheduler of the job's LAST K group (PART 0 / 2; NoEpi for PART 1).
-template <int OMASK, int PART, typename E>
-__device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Operands<OMASK>& xs, FragS& f,
+template <int OMASK, int PART, typename E, int PREC>
+__device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Operands<OMASK, PREC>& xs, FragST<PREC>& f,
                                        const unsigned char* __restrict__ src, int a1,
                                        const float* __restrict__ wc, const float* __restrict__ wn, int lane, E& e) {
   constexpr bool A = PART == 1, B = PART == 2;
-  Pieces (&x)[CELLS] = xs.x;
+  constexpr int TAP_DWORDS = tap_dwords(PREC);        // (of this mode's stream)
+  PiecesT<PREC> (&x)[CELLS] = xs.x;
   if constexpr (B) refill<OMASK, 9>(x, src, a1);
   tap_mfma<OMASK, 0, PART>(acc, xs, f.rb[0], e); load_tap(f.rb[0], wc + 3 * TAP_DWORDS, lane);
   if constexpr (A) refill<OMASK, 0>(x, src, a1);
@@ -393,15 +430,15 @@ __device__ __forceinline__ void kgroup(f32x4 (&acc)[CELLS], Operands<OMASK>& xs,
 // ring holds the first three taps of the job's first K group; on exit those of the next job that reads
 // weights (`w_after`; the stream's start when there is none).  The K groups start at slot `sslot` of the source rows
 // (NET_SSLOT_SPLIT: one K group from two areas, load_cells_split).
-template <int OMASK, int KG, typename E>
-__device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragS& f, const unsigned char* __restrict__ src,
+template <int OMASK, int KG, typename E, int PREC>
+__device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragST<PREC>& f, const unsigned char* __restrict__ src,
                                           const unsigned char* __restrict__ strip, int sslot,
                                           const float* __restrict__ w, const float* __restrict__ w_after, int lane, E& e) {
   const int pos = lane & 15, quad = lane >> 4;
-  Operands<OMASK> xs;
+  Operands<OMASK, PREC> xs;
   if (KG == 1 && OMASK != 0x1FF && sslot == NET_SSLOT_SPLIT) load_cells_split<OMASK>(xs.x, src, strip, pos, quad);   // (no whole-tile job reads the strip)
   else load_cells<OMASK>(xs.x, src, slot_addr(0, pos, sslot + quad));
-  if constexpr (Operands<OMASK>::NP < 3) {                 // piece 2 of the first pairs
+  if constexpr (Operands<OMASK, PREC>::NP == 2) {          // piece 2 of the first pairs
     xs.src = src;
     xs.cur = slot_addr(0, pos, sslot + quad);
     xs.nxt = slot_addr(0, pos, sslot + 4 + quad);
@@ -412,9 +449,9 @@ __device__ __forceinline__ void job_kloop(f32x4 (&acc)[CELLS], FragS& f, const u
   if constexpr (KG == 2) {
     const int a1 = slot_addr(0, pos, sslot + 4 + quad);
     NoEpi none;
-    kgroup<OMASK, 1>(acc, xs, f, src, a1, w, w + NET_KG_DWORDS, lane, none);
-    if constexpr (Operands<OMASK>::NP < 3) xs.cur = a1;
-    kgroup<OMASK, 2>(acc, xs, f, src, a1, w + NET_KG_DWORDS, w_after, lane, e);
+    kgroup<OMASK, 1>(acc, xs, f, src, a1, w, w + kg_dwords(PREC), lane, none);
+    if constexpr (Operands<OMASK, PREC>::NP == 2) xs.cur = a1;
+    kgroup<OMASK, 2>(acc, xs, f, src, a1, w + kg_dwords(PREC), w_after, lane, e);
   } else {
     kgroup<OMASK, 0>(acc, xs, f, src, 0, w, w_after, lane, e);
   }
@@ -587,10 +624,42 @@ __device__ __forceinline__ void epi_read_cells(u32x2 (&q)[CELLS][3], const unsig
     epi_read_cells<CMASK, O + 1>(q, res, off);
   }
 }
-template <int OMASK, int ACT, bool RES, bool STRIP = false>
+// Plain-bf16 mode, one cell: the residual is the STORED bf16 value, widened; the float32 mode's activation; one rounding
+// to nearest even and one 8-byte store into piece plane 0.
+template <int O, int ACT, bool RES, bool STRIP>
+__device__ __forceinline__ void epilogue_cell_bf16(const f32x4& a, const u32x2& q, unsigned char* __restrict__ dst, int off) {
+  constexpr int CB = STRIP ? POS * 32 : POS * 128;
+  f32x4 v = a;
+  if constexpr (RES) {
+    v[0] = a[0] + bf16_lo(q[0]); v[1] = a[1] + bf16_hi(q[0]);
+    v[2] = a[2] + bf16_lo(q[1]); v[3] = a[3] + bf16_hi(q[1]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = epi_act<ACT>(v[r]);
+  *reinterpret_cast<u32x2*>(dst + O * CB + off) = u32x2{pack_rne16(v[0], v[1]), pack_rne16(v[2], v[3])};
+}
+template <int CMASK, int ACT, bool RES, bool STRIP, int O = 0>
+__device__ __forceinline__ void epilogue_cells_bf16(const f32x4 (&acc)[CELLS], const u32x2 (&q)[CELLS],
+                                                    unsigned char* __restrict__ dst, int off) {
+  if constexpr (O < CELLS) {
+    if constexpr ((CMASK >> O) & 1) epilogue_cell_bf16<O, ACT, RES, STRIP>(acc[O], q[O], dst, off);
+    epilogue_cells_bf16<CMASK, ACT, RES, STRIP, O + 1>(acc, q, dst, off);
+  }
+}
+template <int OMASK, int ACT, bool RES, bool STRIP = false, int PREC = PREC_F32>
 __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[CELLS], unsigned char* __restrict__ dst,
                                              const unsigned char* res, int lane, int nt) {
   const int off = epi_off<STRIP>(lane, nt);
+  if constexpr (PREC == PREC_BF16) {      // all residual reads in flight at once, before any write, as below
+    u32x2 q1[CELLS];
+    if constexpr (RES) {
+#pragma unroll
+      for (int o = 0; o < CELLS; ++o)
+        if ((OMASK >> o) & 1) q1[o] = *reinterpret_cast<const u32x2*>(res + o * (POS * 128) + off);
+    }
+    epilogue_cells_bf16<OMASK, ACT, RES, STRIP>(acc, q1, dst, off);
+    return;
+  }
 #ifdef NZ_ABLATE_EPI   // timing-only build: one store per job instead of the epilogue (outputs are wrong)
   {
     float t = 0.f;
@@ -671,25 +740,25 @@ struct ProgEpi {
 };
 
 // (whole-tile jobs, group 0, go to an activation buffer only: engine.hip solo_list)
-template <int OMASK>
+template <int OMASK, int PREC = PREC_F32>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob& job, unsigned char* __restrict__ lds,
                                          unsigned char* __restrict__ strip, int lane, int policy_channels, int n_valid,
                                          float* logits, float* vcells) {
   constexpr bool BUFFER_ONLY = OMASK == 0x1FF;
   if (!BUFFER_ONLY && job.dst == NET_DST_STRIP) {             // ReLU only: the host compiles nothing else into the strip
-    epilogue_lds<OMASK, 1, false, true>(acc, strip, nullptr, lane, 0);
+    epilogue_lds<OMASK, 1, false, true, PREC>(acc, strip, nullptr, lane, 0);
   } else if (BUFFER_ONLY || job.dst < NET_BUFFERS) {
     unsigned char* dst = lds + job.dst * ACT_BYTES;
     if (job.res >= 0) {
-      epilogue_lds<OMASK, 1, true>(acc, dst, lds + job.res * ACT_BYTES, lane, job.dtile);
+      epilogue_lds<OMASK, 1, true, false, PREC>(acc, dst, lds + job.res * ACT_BYTES, lane, job.dtile);
     } else if (job.act == 1) {
-      epilogue_lds<OMASK, 1, false>(acc, dst, nullptr, lane, job.dtile);
+      epilogue_lds<OMASK, 1, false, false, PREC>(acc, dst, nullptr, lane, job.dtile);
     } else if (job.act == 2) {
-      epilogue_lds<OMASK, 2, false>(acc, dst, nullptr, lane, job.dtile);
+      epilogue_lds<OMASK, 2, false, false, PREC>(acc, dst, nullptr, lane, job.dtile);
     } else if (job.act == 3) {
-      epilogue_lds<OMASK, 3, false>(acc, dst, nullptr, lane, job.dtile);
+      epilogue_lds<OMASK, 3, false, false, PREC>(acc, dst, nullptr, lane, job.dtile);
     } else {
-      epilogue_lds<OMASK, 0, false>(acc, dst, nullptr, lane, job.dtile);
+      epilogue_lds<OMASK, 0, false, false, PREC>(acc, dst, nullptr, lane, job.dtile);
     }
   } else if (job.dst == NET_DST_POLICY) {     // policy logits [pos][P][9]
     // (addresses re-derived from an opaque copy of the lane id: hoisted out of the job loop they would sit in
@@ -721,8 +790,8 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[CELLS], const NetJob
 }
 
 // one job: K loop, input-plane step, epilogue
-template <int OMASK, typename Stamp, typename Fetch>
-__device__ __forceinline__ void run_job_plain(const NetJob& job, FragS& f, const float* __restrict__ W,
+template <int OMASK, typename Stamp, typename Fetch, int PREC>
+__device__ __forceinline__ void run_job_plain(const NetJob& job, FragST<PREC>& f, const float* __restrict__ W,
                                               const float* w_after, unsigned char* __restrict__ lds,
                                               unsigned char* __restrict__ strip,
                                               const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
@@ -740,7 +809,7 @@ __device__ __forceinline__ void run_job_plain(const NetJob& job, FragS& f, const
   if (job.extra) extra_planes<OMASK>(acc, W + job.wx_off, inp, lane);
   stamp(1);
   fetch_next();          // the next job's descriptor: in flight under the epilogue, in no register during the K loop
-  epilogue<OMASK>(acc, job, lds, strip, lane, policy_channels, n_valid, logits, value);   // `value`: the per-cell staging area
+  epilogue<OMASK, PREC>(acc, job, lds, strip, lane, policy_channels, n_valid, logits, value);   // `value`: the per-cell staging area
   stamp(2);
 }
 // a job flagged NET_JOB_PROGRESSIVE: one or two K groups from a buffer, no input planes, destination a buffer; the
@@ -766,14 +835,14 @@ __device__ __forceinline__ void run_job_prog(const NetJob& job, FragS& f, const 
   e.finish(acc);
   stamp(2);
 }
-template <int OMASK, typename Stamp, typename Fetch>
-__device__ __forceinline__ void run_job(const NetJob& job, FragS& f, const float* __restrict__ W,
+template <int OMASK, typename Stamp, typename Fetch, int PREC>
+__device__ __forceinline__ void run_job(const NetJob& job, FragST<PREC>& f, const float* __restrict__ W,
                                         const float* w_after, unsigned char* __restrict__ lds,
                                         unsigned char* __restrict__ strip,
                                         const float* __restrict__ inp, int lane, int policy_channels, int n_valid,
                                         float* logits, float* value, Stamp&& stamp, Fetch&& fetch_next) {
 #ifndef NZ_ABLATE_EPI
-  if constexpr (net_og_progressive(OMASK)) {
+  if constexpr (PREC == PREC_F32 && net_og_progressive(OMASK)) {     // (plain-bf16: end-of-job epilogues, the same values)
     if (job.flags & NET_JOB_PROGRESSIVE) {      // (engine.hip add_stage: ReLU with or without residual, or tanh)
       if (job.res >= 0) run_job_prog<OMASK, 1, true>(job, f, W, w_after, lds, strip, lane, stamp, fetch_next);
       else if (job.act == 2) run_job_prog<OMASK, 2, false>(job, f, W, w_after, lds, strip, lane, stamp, fetch_next);
@@ -812,11 +881,18 @@ __device__ __forceinline__ void net_value_mean(const float* lds_f, int tid, int 
 // whole-tile job.  The jobs of a stage are independent of each other, and the progressive-epilogue hazard rule holds for
 // the stage as a whole, so which wave runs a job changes nothing it computes.  The job loop is the same for both lists.
 // SOLO: the caller may steal, so the whole-tile job is compiled in (the stand-alone network kernel does without it).
-template <bool STAMPS = false, bool SOLO = false>
+// PREC: the arithmetic mode; `W` and the program's weight offsets are that mode's stream.  PREC_BF16 has no stealing pass.
+// `after_stage(n)` (the dump kernel only; every thread, after the n-th stage's barrier): copies out what the stage left.
+struct NoStageHook {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <bool STAMPS = false, bool SOLO = false, int PREC = PREC_F32, typename StageHook = NoStageHook>
 __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, const float* __restrict__ W,
                                          float* __restrict__ lds_f, const float* __restrict__ inp,
                                          int policy_channels, int n_valid, float* logits, float* value,
-                                         unsigned long long* stamps = nullptr, int steal = 0) {
+                                         unsigned long long* stamps = nullptr, int steal = 0,
+                                         StageHook after_stage = StageHook()) {
+  static_assert(PREC == PREC_F32 || !SOLO, "the stolen pass is float32 only");
   unsigned char* __restrict__ lds = reinterpret_cast<unsigned char*>(lds_f);
   float* const vcells = lds_f + NET_BUFFERS * ACT_FLOATS + INP_FLOATS;
   unsigned char* const strip = reinterpret_cast<unsigned char*>(vcells + VAL_FLOATS);
@@ -829,9 +905,10 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
   const int n_jobs = __builtin_amdgcn_readfirstlane(steal ? prog->solo_n_jobs[wave] : prog->n_jobs[wave]);
   const int first_w = __builtin_amdgcn_readfirstlane(steal ? prog->solo_first_w[wave] : prog->first_w_off[wave]);
 
-  FragS f;
+  FragST<PREC> f;
   zero_b(f);
   if (first_w >= 0) load_b(f, W + first_w, lane);
+  int stages_done = 0;
 
   unsigned long long tk[4] = {0, 0, 0, 0}, ts = 0;
 #ifdef NZ_STAGE_STAMPS
@@ -893,6 +970,9 @@ __device__ __forceinline__ void net_tile(const NetProgram* __restrict__ prog, co
     }
     stamp(2);
     if (job.flags & NET_JOB_STAGE_END) __syncthreads();
+    if constexpr (!std::is_same<StageHook, NoStageHook>::value) {
+      if (job.flags & NET_JOB_STAGE_END) after_stage(stages_done++);
+    }
     stamp(3);
 #ifdef NZ_STAGE_STAMPS   // diagnostic build: per-stage ticks of waves 0 and 4 of workgroup 0 (K loops + planes, epilogue, barrier)
     if constexpr (STAMPS) {

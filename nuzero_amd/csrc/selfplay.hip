@@ -141,6 +141,9 @@ __device__ __forceinline__ int opaque(int v) {
 
 // The network phase as a real call: its registers are allocated on their own, as in the stand-alone network kernel
 // (inlined into the persistent loop the allocator spills ~140 registers around the job loop).
+// PREC_BF16: the plain-bf16 pass (net_dev.hpp) -- no solo lists, `steal` is 0; the rows' input planes are 0 / 1, which
+// rounding leaves as they are.
+template <int PREC>
 __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W, float* lds, const float* inp,
                                                     float* out_logits, float* out_value, int steal) {
   // arguments of a device function arrive in vector registers; these two are uniform
@@ -150,6 +153,10 @@ __device__ __forceinline__ void net_phase(const NetProgram* prog, const float* W
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
     return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
   };
+  if constexpr (PREC == PREC_BF16)
+    net_tile<false, false, PREC_BF16>(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds,
+                                      inp, 1, POS, out_logits, out_value, nullptr, 0);
+  else
   net_tile<false, true>(static_cast<const NetProgram*>(uniform(prog)), static_cast<const float*>(uniform(W)), lds, inp, 1,
                         POS, out_logits, out_value, nullptr, steal);       // (true: with the solo lists' whole-tile job)
 }
@@ -241,8 +248,11 @@ __device__ __forceinline__ int burst_under_pass(int32_t (*park_row)[POS], int32_
 
 // PACKED: the network phase is the packed pass for slots_per_wg <= NET_PACKED_MAX rows.  It has no stealing partner: no
 // wave sits a pass out (the host keeps burst_under_net off for such an engine).
-template <bool STAMPS, bool PACKED = false>
+// PREC: the network pass's arithmetic (net_dev.hpp).  PREC_BF16 exists for the 16-column pass on a wave's own job list
+// only: the host launches it with burst_under_net 0 and never packed.
+template <bool STAMPS, bool PACKED = false, int PREC = PREC_F32>
 __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
+  static_assert(PREC == PREC_F32 || !PACKED, "the packed pass is float32 only");
   __shared__ __attribute__((aligned(16))) float lds[NET_LDS_FLOATS + POS * TTT_ACTIONS + POS];
   float* const inp = lds + NET_BUFFERS * ACT_FLOATS;
   float* const out_logits = lds + NET_LDS_FLOATS;             // [16][9], after net_tile's own areas
@@ -461,7 +471,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     row_pending = pending;
     row_cap = row_capped(st);
     }
-    if (!PACKED && p.burst_under_net != 0) {
+    if (!PACKED && PREC == PREC_F32 && p.burst_under_net != 0) {
       const int wave_cap = __builtin_amdgcn_ballot_w64(row_cap) != 0ull ? 1 : 0;
       if ((tid & 63) == 0) s_capped[tid >> 6] = wave_cap;
     }
@@ -484,7 +494,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
     // when both have one; the other runs both halves of the SIMD's tile.  (s_capped is written again only after the
     // pass's barriers.)  Uniform per wave.
     int absent = 0, steal = 0;
-    if (!PACKED && p.burst_under_net != 0) {
+    if (!PACKED && PREC == PREC_F32 && p.burst_under_net != 0) {
       const int w = tid >> 6, lo = w & (NET_WAVES / 2 - 1);
       const int cap_lo = s_capped[lo], cap_hi = s_capped[lo + NET_WAVES / 2];
       const int out = p.burst_under_net == 2 ? lo : cap_lo ? lo : cap_hi ? lo + NET_WAVES / 2 : -1;   // 2: the test hook
@@ -510,7 +520,7 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
       }
     } else {
       const SelfplayArgs& na = kernel_args();
-      net_phase(na.prog, na.W, lds, inp, out_logits, out_value, steal);
+      net_phase<PREC>(na.prog, na.W, lds, inp, out_logits, out_value, steal);
     }
     // net_tile ends with a barrier: outputs are visible to every row
     if constexpr (STAMPS) {
@@ -553,11 +563,14 @@ __global__ __launch_bounds__(NET_THREADS) void selfplay_kernel(SelfplayArgs) {
 int selfplay_blocks(int n_slots, int slots_per_wg) { return (n_slots + slots_per_wg - 1) / slots_per_wg; }
 
 void launch_selfplay(const TreeParams& p, const NetProgram* prog_dev, int n_layers, const float* weights,
-                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s) {
+                     const double* noise, const double* uniforms, unsigned long long* stamps, bool packed, hipStream_t s,
+                     int prec) {
   const int blocks = selfplay_blocks(p.n_slots, p.slots_per_wg);
   (void)n_layers;
   const SelfplayArgs a{p, prog_dev, weights, noise, uniforms, stamps};
-  if (packed && stamps != nullptr) hipLaunchKernelGGL((selfplay_kernel<true, true>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  if (prec == PREC_BF16 && stamps != nullptr) hipLaunchKernelGGL((selfplay_kernel<true, false, PREC_BF16>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  else if (prec == PREC_BF16) hipLaunchKernelGGL((selfplay_kernel<false, false, PREC_BF16>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
+  else if (packed && stamps != nullptr) hipLaunchKernelGGL((selfplay_kernel<true, true>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
   else if (packed) hipLaunchKernelGGL((selfplay_kernel<false, true>), dim3(blocks), dim3(NET_THREADS), 0, s, a);
   else if (stamps != nullptr) hipLaunchKernelGGL(selfplay_kernel<true>, dim3(blocks), dim3(NET_THREADS), 0, s, a);
   else hipLaunchKernelGGL(selfplay_kernel<false>, dim3(blocks), dim3(NET_THREADS), 0, s, a);

@@ -11,6 +11,10 @@ from ._lib import lib, check
 from .search_config import to_struct
 
 
+_PREC = {"float32": _lib.NZ_PREC_FLOAT32, "bf16": _lib.NZ_PREC_BF16}
+_PREC_NAMES = {v: k for k, v in _PREC.items()}
+
+
 def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
 
@@ -24,9 +28,16 @@ class SelfPlayEngine:
 
     ``search_config`` is the reference's nested dict; ``training`` is the second
     argument of the reference's ``Explorer(search_config, training)``.
+
+    ``precision``: "float32" (the default: 1e-5 from the reference) or "bf16", the opt-in plain-bf16 arithmetic of the
+    network (nz_engine_precision): one rounded bf16 per weight, input plane and stored activation, one MFMA per K step.
+    It exists for the 16-column pass on a wave's own job list: a bf16 engine never takes the packed pass and no wave
+    sits a pass out, `positions_per_pass` is 16, and the packed and stamped forwards raise.
     """
 
-    def __init__(self, search_config, n_games, training=True, device=0, negate_player=2, n_slots=None):
+    def __init__(self, search_config, n_games, training=True, device=0, negate_player=2, n_slots=None, precision=None):
+        if precision is not None and precision not in _PREC:
+            raise ValueError(f"bad precision {precision!r}: 'float32' or 'bf16'")
         if not torch.cuda.is_available():
             raise RuntimeError("nuzero_amd needs a ROCm GPU; there is no CPU fallback")
         self.device = torch.device("cuda", device)
@@ -45,6 +56,24 @@ class SelfPlayEngine:
         self.state_shape = (d.state_channels, d.rows, d.cols)
         self.node_capacity = d.node_capacity
         self.net_spec = None
+        if precision is not None:
+            self.precision = precision
+
+    @property
+    def precision(self):
+        cur = c_int32(0)
+        check(lib.nz_engine_precision(self._h, -1, byref(cur)), self._h)
+        return _PREC_NAMES[cur.value]
+
+    @precision.setter
+    def precision(self, mode):
+        """A change of mode drops the engine's weights: set_weights again (a table set with set_table stays)."""
+        if mode not in _PREC:
+            raise ValueError(f"bad precision {mode!r}: 'float32' or 'bf16'")
+        if _PREC[mode] != _PREC[self.precision]:
+            self.net_spec = None
+            self.position_cache = False
+        check(lib.nz_engine_precision(self._h, _PREC[mode], None), self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -129,6 +158,31 @@ class SelfPlayEngine:
                 check(lib.nz_net_forward_packed(self._h, _ptr(x), b, int(positions_per_pass), _ptr(logits), _ptr(value),
                                                 _ptr(probs), _stream()), self._h)
         return logits, value, probs
+
+    def net_forward_dump(self, states):
+        """Plain-bf16 mode only, the test hook (nz_net_forward_dump): net_forward's outputs and what the device itself
+        held, widened to float32, for all R = 16 * ceil(B / 16) rows of the tiles: a dict with logits [B, 9], value [B],
+        probs [B, 9], planes [R, 9 cells, 4], acts [stages, R, 1296] (after each stage piece plane 0 of buffer 0 and
+        buffer 1, [9 cells, 64] each, then of the strip, [9 cells, 16]) and vcells [R, 9]."""
+        x = torch.as_tensor(states, dtype=torch.float32).to(self.device).contiguous()
+        b = x.shape[0]
+        rows = 16 * ((b + 15) // 16)
+        n_stages = c_int32(0)
+        dev = self.device
+        logits = torch.empty((b, 9), dtype=torch.float32, device=dev)
+        value = torch.empty((b,), dtype=torch.float32, device=dev)
+        probs = torch.empty((b, 9), dtype=torch.float32, device=dev)
+        planes = torch.zeros((rows, 9, 4), dtype=torch.float32, device=dev)
+        vcells = torch.zeros((rows, 9), dtype=torch.float32, device=dev)
+        acts = torch.zeros((0, rows, _lib.NZ_NET_DUMP_ROW), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            # (the first call only asks for the number of stages)
+            check(lib.nz_net_forward_dump(self._h, _ptr(x), 0, _ptr(logits), _ptr(value), _ptr(probs), _ptr(planes),
+                                          _ptr(planes), 0, _ptr(vcells), byref(n_stages), _stream()), self._h)
+            acts = torch.zeros((n_stages.value, rows, _lib.NZ_NET_DUMP_ROW), dtype=torch.float32, device=dev)
+            check(lib.nz_net_forward_dump(self._h, _ptr(x), b, _ptr(logits), _ptr(value), _ptr(probs), _ptr(planes),
+                                          _ptr(acts), n_stages.value, _ptr(vcells), byref(n_stages), _stream()), self._h)
+        return dict(logits=logits, value=value, probs=probs, planes=planes, acts=acts, vcells=vcells)
 
     @property
     def positions_per_pass(self):

@@ -139,8 +139,9 @@ class Gamer:
         `shared_storage` is anything with ``get()`` returning a Network_Manager (or
         the Network_Manager itself); `buffer` anything with ``save_game(game, i)``
         or None.  `game_class` is Tic_Tac_Toe or SCS_Game (recognised by name); for SCS `game_args[0]` is
-        the game config file and all `num_games` games of a round run concurrently.  `net_precision` (SCS only): the
-        board net's arithmetic, "float32" or the opt-in "bf16" (BoardNet(precision=))."""
+        the game config file and all `num_games` games of a round run concurrently.  `net_precision`: the network's
+        arithmetic, "float32" or the opt-in plain "bf16" -- the board net's on SCS (BoardNet(precision=)), the engine's on
+        Tic-Tac-Toe (SelfPlayEngine(precision=); play_games, play_game and play_forever's engines all carry it)."""
         if net_precision not in ("float32", "bf16"):
             raise ValueError(f"bad net_precision {net_precision!r}")
         self.net_precision = net_precision
@@ -148,8 +149,6 @@ class Gamer:
         self.is_scs = "scs" in name
         if not self.is_scs and "tic" not in name and "ttt" not in name:
             raise NotImplementedError(f"game {name!r}: Tic_Tac_Toe and SCS_Game run on the GPU engine")
-        if not self.is_scs and net_precision != "float32":
-            raise ValueError("net_precision='bf16' exists for the SCS board nets only: the Tic-Tac-Toe network is float32")
         if cache_choice not in ("disabled", None, "dict", "keyless"):
             raise ValueError(f"bad cache_choice {cache_choice!r}")          # general_utils.py:14-24
         self.cache_choice = cache_choice if cache_choice else "disabled"
@@ -194,7 +193,7 @@ class Gamer:
             self._board_net = None
             return
         self.engine = SelfPlayEngine(search_config, num_games, training=True, device=device,
-                                     n_slots=concurrent_games or num_games)
+                                     n_slots=concurrent_games or num_games, precision=net_precision)
 
     def _network(self):
         """shared_storage.get() (Gamer.py:40,61).  A raw module / state dict is wrapped once and the wrapper kept, so
@@ -309,7 +308,8 @@ class Gamer:
             if not made:
                 made.append(first)
                 return first
-            e = SelfPlayEngine(self.search_config, self.num_games, training=True, device=self.device, n_slots=first.n_slots)
+            e = SelfPlayEngine(self.search_config, self.num_games, training=True, device=self.device, n_slots=first.n_slots,
+                               precision=self.net_precision)
             made.append(e)
             return e
 

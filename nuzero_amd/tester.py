@@ -432,9 +432,15 @@ class TttAgentMatch:
     ("policy",), ("random",) as ScsAgentMatch takes them, in any pairing but two random sides.  `engines`: per side the
     SelfPlayEngine(training=False) of an MCTS or policy side, None for a random side; after play() an MCTS side's
     engine holds its search records (export()).  `share_policy_engine`: two policy sides that play with the SAME
-    network use one engine instead of one each."""
+    network use one engine instead of one each.  `precision`: the network arithmetic of the sides' engines, "float32" /
+    "bf16" (SelfPlayEngine(precision=)) for both or a pair, one per side (None: the default)."""
 
-    def __init__(self, agent1, agent2, n_matches, device=0, share_policy_engine=False):
+    def __init__(self, agent1, agent2, n_matches, device=0, share_policy_engine=False, precision=None):
+        self.precisions = tuple(precision) if isinstance(precision, (tuple, list)) else (precision, precision)
+        if len(self.precisions) != 2 or any(p not in (None, "float32", "bf16") for p in self.precisions):
+            raise ValueError(f"bad precision {precision!r}: 'float32', 'bf16' or a pair of them")
+        if share_policy_engine and self.precisions[0] != self.precisions[1]:
+            raise ValueError("share_policy_engine: one engine has one precision")
         self.kinds, self.search_cfgs = zip(*(_agent_spec(a) for a in (agent1, agent2)))
         if self.kinds == ("random", "random"):
             raise ValueError("two random agents: one side must be an MCTS or policy agent (its engine holds the matches)")
@@ -449,13 +455,14 @@ class TttAgentMatch:
         self.n_matches, self.device = int(n_matches), device
         from .engine import SelfPlayEngine            # (needs the GPU from here on)
         engines = []
-        for kind, sc in zip(self.kinds, self.search_cfgs):
+        for kind, sc, prec in zip(self.kinds, self.search_cfgs, self.precisions):
             if kind == "random":
                 engines.append(None)
             elif share_policy_engine and engines:
                 engines.append(engines[0])            # one engine, one network
             else:
-                engines.append(SelfPlayEngine(sc or _NO_SEARCH, self.n_matches, training=False, device=device))
+                kw = {"precision": prec} if prec is not None else {}
+                engines.append(SelfPlayEngine(sc or _NO_SEARCH, self.n_matches, training=False, device=device, **kw))
         self.engines = tuple(engines)
 
     def close(self):
@@ -549,11 +556,11 @@ class TttMatch(TttAgentMatch):
     deterministic, so from the empty board the matches of a round are copies of one game: pass `start_boards` (one
     position per match, e.g. ttt_positions.openings(2)) for matches that differ."""
 
-    def __init__(self, search_cfg_1, search_cfg_2, n_matches, device=0):
+    def __init__(self, search_cfg_1, search_cfg_2, n_matches, device=0, precision=None):
         for i, sc in enumerate((search_cfg_1, search_cfg_2)):
             if not isinstance(sc, Mapping):
                 raise ValueError(f"agent {i + 1}: TttMatch takes two search configs (scripted sides: TttAgentMatch)")
-        super().__init__(("mcts", search_cfg_1), ("mcts", search_cfg_2), n_matches, device=device)
+        super().__init__(("mcts", search_cfg_1), ("mcts", search_cfg_2), n_matches, device=device, precision=precision)
 
     def play(self, weights1, weights2, start_boards=None, **net_kwargs):
         return super().play(weights1, weights2, start_boards=start_boards, **net_kwargs)
