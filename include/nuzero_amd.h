@@ -953,6 +953,64 @@ nz_status nz_replay_gather(nz_replay* h, const int64_t* slots_dev, int64_t batch
 /* synchronises; NZ_ERR_OVERFLOW if a kernel has seen a slot, an action or a child count out of range (sticky, see above) */
 nz_status nz_replay_check(nz_replay* h, void* stream);
 
+/* ---- compact SCS replay buffer ("states as compact game state re-rendered") ----------
+ * A second buffer beside nz_replay for SCS games: a slot holds the game STATE the position was, not its image, and the
+ * gather renders the image.  A record is self-contained:
+ *   int32 n_children, float value, int32 game_index | float terrain[tiles][3] (the game's own map, the image's values) |
+ *   {int32 action, float policy}[max_children] (the root's child list) | the rules' state struct (640 bytes) |
+ *   int8 victory-point tiles [2 * tiles reserved]
+ * 1.5 KB on a 5x5 board with 64 children, 4.1 KB on 10x10 with 256, against 10.7 KB and 42.8 KB of a dense row.  Slots
+ * are assigned by the caller exactly as for nz_replay.  All array arguments are device pointers unless named _host;
+ * work is enqueued on `stream`. */
+typedef struct nz_scs_replay nz_scs_replay;
+/* Host code, no device needed: the bytes of one record for boards of `desc`'s shape with `max_children` child entries
+ * (<= 0: the description's own bound on the legal actions of a position, rounded up to a multiple of 64 as the search
+ * engine's records round it).  -1, with a message for the last-error call with NULL, for a description the rules refuse
+ * or a max_children below the description's bound. */
+int64_t nz_scs_replay_record_bytes(const nz_scs_desc* desc, int32_t max_children);
+/* `capacity_positions` records of `max_children` child entries for images [channels][rows][cols] and `num_actions`
+ * actions (they must be an SCS shape: channels = 48 + 19 * stacking, actions = (3 + 9 * stacking) * rows * cols).
+ * NZ_ERR_ARG for sizes that are none, NZ_ERR_HIP where `device` is no HIP device or the allocation fails. */
+nz_status nz_scs_replay_create(nz_scs_replay** out, int64_t capacity_positions, int32_t max_children, int32_t channels,
+                               int32_t rows, int32_t cols, int32_t num_actions, int32_t device);
+void nz_scs_replay_destroy(nz_scs_replay* h);
+const char* nz_scs_replay_last_error(const nz_scs_replay* h);
+nz_status nz_scs_replay_dims(const nz_scs_replay* h, int64_t* capacity, int32_t* record_bytes, int32_t* max_children,
+                             int32_t* num_actions);
+/* The game description of `game_index` (0 .. 15), which is what the trainer buckets batches by.  NZ_ERR_ARG: rows,
+ * columns, action planes or channels differ from the buffer's; the description's bound on a position's legal actions
+ * exceeds the buffer's max_children; the index already has a DIFFERENT description (the same one again is NZ_OK). */
+nz_status nz_scs_replay_register(nz_scs_replay* h, int32_t game_index, const nz_scs_desc* desc);
+/* Replays the first `n_games` games of a finished round from their recorded actions [G][max_moves] (lengths [G],
+ * outcomes [G] int32; terrain float [G][tiles][3] and vp int32 [G][n_vp0 + n_vp1][2] for per-game maps, or both NULL),
+ * one wavefront per game, and stores nothing.  Before every step the action must be inside 0 .. A-1 and legal; a game
+ * that reached its end must have the recorded outcome; a game that stops before its end is accepted as it is.
+ * Synchronises; NZ_ERR_ARG with "game G, move M: ..." for the first record that fails. */
+nz_status nz_scs_replay_check_games(nz_scs_replay* h, int32_t game_index, int64_t n_games, const int32_t* actions_dev,
+                                    int32_t max_moves, const int32_t* lengths_dev, const int32_t* outcomes_dev,
+                                    const float* terrain_dev, const int32_t* vp_dev, void* stream);
+/* The same replay in one launch, storing move m of game g in slot dst_slot_dev[g][m] (int64 [G][dst_stride]; negative,
+ * or m >= dst_stride: not stored).  Child lists as the search engine exports them: child_action / child_visit int32
+ * [G][max_moves][round_children], n_children [G][max_moves]; policy = (float)((double)visit / (double)sum of visits),
+ * 0 for a zero visit count, as the dense buffer's append forms it.  Meant to follow a clean check of the same round: a
+ * record the check would refuse stops its game's replay and raises flag 8. */
+nz_status nz_scs_replay_save(nz_scs_replay* h, int32_t game_index, int64_t n_games, const int32_t* actions_dev,
+                             int32_t max_moves, const int32_t* lengths_dev, const int32_t* outcomes_dev,
+                             const float* terrain_dev, const int32_t* vp_dev, const int32_t* child_action_dev,
+                             const int32_t* child_visit_dev, const int32_t* n_children_dev, int32_t round_children,
+                             const int64_t* dst_slot_dev, int32_t dst_stride, void* stream);
+/* states [B][channels][rows][cols], policies [B][A], values [B], game indices [B] of the slots of a batch, one wavefront
+ * per row; each output may be NULL.  A slot outside 0 .. capacity-1 raises flag 4 and leaves its row as it was. */
+nz_status nz_scs_replay_gather(nz_scs_replay* h, const int64_t* slots_dev, int64_t batch, float* states_out,
+                               float* policies_out, float* values_out, int32_t* game_index_out, void* stream);
+/* synchronises; NZ_ERR_OVERFLOW while the sticky error word is set: 1 slot at or beyond capacity, 2 child count or child
+ * action out of range, 4 batch slot out of range, 8 unchecked record in a save, 16 a slot's game index has no description,
+ * 32 a slot's state or map points outside the board (never saved, or a damaged checkpoint; the row is left as it was) */
+nz_status nz_scs_replay_check(nz_scs_replay* h, void* stream);
+/* the raw records of slots 0 .. n-1 to / from a device byte buffer of n * record_bytes (checkpoints) */
+nz_status nz_scs_replay_export_slots(nz_scs_replay* h, int64_t n, void* bytes_dev, void* stream);
+nz_status nz_scs_replay_import_slots(nz_scs_replay* h, int64_t n, const void* bytes_dev, void* stream);
+
 /* ---- batched loss ---------------------------------------------------------------
  * AlphaZero.calculate_loss (Training/AlphaZero.py:891-921) for a whole batch in one launch, with the gradients of the
  * combined loss: losses3 = (value_loss, policy_loss, combined_loss); dlogits [B, A], dvalues [B] may be NULL.

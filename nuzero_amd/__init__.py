@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("ScsMatch", "ScsAgentMatch", "ScsTester", "TttMatch", "TttAgentMatch", "TttTester"):
         from . import tester
         return getattr(tester, name)
+    if name == "ScsReplayBuffer":              # the compact SCS replay buffer (it loads the shared library)
+        from . import replay_scs
+        return replay_scs.ScsReplayBuffer
     if name == "ttt_positions":                # start positions of the Tic-Tac-Toe matches (plain numpy)
         import importlib
         return importlib.import_module(".ttt_positions", __name__)

@@ -230,6 +230,20 @@ SIGNATURES = {
                                    c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p]),
     "nz_replay_gather": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_replay_check": (c_int32, [c_void_p, c_void_p]),
+    "nz_scs_replay_record_bytes": (c_int64, [POINTER(ScsDesc), c_int32]),
+    "nz_scs_replay_create": (c_int32, [POINTER(c_void_p), c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "nz_scs_replay_destroy": (None, [c_void_p]),
+    "nz_scs_replay_last_error": (c_char_p, [c_void_p]),
+    "nz_scs_replay_dims": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "nz_scs_replay_register": (c_int32, [c_void_p, c_int32, POINTER(ScsDesc)]),
+    "nz_scs_replay_check_games": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "nz_scs_replay_save": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "nz_scs_replay_gather": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nz_scs_replay_check": (c_int32, [c_void_p, c_void_p]),
+    "nz_scs_replay_export_slots": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "nz_scs_replay_import_slots": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
     "nz_loss_forward_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_loss_last_error": (c_char_p, []),

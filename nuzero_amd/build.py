@@ -31,6 +31,7 @@ UNITS = [
     ("ttt_agents.hip", ["-ffp-contract=off"]),
     ("boardnet.hip", []),
     ("replay.hip", ["-ffp-contract=off"]),
+    ("scs_replay.hip", ["-ffp-contract=off"]),
     ("loss.hip", []),
     ("rng_host.cpp", ["-ffp-contract=off"]),
 ]

@@ -48,6 +48,22 @@ struct ScsRules {                     // immutable game description (one per eng
 
 bool scs_fill_rules(const nz_scs_desc* d, ScsRules* out, std::string* err);   // scs.hip (host)
 
+// The most legal actions one position of the game can have: the arrival tiles of a unit (placement), 7 per unit of the
+// player to move (6 directions + end movement; end fighting + <= 6 adjacent enemy tiles), 6 * stacking + 1 attackers.
+// The search engine's records hold this many children per node, rounded up to whole wavefronts.
+inline int scs_children_bound(const ScsRules& R) {
+  int units[2] = {0, 0}, arrive = 0;
+  for (int u = 0; u < R.n_units; ++u) {
+    units[R.u_player[u] ? 1 : 0] += 1;
+    int a = 0;
+    for (int t = 0; t < R.tiles; ++t) a += R.arrival[u][t] ? 1 : 0;
+    arrive = a > arrive ? a : arrive;
+  }
+  const int per_unit = 7 * (units[0] > units[1] ? units[0] : units[1]), attackers = 6 * (int)R.stacking + 1;
+  const int c = arrive > per_unit ? arrive : per_unit;
+  return c > attackers ? c : attackers;
+}
+
 // A game's own map over a description: terrain [tiles][3] (attack modifier, defense modifier, cost) and the victory
 // points [n_vp[0] + n_vp[1]][2] (row, column), the counts as in the description.  Host (nz_scs_set_maps,
 // nz_scs_search_set_games) and device (scs_draw_kernel) apply maps with this one function.

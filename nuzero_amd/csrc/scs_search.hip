@@ -2181,21 +2181,14 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   {   // what the records must hold, from the game description (the reference has no limits at all):
       //   decisions per game: one placement per unit, then per turn and unit at most ceil(movement / cheapest tile)
       //     steps + 1 "end movement", 1 "end fighting" or 1 target choice, 1 selection as attacker, 1 confirmation
-      //   legal actions per position: the arrival tiles of a unit (placement), 7 per unit of the player to move
-      //     (6 directions + end movement; end fighting + <= 6 adjacent enemy tiles), 6 * stacking + 1 attackers
+      //   legal actions per position: scs_children_bound (scs_dev.hpp)
     const ScsRules& R = h->host_rules;
-    int min_cost = 1 << 30, units[2] = {0, 0}, arrive = 0;
+    int min_cost = 1 << 30;
     for (int t = 0; t < R.tiles; ++t) min_cost = std::min(min_cost, (int)R.cost[t]);
     if (min_cost < 1) { delete h; return sfail(nullptr, NZ_ERR_ARG, "a terrain with movement cost < 1 makes a game's length unbounded"); }
     long long moves = R.n_units;
-    for (int u = 0; u < R.n_units; ++u) {
-      units[R.u_player[u] ? 1 : 0] += 1;
-      moves += (long long)R.turns * ((R.u_mov[u] + min_cost - 1) / min_cost + 4);
-      int a = 0;
-      for (int t = 0; t < R.tiles; ++t) a += R.arrival[u][t] ? 1 : 0;
-      arrive = std::max(arrive, a);
-    }
-    const int children = std::max(std::max(arrive, 7 * std::max(units[0], units[1])), 6 * (int)R.stacking + 1);
+    for (int u = 0; u < R.n_units; ++u) moves += (long long)R.turns * ((R.u_mov[u] + min_cost - 1) / min_cost + 4);
+    const int children = scs_children_bound(R);
     if (children > MAXC_LIMIT) {
       delete h;
       return sfail(nullptr, NZ_ERR_ARG, "this game can have %d legal actions in one position; the search kernels hold %d "

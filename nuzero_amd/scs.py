@@ -383,6 +383,21 @@ class ScsSelfPlay:
     def game_maps(self, maps):
         self._game_maps = maps
 
+    def game_maps_device(self):
+        """`game_maps` as device tensors (terrain float32 [n, tiles, 3], vp int32 [n, k, 2]).  After a device draw they
+        are copied on the device and never visit the host; maps set from the host are uploaded."""
+        if self._game_maps is None and self._draws:
+            c, n = self.cfg, ctypes.c_int64(0)
+            self._check(lib.nz_scs_search_drawn_games(self._h, byref(n), None, None, None, None, self._stream()))
+            t = torch.empty((int(n.value), c.rows * c.cols, 3), dtype=torch.float32, device=self.device)
+            v = torch.empty((int(n.value), len(c.vp), 2), dtype=torch.int32, device=self.device)
+            self._check(lib.nz_scs_search_drawn_games(self._h, None, c_void_p(t.data_ptr()), c_void_p(v.data_ptr()), None,
+                                                      None, self._stream()))
+            return t, v
+        t, v = self.game_maps
+        return (torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(self.device),
+                torch.from_numpy(np.ascontiguousarray(v, np.int32)).to(self.device))
+
     def _drawn(self, maps=False, streams=False):
         """Copies of the last device draw (nz_scs_search_drawn_games): (terrain, vp) and / or (MT19937 keys, positions)."""
         c, n = self.cfg, ctypes.c_int64(0)
