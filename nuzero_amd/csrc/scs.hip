@@ -103,7 +103,7 @@ bool nz::scs_fill_rules(const nz_scs_desc* d, ScsRules* out, std::string* err) {
   memset(&r, 0, sizeof(r));
   const int S = d->stacking;
   r.rows = d->rows; r.cols = d->cols; r.tiles = T; r.turns = d->turns; r.stacking = S; r.n_units = d->n_units;
-  r.planes = 1 + 6 * S + 1 + S + 1 + S + S;                     // SCS_Game.py:147-180
+  r.planes = scs_planes(S);                                     // (<= SCS_MAX_PLANES: S was checked above)
   r.placement_limit = 1;
   r.movement_limit = 1 + 6 * S;
   r.target_limit = r.movement_limit + 1;

@@ -7,35 +7,20 @@
 //   * random agent: the match's MT19937 state stays in HBM between its decisions; agent_act_kernel draws
 //     k = randint(n_legal) (scs_mt.hpp: numpy's legacy masked rejection, n == 1 draws nothing) and takes the k-th set bit
 //     of the legal mask in ascending flat action index.
-// The legal mask, the planes and the step are scs_dev.hpp's.  Every loop is bounded; a rejection cap, a position
-// without a legal action and a game past the records' bound set the match's error word.
+// The legal mask, the planes and the step are scs_dev.hpp's, the legal set and the copies scs_wave.hpp's, the stream in
+// HBM scs_mt.hpp's.  Every loop is bounded; a rejection cap, a position without a legal action and a game past the
+// records' bound set the match's error word.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nuzero_amd.h"
 #include "scs_agents.hpp"
 #include "scs_mt.hpp"
+#include "scs_wave.hpp"
 
 namespace nz {
 namespace {
 
-static_assert(sizeof(ScsRules) % 8 == 0, "rules rows are copied in 8-byte words");
-static_assert(sizeof(ScsState) % 2 == 0, "game states are copied in 2-byte words");
-static_assert(MT_N % 4 == 0, "keys are copied in 16-byte words");
-
-__device__ __forceinline__ void copy_rules(ScsRules* dst, const ScsRules* src, int lane) {
-  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);
-  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
-  for (int i = lane; i < (int)(sizeof(ScsRules) / 8); i += 64) d[i] = s[i];
-}
-__device__ __forceinline__ void copy_state(ScsState* dst, const ScsState* src, int lane) {
-  const uint16_t* s = reinterpret_cast<const uint16_t*>(src);
-  uint16_t* d = reinterpret_cast<uint16_t*>(dst);
-  for (int i = lane; i < (int)(sizeof(ScsState) / 2); i += 64) d[i] = s[i];
-}
-__device__ __forceinline__ const ScsRules* rules_of(const AgentArgs& a, int g) {
-  return a.rules + (a.rules_row ? a.rules_row[g] : 0);
-}
 // the side that decides in this position: agent 1 moves for player index 1
 __device__ __forceinline__ int mover_of(const ScsState& s) { return s.player == 1 ? 0 : 1; }
 
@@ -46,9 +31,7 @@ __global__ __launch_bounds__(64) void agent_seed_kernel(const uint32_t* __restri
   if (g >= n) return;
   mt_seed(key, seeds[g], lane);
   __syncthreads();
-  const uint4* src = reinterpret_cast<const uint4*>(key);
-  uint4* dst = reinterpret_cast<uint4*>(mt_keys + (size_t)g * MT_N);
-  for (int i = lane; i < MT_N / 4; i += 64) dst[i] = src[i];
+  mt_store_keys(mt_keys, g, key, lane);
   if (lane == 0) mt_pos[g] = MT_N;                       // as after RandomState(seed): the first draw twists
 }
 
@@ -77,8 +60,8 @@ __global__ __launch_bounds__(64) void agent_image_kernel(AgentArgs a, int side) 
   if (real.terminal || real.length >= a.max_moves) return;           // (wave-uniform)
   if (mover_of(real) != side) return;
   const AgentSide& me = a.side[side];
-  copy_rules(&R, rules_of(a, g), lane);
-  copy_state(&sc, &real, lane);
+  wave_copy<uint64_t>(&R, rules_of(a.rules, a.rules_row, g), lane);
+  wave_copy<uint16_t>(&sc, &real, lane);
   if (lane == 0) s_slot = atomicAdd(me.count, 1);
   __syncthreads();
   const int slot = s_slot;
@@ -101,7 +84,7 @@ __global__ __launch_bounds__(64) void agent_image_kernel(AgentArgs a, int side) 
 __global__ __launch_bounds__(64) void agent_act_kernel(AgentArgs a) {
   __shared__ __align__(16) ScsRules R;
   __shared__ ScsState sc;
-  __shared__ uint32_t smask[AGENT_MASK_WORDS];
+  __shared__ uint32_t smask[SCS_MASK_WORDS];
   __shared__ __align__(16) uint32_t key[MT_N];
   const int lane = threadIdx.x, g = blockIdx.x;
   if (g >= a.n_games) return;
@@ -115,13 +98,11 @@ __global__ __launch_bounds__(64) void agent_act_kernel(AgentArgs a) {
     if (lane == 0) atomicOr(&a.err[g], AGENT_ERR_LENGTH);
     return;
   }
-  copy_rules(&R, rules_of(a, g), lane);
-  copy_state(&sc, &real, lane);
+  wave_copy<uint64_t>(&R, rules_of(a.rules, a.rules_row, g), lane);
+  wave_copy<uint16_t>(&sc, &real, lane);
   __syncthreads();
-  scs_legal_mask_wave<AGENT_MASK_WORDS>(R, sc, smask, lane);
-  const uint32_t w0 = lane < AGENT_MASK_WORDS ? smask[lane] : 0u;
-  const uint32_t w1 = lane + 64 < AGENT_MASK_WORDS ? smask[lane + 64] : 0u;
-  const int n_legal = __shfl(wave_scan(__popc(w0) + __popc(w1), lane), 63, 64);
+  const WaveLegal legal = wave_legal(R, sc, smask, lane);
+  const int n_legal = legal.count;
   if (n_legal == 0) {
     if (lane == 0) atomicOr(&a.err[g], AGENT_ERR_NO_LEGAL);
     return;
@@ -150,27 +131,12 @@ __global__ __launch_bounds__(64) void agent_act_kernel(AgentArgs a) {
     action = at;
     won = best;
   } else {
-    const uint4* src = reinterpret_cast<const uint4*>(me.mt_keys + (size_t)g * MT_N);
-    uint4* dst = reinterpret_cast<uint4*>(key);
-    for (int i = lane; i < MT_N / 4; i += 64) dst[i] = src[i];
-    __syncthreads();
-    const int pos0 = me.mt_pos[g];
-    Mt m{key, pos0, lane};
-    int k = mt_randint(m, n_legal);
-    __syncthreads();
-    // at most MT_RANDINT_TRIES < 624 words are drawn: the position went down exactly when the state was twisted
-    if (m.pos < pos0) {
-      const uint4* s2 = reinterpret_cast<const uint4*>(key);
-      uint4* d2 = reinterpret_cast<uint4*>(me.mt_keys + (size_t)g * MT_N);
-      for (int i = lane; i < MT_N / 4; i += 64) d2[i] = s2[i];
-    }
-    if (lane == 0) me.mt_pos[g] = m.pos;
+    const int k = mt_stream_randint(key, me.mt_keys, me.mt_pos, g, n_legal, lane);
     if (k < 0) {
       if (lane == 0) atomicOr(&a.err[g], AGENT_ERR_CAP);
       return;
     }
-    action = kth_set_bit(w0, 0, k, lane);
-    if (action < 0) action = kth_set_bit(w1, 64, k, lane);
+    action = legal.kth(k, lane);
   }
   if (action < 0 || action >= A) {                                    // (cannot happen: k < n_legal, the mask has n_legal bits)
     if (lane == 0) atomicOr(&a.err[g], AGENT_ERR_NO_LEGAL);
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(64) void agent_act_kernel(AgentArgs a) {
     // no engine searches: the games step here, and the handle's tree stays the unexpanded root of its reset -- the
     // right tree for whatever position the game is in
     scs_step_wave<true>(R, sc, action, lane);
-    copy_state(&a.real[g], &sc, lane);
+    wave_copy<uint16_t>(&a.real[g], &sc, lane);
     if (lane == 0) a.rec_action[gm] = action;
   }
 }

@@ -9,38 +9,9 @@
 
 namespace nz {
 
-constexpr int AGENT_MAX_PLANES = 3 + 9 * SCS_MAX_STACK;       // 1 + 6 S + 1 + S + 1 + S + S action planes (scs_fill_rules)
-constexpr int AGENT_MASK_WORDS = (AGENT_MAX_PLANES * SCS_MAX_TILES + 31) / 32;
-static_assert(AGENT_MASK_WORDS <= 128, "a lane holds two words of the legal mask");
-
 // per-match error word: the randint rejection cap was reached; a live position without a legal action; a game longer
 // than the records' bound
 enum : int32_t { AGENT_ERR_CAP = 1, AGENT_ERR_NO_LEGAL = 2, AGENT_ERR_LENGTH = 4 };
-
-// inclusive prefix sum over the wavefront
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// The index of the k-th set bit (k < the number of set bits) of the mask whose words `base + lane` the lanes hold in w,
-// or -1 when it lies past these 64 words (k is then reduced by their count): ballot and popcount prefix.
-__device__ __forceinline__ int kth_set_bit(uint32_t w, int base, int& k, int lane) {
-  const int c = __popc(w), inc = wave_scan(c, lane);
-  const int total = __shfl(inc, 63, 64);
-  if (k >= total) { k -= total; return -1; }
-  const int owner = __ffsll((long long)__ballot(inc > k)) - 1;       // the first lane whose words reach past k
-  int bit = -1;
-  if (lane == owner) {
-    uint32_t x = w;
-    for (int i = k - (inc - c); i > 0; --i) x &= x - 1;               // (at most 31 rounds)
-    bit = (base + lane) * 32 + __ffs((int)x) - 1;
-  }
-  return __shfl(bit, owner, 64);
-}
 
 struct AgentSide {
   int32_t kind;                  // NZ_AGENT_*

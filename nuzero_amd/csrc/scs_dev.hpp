@@ -26,6 +26,10 @@ constexpr int SCS_MAX_TILES = 100;    // 10 x 10
 constexpr int SCS_MAX_STACK = 3;
 constexpr int SCS_MAX_UNITS = 32;
 constexpr int SCS_MAX_TURNS = 16;
+// action planes at stacking limit S (SCS_Game.py:147-180); scs_fill_rules refuses S > SCS_MAX_STACK, so no rules row
+// has more than SCS_MAX_PLANES
+constexpr int scs_planes(int S) { return 1 + 6 * S + 1 + S + 1 + S + S; }
+constexpr int SCS_MAX_PLANES = scs_planes(SCS_MAX_STACK);
 
 // unit status: queued (not yet placed), the reference's 0/1/2, destroyed
 enum : int8_t { SCS_QUEUED = -1, SCS_AVAILABLE = 0, SCS_MOVED = 1, SCS_ATTACKED = 2, SCS_DEAD = 3 };

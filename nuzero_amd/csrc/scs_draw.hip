@@ -16,8 +16,8 @@
 #include <stdint.h>
 
 #include "../../include/nuzero_amd.h"
-#include "scs_dev.hpp"
 #include "scs_mt.hpp"
+#include "scs_wave.hpp"
 
 namespace nz {
 namespace {
@@ -40,11 +40,7 @@ __global__ __launch_bounds__(64) void scs_draw_kernel(ScsDrawSpec sp, const ScsR
   if (g >= n) return;
 
   // the engine's template row; init_genrand (a serial recurrence: one lane)
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(tmpl);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&row);
-    for (int i = lane; i < (int)(sizeof(ScsRules) / 8); i += 64) dst[i] = src[i];
-  }
+  wave_copy<uint64_t>(&row, tmpl, lane);
   mt_seed(key, seeds[g], lane);
   __syncthreads();
   // the template's map: what the sections the config gives in "Detailed" form stay
@@ -107,22 +103,11 @@ __global__ __launch_bounds__(64) void scs_draw_kernel(ScsDrawSpec sp, const ScsR
   }
   __syncthreads();
 
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(&row);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(rows + g);
-    for (int i = lane; i < (int)(sizeof(ScsRules) / 8); i += 64) dst[i] = src[i];
-  }
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(key);
-    uint4* dst = reinterpret_cast<uint4*>(mt_keys + (size_t)g * MT_N);
-    for (int i = lane; i < MT_N / 4; i += 64) dst[i] = src[i];
-  }
+  wave_copy<uint64_t>(rows + g, &row, lane);
+  mt_store_keys(mt_keys, g, key, lane);
   for (int i = lane; i < T * 3; i += 64) terrain_out[(size_t)g * T * 3 + i] = terr[i];
   for (int i = lane; i < nv * 2; i += 64) vp_out[(size_t)g * nv * 2 + i] = vp[i];
 }
-
-static_assert(sizeof(ScsRules) % 8 == 0, "rules rows are copied in 8-byte words");
-static_assert(MT_N % 4 == 0, "keys are copied in 16-byte words");
 
 }  // namespace
 

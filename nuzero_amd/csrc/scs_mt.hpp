@@ -83,8 +83,39 @@ __device__ inline int mt_randint(Mt& m, int n) {
   return -1;
 }
 
-// Streams kept in HBM between a random agent's decisions (scs_agents.hip, ttt_agents.hip): keys [n][624] / pos [n] of
-// match g = RandomState(seeds[g]) (pos = 624: the first draw twists).  Defined in scs_agents.hip.
+// ---- streams kept in HBM (mt_keys [n][624], mt_pos [n]) between a wavefront's visits ---------------------------------
+// One stream's keys between HBM and the wavefront's LDS copy (key [624], 16-byte aligned as the rows of mt_keys are).
+static_assert(MT_N % 4 == 0, "keys are copied in 16-byte words");
+__device__ __forceinline__ void mt_copy_keys(uint32_t* dst, const uint32_t* src, int lane) {
+  const uint4* s = reinterpret_cast<const uint4*>(src);
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  for (int i = lane; i < MT_N / 4; i += 64) d[i] = s[i];
+}
+__device__ __forceinline__ void mt_load_keys(uint32_t* key, const uint32_t* mt_keys, int64_t g, int lane) {
+  mt_copy_keys(key, mt_keys + (size_t)g * MT_N, lane);
+}
+__device__ __forceinline__ void mt_store_keys(uint32_t* mt_keys, int64_t g, const uint32_t* key, int lane) {
+  mt_copy_keys(mt_keys + (size_t)g * MT_N, key, lane);
+}
+
+// randint(0, n) on stream g, through the LDS copy `key`: the keys go back only if the draw twisted them, the position
+// always.  -1 as mt_randint.  The wavefront meets after the load and after the draw.  (Inlined by force: left to the
+// compiler it became a real call in agent_act_kernel, with the registers and hidden kernel arguments a call brings.)
+__device__ __forceinline__ int mt_stream_randint(uint32_t* key, uint32_t* mt_keys, int32_t* mt_pos, int64_t g, int n, int lane) {
+  mt_load_keys(key, mt_keys, g, lane);
+  __syncthreads();
+  const int pos0 = mt_pos[g];
+  Mt m{key, pos0, lane};
+  const int k = mt_randint(m, n);
+  __syncthreads();
+  // at most MT_RANDINT_TRIES < 624 words are drawn: the position went down exactly when the state was twisted
+  if (m.pos < pos0) mt_store_keys(mt_keys, g, key, lane);
+  if (lane == 0) mt_pos[g] = m.pos;
+  return k;
+}
+
+// The random agents' streams (scs_agents.hip, ttt_agents.hip): match g = RandomState(seeds[g]) (pos = 624: the first
+// draw twists).  Defined in scs_agents.hip.
 hipError_t agent_seed_launch(const uint32_t* seeds, uint32_t* mt_keys, int32_t* mt_pos, int n, hipStream_t stream);
 
 }  // namespace nz

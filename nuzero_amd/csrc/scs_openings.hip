@@ -1,7 +1,7 @@
 // Evaluation matches from opening positions (nz_scs_search_reset_to, nz_scs_openings_draw, nz_scs_openings_expand;
 // DESIGN.md section 5b).  Evaluation agents are deterministic, so the matches of a round on one map are copies of one
 // game unless they start at different positions.  Three kernels, one wavefront per match or prefix, the rules row and the
-// game in LDS as in agent_act_kernel:
+// game in LDS (scs_wave.hpp):
 //   * apply: after the slot's reset, replay the match's prefix through the legal mask and the step; the tree stays the
 //     unexpanded root (MctsAgent.new_game, then choose_action, on a game stepped to the position);
 //   * draw: the random agent's rule from the start, on the stream RandomState(opening_seeds[g]);
@@ -15,53 +15,27 @@
 #include <stdint.h>
 
 #include "../../include/nuzero_amd.h"
-#include "scs_agents.hpp"
 #include "scs_mt.hpp"
 #include "scs_openings.hpp"
+#include "scs_wave.hpp"
 
 namespace nz {
 namespace {
-
-static_assert(sizeof(ScsRules) % 8 == 0, "rules rows are copied in 8-byte words");
-static_assert(sizeof(ScsState) % 2 == 0, "game states are copied in 2-byte words");
-
-__device__ __forceinline__ void copy_rules(ScsRules* dst, const ScsRules* src, int lane) {
-  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);
-  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
-  for (int i = lane; i < (int)(sizeof(ScsRules) / 8); i += 64) d[i] = s[i];
-}
-__device__ __forceinline__ void copy_state(ScsState* dst, const ScsState* src, int lane) {
-  const uint16_t* s = reinterpret_cast<const uint16_t*>(src);
-  uint16_t* d = reinterpret_cast<uint16_t*>(dst);
-  for (int i = lane; i < (int)(sizeof(ScsState) / 2); i += 64) d[i] = s[i];
-}
-__device__ __forceinline__ const ScsRules* rules_of(const OpeningGames& og, int g) {
-  return og.rules + (og.rules_row ? og.rules_row[g] : 0);
-}
 
 // Replays acts[0 .. n) on the game `sc` (LDS): 0, or the error word of the first violation, at which `sc` stays where the
 // sound part of the prefix left it.  Wave-uniform: every lane returns the same word.
 __device__ __forceinline__ int32_t replay_prefix(const ScsRules& R, ScsState& sc, uint32_t* smask, const int32_t* acts, int n,
                                                  int num_actions, int max_moves, int lane) {
   for (int ply = 0; ply < n; ++ply) {
-    if (sc.terminal) return (ply << 8) | OPENING_ERR_GAME_OVER;
-    if (sc.length >= max_moves) return (ply << 8) | OPENING_ERR_LENGTH;
     const int a = acts[ply];
-    if (a < 0 || a >= num_actions) return (ply << 8) | OPENING_ERR_ILLEGAL;
-    scs_legal_mask_wave<AGENT_MASK_WORDS>(R, sc, smask, lane);
-    if (!((smask[a >> 5] >> (a & 31)) & 1u)) return (ply << 8) | OPENING_ERR_ILLEGAL;
+    const int refused = scs_admit_wave(R, sc, smask, a, num_actions, lane);
+    // the records' bound is reported behind a game that is over and ahead of what is wrong with the action itself
+    if (refused == SCS_ADMIT_GAME_OVER) return (ply << 8) | OPENING_ERR_GAME_OVER;
+    if (sc.length >= max_moves) return (ply << 8) | OPENING_ERR_LENGTH;
+    if (refused) return (ply << 8) | OPENING_ERR_ILLEGAL;
     scs_step_wave<true>(R, sc, a, lane);
   }
   return 0;
-}
-
-// the legal actions of `sc`'s position: the mask in smask, the lanes' two words each, their count
-__device__ __forceinline__ int legal_count(const ScsRules& R, const ScsState& sc, uint32_t* smask, int lane, uint32_t& w0,
-                                           uint32_t& w1) {
-  scs_legal_mask_wave<AGENT_MASK_WORDS>(R, sc, smask, lane);
-  w0 = lane < AGENT_MASK_WORDS ? smask[lane] : 0u;
-  w1 = lane + 64 < AGENT_MASK_WORDS ? smask[lane + 64] : 0u;
-  return __shfl(wave_scan(__popc(w0) + __popc(w1), lane), 63, 64);
 }
 
 __global__ __launch_bounds__(64) void opening_apply_kernel(OpeningGames og, int n, const int32_t* __restrict__ actions,
@@ -70,11 +44,11 @@ __global__ __launch_bounds__(64) void opening_apply_kernel(OpeningGames og, int 
                                                            int32_t* __restrict__ err) {
   __shared__ __align__(16) ScsRules R;
   __shared__ ScsState sc;
-  __shared__ uint32_t smask[AGENT_MASK_WORDS];
+  __shared__ uint32_t smask[SCS_MASK_WORDS];
   const int lane = threadIdx.x, g = blockIdx.x;
   if (g >= n) return;
-  copy_rules(&R, rules_of(og, g), lane);
-  copy_state(&sc, &real[g], lane);
+  wave_copy<uint64_t>(&R, rules_of(og.rules, og.rules_row, g), lane);
+  wave_copy<uint16_t>(&sc, &real[g], lane);
   __syncthreads();
   int np = n_plies ? n_plies[g] : max_plies;
   np = np < 0 ? 0 : np > max_plies ? max_plies : np;                  // (the host refused anything else)
@@ -84,7 +58,7 @@ __global__ __launch_bounds__(64) void opening_apply_kernel(OpeningGames og, int 
   if (!e && first + np > max_moves) e = (np << 8) | OPENING_ERR_LENGTH;
   if (lane == 0) err[g] = e;
   if (e) return;                                                      // (wave-uniform) the match stays at its reset state
-  copy_state(&real[g], &sc, lane);
+  wave_copy<uint16_t>(&real[g], &sc, lane);
   // records stay indexed by the game's decision number; rec_children / rec_tree_size stay 0: nobody searched these plies
   for (int ply = lane; ply < np; ply += 64) rec_action[(size_t)g * max_moves + first + ply] = mine[ply];
 }
@@ -94,11 +68,11 @@ __global__ __launch_bounds__(64) void opening_draw_kernel(OpeningGames og, int n
                                                           int32_t* __restrict__ err) {
   __shared__ __align__(16) ScsRules R;
   __shared__ ScsState sc;
-  __shared__ uint32_t smask[AGENT_MASK_WORDS];
+  __shared__ uint32_t smask[SCS_MASK_WORDS];
   __shared__ __align__(16) uint32_t key[MT_N];
   const int lane = threadIdx.x, g = blockIdx.x;
   if (g >= n) return;
-  copy_rules(&R, rules_of(og, g), lane);
+  wave_copy<uint64_t>(&R, rules_of(og.rules, og.rules_row, g), lane);
   mt_seed(key, seeds[g], lane);
   __syncthreads();
   if (lane == 0) Scs(R, sc).reset();
@@ -108,13 +82,12 @@ __global__ __launch_bounds__(64) void opening_draw_kernel(OpeningGames og, int n
   int ply = 0;
   for (; ply < plies; ++ply) {
     if (sc.terminal) break;                                           // (wave-uniform, as every exit below)
-    uint32_t w0, w1;
-    const int n_legal = legal_count(R, sc, smask, lane, w0, w1);
+    const WaveLegal legal = wave_legal(R, sc, smask, lane);
+    const int n_legal = legal.count;
     if (n_legal == 0) { e = (ply << 8) | OPENING_ERR_NO_LEGAL; break; }
-    int k = mt_randint(m, n_legal);
+    const int k = mt_randint(m, n_legal);
     if (k < 0) { e = (ply << 8) | OPENING_ERR_CAP; break; }
-    int action = kth_set_bit(w0, 0, k, lane);
-    if (action < 0) action = kth_set_bit(w1, 64, k, lane);
+    const int action = legal.kth(k, lane);
     if (action < 0 || action >= og.num_actions) { e = (ply << 8) | OPENING_ERR_NO_LEGAL; break; }   // (cannot happen: k < n_legal)
     if (lane == 0) actions_out[(size_t)g * plies + ply] = action;
     scs_step_wave<true>(R, sc, action, lane);
@@ -133,10 +106,10 @@ __global__ __launch_bounds__(64) void opening_expand_kernel(OpeningGames og, int
                                                             float* __restrict__ planes, int32_t* __restrict__ err) {
   __shared__ __align__(16) ScsRules R;
   __shared__ ScsState sc, child;
-  __shared__ uint32_t smask[AGENT_MASK_WORDS];
+  __shared__ uint32_t smask[SCS_MASK_WORDS];
   const int lane = threadIdx.x, f = blockIdx.x;
   if (f >= n) return;
-  copy_rules(&R, rules_of(og, f), lane);
+  wave_copy<uint64_t>(&R, rules_of(og.rules, og.rules_row, f), lane);
   __syncthreads();
   if (lane == 0) Scs(R, sc).reset();
   __syncthreads();
@@ -144,10 +117,8 @@ __global__ __launch_bounds__(64) void opening_expand_kernel(OpeningGames og, int
   const int32_t e = replay_prefix(R, sc, smask, mine, depth, og.num_actions, max_moves, lane);
   if (lane == 0) err[f] = e;
   int n_legal = 0;
-  if (!e && !sc.terminal && sc.length < max_moves) {                  // a terminal prefix has no children
-    uint32_t w0, w1;
-    n_legal = legal_count(R, sc, smask, lane, w0, w1);
-  }
+  if (!e && !sc.terminal && sc.length < max_moves)                    // a terminal prefix has no children
+    n_legal = wave_legal(R, sc, smask, lane).count;
   if (!children) {
     if (lane == 0) counts[f] = n_legal;
     return;
@@ -158,12 +129,12 @@ __global__ __launch_bounds__(64) void opening_expand_kernel(OpeningGames og, int
   float* const img = planes + (size_t)f * R.channels * R.tiles;       // this wavefront's own [channels][tiles]
   const int tiles = R.tiles;
   int j = 0;
-  for (int w = 0; w < AGENT_MASK_WORDS && j < room; ++w) {
+  for (int w = 0; w < SCS_MASK_WORDS && j < room; ++w) {
     uint32_t bits = smask[w];
     while (bits && j < room) {                                        // (at most 32 rounds, ascending)
       const int a = w * 32 + __ffs((int)bits) - 1;
       bits &= bits - 1;
-      copy_state(&child, &sc, lane);
+      wave_copy<uint16_t>(&child, &sc, lane);
       __syncthreads();
       scs_step_wave<true>(R, child, a, lane);
       // the digest of the planes just written, read back behind a fence (this wavefront's own stores)

@@ -16,7 +16,7 @@
 //
 // Which slot a position takes and which slots a batch reads is decided on the host (nuzero_amd/replay_device.py
 // ReplayIndex, unchanged); the kernels below replay the recorded actions of a finished round through the device rules
-// (scs_dev.hpp: scs_legal_mask_wave, scs_step_wave), one wavefront per game, and render batch rows
+// (scs_wave.hpp: scs_admit_wave, scs_dev.hpp: scs_step_wave), one wavefront per game, and render batch rows
 // (scs_state_image_wave), one wavefront per row.  Policy targets are formed exactly as replay.hip's append_kernel
 // forms them: (float)((double)visit / (double)sum of visits), 0 for a zero visit count.
 #include <hip/hip_runtime.h>
@@ -29,13 +29,12 @@
 
 #include "../../include/nuzero_amd.h"
 #include "hip_own.hpp"
-#include "scs_dev.hpp"
+#include "scs_wave.hpp"
 
 using namespace nz;
 
 namespace {
 constexpr int NDESC = 16;                                      // game descriptions per buffer (game_index 0 .. 15)
-constexpr int RP_MASK_WORDS = (30 * SCS_MAX_TILES + 31) / 32;  // stacking 3: 30 action planes
 
 struct RecLayout {                                             // byte offsets inside a record (all multiples of 4)
   int32_t terrain, children, state, vp, bytes;
@@ -49,7 +48,8 @@ RecLayout rec_layout(int tiles, int max_children) {
   l.bytes = (l.vp + 2 * tiles + 3) & ~3;
   return l;
 }
-static_assert(sizeof(ScsState) % 4 == 0 && sizeof(ScsRules) % 4 == 0, "records and rules rows are copied word by word");
+// A record is 4-byte aligned and no more (its size is any multiple of 4), so whatever goes into or comes out of one is
+// copied in 4-byte words (wave_copy<uint32_t>), and the LDS state at the other end is declared that wide.
 }  // namespace
 
 struct nz_scs_replay {
@@ -115,14 +115,10 @@ struct ReplayArgs {
 template <bool SAVE>
 __global__ __launch_bounds__(64) void scs_replay_kernel(ReplayArgs a) {
   __shared__ ScsRules R;
-  __shared__ ScsState S;
-  __shared__ uint32_t mask[RP_MASK_WORDS];
+  __shared__ __align__(4) ScsState S;
+  __shared__ uint32_t mask[SCS_MASK_WORDS];
   const int g = blockIdx.x, lane = threadIdx.x;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.desc);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&R);
-    for (int i = lane; i < (int)(sizeof(ScsRules) / 4); i += 64) dst[i] = src[i];
-  }
+  wave_copy<uint32_t>(&R, a.desc, lane);
   __syncthreads();
   if (lane == 0) {
     if (a.terrain != nullptr)
@@ -139,20 +135,18 @@ __global__ __launch_bounds__(64) void scs_replay_kernel(ReplayArgs a) {
   const int len = a.lengths[g];
   if (len < 0 || len > a.max_moves) { bad(0, BAD_LENGTH); return; }
   for (int m = 0; m < len; ++m) {
-    if (S.terminal) { bad(m, BAD_ENDED); return; }            // (the state is wave-uniform: every lane reads the same LDS)
     const int act = __builtin_amdgcn_readfirstlane(a.actions[(size_t)g * a.max_moves + m]);
-    if (act < 0 || act >= A) { bad(m, BAD_RANGE); return; }
-    scs_legal_mask_wave<RP_MASK_WORDS>(R, S, mask, lane);
-    if (!((mask[act >> 5] >> (act & 31)) & 1u)) { bad(m, BAD_ILLEGAL); return; }
+    if (const int refused = scs_admit_wave(R, S, mask, act, A, lane)) {   // (wave-uniform: the state is the same LDS for every lane)
+      bad(m, refused == SCS_ADMIT_GAME_OVER ? BAD_ENDED : refused == SCS_ADMIT_RANGE ? BAD_RANGE : BAD_ILLEGAL);
+      return;
+    }
     if constexpr (SAVE) {
       const int64_t slot = m < a.dst_stride ? a.dst_slot[(size_t)g * a.dst_stride + m] : -1;
       if (slot >= a.capacity) {
         if (lane == 0) atomicOr(a.error_flag, FLAG_SLOT);
       } else if (slot >= 0) {
         unsigned char* rec = a.records + (size_t)slot * a.lay.bytes;
-        uint32_t* st = reinterpret_cast<uint32_t*>(rec + a.lay.state);
-        const uint32_t* ss = reinterpret_cast<const uint32_t*>(&S);
-        for (int i = lane; i < (int)(sizeof(ScsState) / 4); i += 64) st[i] = ss[i];
+        wave_copy<uint32_t>(reinterpret_cast<ScsState*>(rec + a.lay.state), &S, lane);
         float* tr = reinterpret_cast<float*>(rec + a.lay.terrain);
         for (int i = lane; i < 3 * T; i += 64) tr[i] = (&R.terrain_f[0][0])[i];
         int8_t* v = reinterpret_cast<int8_t*>(rec + a.lay.vp);
@@ -211,7 +205,7 @@ struct GatherArgs {
 // and the image is rendered straight into the batch tensor.
 __global__ __launch_bounds__(64) void scs_gather_kernel(GatherArgs a) {
   __shared__ ScsRules R;
-  __shared__ ScsState S;
+  __shared__ __align__(4) ScsState S;
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x;
   const int64_t slot = a.slots[b];
@@ -231,12 +225,8 @@ __global__ __launch_bounds__(64) void scs_gather_kernel(GatherArgs a) {
   if (a.out_states != nullptr) {
     // the rules row of this position: the description, with the record's map over terrain_f and vp (all the image reads
     // of a map; attack_mod / defense_mod / cost are the rules' and stay the description's)
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(D);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&R);
-    for (int i = lane; i < (int)(sizeof(ScsRules) / 4); i += 64) dst[i] = src[i];
-    const uint32_t* ss = reinterpret_cast<const uint32_t*>(rec + a.lay.state);
-    uint32_t* sd = reinterpret_cast<uint32_t*>(&S);
-    for (int i = lane; i < (int)(sizeof(ScsState) / 4); i += 64) sd[i] = ss[i];
+    wave_copy<uint32_t>(&R, D, lane);
+    wave_copy<uint32_t>(&S, reinterpret_cast<const ScsState*>(rec + a.lay.state), lane);
     __syncthreads();
     const float* tr = reinterpret_cast<const float*>(rec + a.lay.terrain);
     for (int i = lane; i < 3 * T; i += 64) (&R.terrain_f[0][0])[i] = tr[i];

@@ -2167,6 +2167,7 @@ nz_status nz_scs_search_create(nz_scs_search** out, const nz_scs_desc* d, const 
   h->n_games = n_games;
   h->cfg = *cfg;
   std::string err;
+  // (a description it accepts has at most SCS_MAX_PLANES action planes: what the side kernels' legal masks hold, scs_wave.hpp)
   if (!scs_fill_rules(d, &h->host_rules, &err)) { delete h; return sfail(nullptr, NZ_ERR_ARG, "%s", err.c_str()); }
   if (h->host_rules.planes * h->host_rules.tiles > MAX_ACTIONS) { delete h; return sfail(nullptr, NZ_ERR_ARG, "too many actions"); }
   (void)hipSetDevice(device);
@@ -2468,18 +2469,28 @@ struct PlayRoute {
   int32_t row_stride = 0;
 };
 
+// The network fits the handle's game and holds a position of each of its games; its input rows.  agent = 1 / 2: the
+// network of a scripted side of an agent match (the message says whose), 0: the searching network.
+nz_status net_fits(nz_scs_search* h, nz_boardnet* net, int agent, float** net_rows, int32_t* row_stride) {
+  const ScsRules& R = h->host_rules;
+  char who[16] = "";
+  if (agent) snprintf(who, sizeof(who), "agent %d: ", agent);
+  int32_t nin = 0, npol = 0, nrows = 0, ncols = 0, nmax = 0;
+  if (nz_boardnet_dims(net, &nin, &npol, &nrows, &ncols, &nmax) != NZ_OK) return sfail(h, NZ_ERR_ARG, "%sbad network handle", who);
+  if (nin != R.channels || npol != R.planes || nrows != R.rows || ncols != R.cols)
+    return sfail(h, NZ_ERR_ARG, "%snetwork is %d planes -> %d planes on %dx%d, the game needs %d -> %d on %dx%d", who, nin, npol,
+                 nrows, ncols, R.channels, R.planes, R.rows, R.cols);
+  if (nmax < h->n_games) return sfail(h, NZ_ERR_ARG, "%snetwork max_batch %d < %d %s", who, nmax, h->n_games, agent ? "matches" : "games");
+  if (nz_boardnet_input_rows(net, net_rows, row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "%sbad network handle", who);
+  return NZ_OK;
+}
+
 nz_status play_prepare(nz_scs_search* h, nz_boardnet* net, PlayRoute* route, void* stream) {
   const int G = h->n_games;
   const int MAXC = h->p.maxc;
   const ScsRules& R = h->host_rules;
   const int A = R.planes * R.tiles;
-  int32_t nin = 0, npol = 0, nrows = 0, ncols = 0, nmax = 0;
-  if (nz_boardnet_dims(net, &nin, &npol, &nrows, &ncols, &nmax) != NZ_OK) return sfail(h, NZ_ERR_ARG, "bad network handle");
-  if (nin != R.channels || npol != R.planes || nrows != R.rows || ncols != R.cols)
-    return sfail(h, NZ_ERR_ARG, "network is %d planes -> %d planes on %dx%d, the game needs %d -> %d on %dx%d", nin, npol,
-                 nrows, ncols, R.channels, R.planes, R.rows, R.cols);
-  if (nmax < G) return sfail(h, NZ_ERR_ARG, "network max_batch %d < %d games", nmax, G);
-  if (nz_boardnet_input_rows(net, &route->net_rows, &route->row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "bad network handle");
+  if (nz_status st = net_fits(h, net, 0, &route->net_rows, &route->row_stride)) return st;
   const bool bufs = h->play.ensure((size_t)G, (size_t)A, (size_t)MAXC);
   h->play.bind(h->p);
   if (!bufs) return sfail(h, NZ_ERR_HIP, "device allocation failed");
@@ -2856,11 +2867,18 @@ void clear_games(nz_scs_search* h) {
   h->rows.bind(h->p, h->made.rules.get(), false);
 }
 
-// The rows are in place: slot g plays row g, the plays read the per-game rows and digests.
-nz_status use_game_rows(nz_scs_search* h, int64_t n, void* stream) {
+// Slot g reads row g of the per-game rows (a refilled round leaves the slots on later rows).  A copy that waits: a
+// caller whose stream may still read the rows waits for that stream first.
+nz_status slots_read_own_rows(nz_scs_search* h) {
   std::vector<int32_t> ident(h->n_games);
   for (int g = 0; g < h->n_games; ++g) ident[g] = g;
   S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return NZ_OK;
+}
+
+// The rows are in place: slot g plays row g, the plays read the per-game rows and digests.
+nz_status use_game_rows(nz_scs_search* h, int64_t n, void* stream) {
+  if (nz_status st = slots_read_own_rows(h)) return st;
   h->n_game_rows = n;
   h->rows.bind(h->p, h->made.rules.get(), true);
   return nz_scs_search_reset(h, stream);       // the slots' games start on their own maps (row g for slot g)
@@ -3252,6 +3270,28 @@ __global__ void match_tally_kernel(MatchSide a, MatchSide b, int n, int max_move
     if (bad) atomicAdd(&tally[7], 1ull);
   }
 }
+
+// The tally of h's round against `record` (with `other` the second engine's side, or none), read out into out_host, and
+// the record copied to actions_dev; either may be null.  Refused matches fail with `refused` (one %lld: how many).
+nz_status tally_result(nz_scs_search* h, int64_t* tally, const MatchSide& other, const int32_t* record, const char* refused,
+                       nz_scs_match_tally* out_host, int32_t* actions_dev, hipStream_t s) {
+  const int G = h->n_games, MAX_MOVES = h->p.max_moves;
+  S_HIP(h, hipMemsetAsync(tally, 0, 8 * sizeof(int64_t), s));
+  hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(h->p), other, G, MAX_MOVES, record,
+                     (unsigned long long*)tally);
+  S_HIP(h, hipGetLastError());
+  int64_t t[8];
+  S_HIP(h, hipMemcpyAsync(t, tally, sizeof(t), hipMemcpyDeviceToHost, s));
+  if (actions_dev)
+    S_HIP(h, hipMemcpyAsync(actions_dev, record, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  S_HIP(h, hipStreamSynchronize(s));
+  if (t[7] != 0) return sfail(h, NZ_ERR_STATE, refused, (long long)t[7]);
+  if (out_host) {
+    out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
+    out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
+  }
+  return NZ_OK;
+}
 }  // namespace
 
 extern "C" nz_status nz_scs_match_play(nz_scs_search* a1, nz_boardnet* net1, nz_scs_search* a2, nz_boardnet* net2,
@@ -3276,11 +3316,14 @@ extern "C" nz_status nz_scs_match_play_from(nz_scs_search* a1, nz_boardnet* net1
   const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
   if (a1->n_game_rows != a2->n_game_rows)
     return sfail(a1, NZ_ERR_ARG, "per-game maps: %lld set on agent 1, %lld on agent 2", (long long)a1->n_game_rows, (long long)a2->n_game_rows);
-  if (a1->n_game_rows > 0) {                   // every match on its own map: the same one in both engines
+  // agent 2's failures are reported on agent 1's handle, the one the caller asks
+  auto on2 = [&](nz_status st) {
+    if (st != NZ_OK) a1->error = "agent 2: " + a2->error;
+    return st;
+  };
+  if (a1->n_game_rows > 0) {                  // every match on its own map: the same one in both engines
     if (a1->n_game_rows < G) return sfail(a1, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)a1->n_game_rows);
     std::vector<uint64_t> k1((size_t)G * 2), k2((size_t)G * 2);
-    std::vector<int32_t> ident(G);
-    for (int g = 0; g < G; ++g) ident[g] = g;
     S_HIP(a1, hipStreamSynchronize(s1));
     S_HIP(a1, hipMemcpy(k1.data(), a1->rows.key.get(), k1.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     S_HIP(a1, hipMemcpy(k2.data(), a2->rows.key.get(), k2.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -3289,14 +3332,9 @@ extern "C" nz_status nz_scs_match_play_from(nz_scs_search* a1, nz_boardnet* net1
         return sfail(a1, NZ_ERR_ARG, "match %d: the two engines hold different maps (digests %016llx%016llx and %016llx%016llx)", g,
                      (unsigned long long)k1[(size_t)g * 2], (unsigned long long)k1[(size_t)g * 2 + 1],
                      (unsigned long long)k2[(size_t)g * 2], (unsigned long long)k2[(size_t)g * 2 + 1]);
-    S_HIP(a1, hipMemcpy(a1->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
-    S_HIP(a1, hipMemcpy(a2->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nz_status st = slots_read_own_rows(a1)) return st;
+    if (nz_status st = on2(slots_read_own_rows(a2))) return st;
   }
-  // agent 2's failures are reported on agent 1's handle, the one the caller asks
-  auto on2 = [&](nz_status st) {
-    if (st != NZ_OK) a1->error = "agent 2: " + a2->error;
-    return st;
-  };
   PlayRoute r1, r2;
   if (nz_status st = play_prepare(a1, net1, &r1, stream)) return st;
   if (nz_status st = on2(play_prepare(a2, net2, &r2, stream))) return st;
@@ -3385,24 +3423,9 @@ extern "C" nz_status nz_scs_match_result(nz_scs_search* a1, nz_scs_search* a2, n
   if (!a1 || !a2) return sfail(a1, NZ_ERR_ARG, "null argument");
   if (a1->match_peer != a2) return sfail(a1, NZ_ERR_STATE, "no match round was played on these two handles");
   S_HIP(a1, hipSetDevice(a1->device));
-  hipStream_t s = (hipStream_t)stream;
-  const int G = a1->n_games, MAX_MOVES = a1->p.max_moves;
-  S_HIP(a1, hipMemsetAsync(a1->match.tally.get(), 0, 8 * sizeof(int64_t), s));
-  hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(a1->p), match_side(a2->p), G, MAX_MOVES,
-                     (const int32_t*)a1->match.actions.get(), (unsigned long long*)a1->match.tally.get());
-  S_HIP(a1, hipGetLastError());
-  int64_t t[8];
-  S_HIP(a1, hipMemcpyAsync(t, a1->match.tally.get(), sizeof(t), hipMemcpyDeviceToHost, s));
-  if (actions_dev)
-    S_HIP(a1, hipMemcpyAsync(actions_dev, a1->match.actions.get(), (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  S_HIP(a1, hipStreamSynchronize(s));
-  if (t[7] != 0)
-    return sfail(a1, NZ_ERR_STATE, "internal: in %lld matches the two engines' records and the match record disagree", (long long)t[7]);
-  if (out_host) {
-    out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
-    out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
-  }
-  return NZ_OK;
+  return tally_result(a1, a1->match.tally.get(), match_side(a2->p), a1->match.actions.get(),
+                      "internal: in %lld matches the two engines' records and the match record disagree", out_host, actions_dev,
+                      (hipStream_t)stream);
 }
 
 // ---- evaluation matches against scripted agents (nz_scs_agent_match_play) ----------------------------------------------
@@ -3453,13 +3476,10 @@ extern "C" nz_status nz_scs_agent_match_play_from(nz_scs_search* h, const nz_scs
   const int G = h->n_games, MAX_MOVES = h->p.max_moves;
   const ScsRules& R = h->host_rules;
   const size_t A = (size_t)R.planes * R.tiles, GM = (size_t)G * MAX_MOVES;
-  if (R.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", R.planes);
   if (h->n_game_rows > 0) {                    // every match on its own map
     if (h->n_game_rows < G) return sfail(h, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)h->n_game_rows);
-    std::vector<int32_t> ident(G);
-    for (int g = 0; g < G; ++g) ident[g] = g;
     S_HIP(h, hipStreamSynchronize(s));
-    S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nz_status st = slots_read_own_rows(h)) return st;
   }
   AgentBufs& b = h->agents;
   const int kinds[2] = {p1->kind, p2->kind};
@@ -3476,15 +3496,8 @@ extern "C" nz_status nz_scs_agent_match_play_from(nz_scs_search* h, const nz_scs
   for (int i = 0; i < 2; ++i) {
     AgentSide& sd = a.side[i];
     sd.kind = ag[i]->kind;
-    if (sd.kind == NZ_AGENT_POLICY) {          // the network fits the game and holds every match's position
-      int32_t nin = 0, npol = 0, nrows = 0, ncols = 0, nmax = 0;
-      if (nz_boardnet_dims(ag[i]->net, &nin, &npol, &nrows, &ncols, &nmax) != NZ_OK) return sfail(h, NZ_ERR_ARG, "agent %d: bad network handle", i + 1);
-      if (nin != R.channels || npol != R.planes || nrows != R.rows || ncols != R.cols)
-        return sfail(h, NZ_ERR_ARG, "agent %d: network is %d planes -> %d planes on %dx%d, the game needs %d -> %d on %dx%d", i + 1, nin, npol,
-                     nrows, ncols, R.channels, R.planes, R.rows, R.cols);
-      if (nmax < G) return sfail(h, NZ_ERR_ARG, "agent %d: network max_batch %d < %d matches", i + 1, nmax, G);
-      if (nz_boardnet_input_rows(ag[i]->net, &sd.net_rows, &sd.row_stride) != NZ_OK) return sfail(h, NZ_ERR_ARG, "agent %d: bad network handle", i + 1);
-    }
+    if (sd.kind == NZ_AGENT_POLICY)            // the network fits the game and holds every match's position
+      if (nz_status st = net_fits(h, ag[i]->net, i + 1, &sd.net_rows, &sd.row_stride)) return st;
   }
   if (nz_status st = nz_scs_search_reset_to(h, openings, stream)) return st;
   h->waves = 0;
@@ -3553,23 +3566,8 @@ extern "C" nz_status nz_scs_agent_match_result(nz_scs_search* h, nz_scs_match_ta
   if (!h) return sfail(h, NZ_ERR_ARG, "null argument");
   if (h->agents.kinds[0] < 0) return sfail(h, NZ_ERR_STATE, "no agent match round was played on this handle");
   S_HIP(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  const int G = h->n_games, MAX_MOVES = h->p.max_moves;
-  S_HIP(h, hipMemsetAsync(h->agents.tally.get(), 0, 8 * sizeof(int64_t), s));
-  hipLaunchKernelGGL(match_tally_kernel, dim3((G + 127) / 128), dim3(128), 0, s, match_side(h->p), MatchSide{}, G, MAX_MOVES,
-                     (const int32_t*)h->p.rec_action, (unsigned long long*)h->agents.tally.get());
-  S_HIP(h, hipGetLastError());
-  int64_t t[8];
-  S_HIP(h, hipMemcpyAsync(t, h->agents.tally.get(), sizeof(t), hipMemcpyDeviceToHost, s));
-  if (actions_dev)
-    S_HIP(h, hipMemcpyAsync(actions_dev, h->p.rec_action, (size_t)G * MAX_MOVES * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  S_HIP(h, hipStreamSynchronize(s));
-  if (t[7] != 0) return sfail(h, NZ_ERR_STATE, "internal: the action record of %lld matches has a gap", (long long)t[7]);
-  if (out_host) {
-    out_host->matches = t[0]; out_host->p1_wins = t[1]; out_host->p2_wins = t[2]; out_host->draws = t[3];
-    out_host->unfinished = t[4]; out_host->length_sum = t[5]; out_host->length_max = t[6];
-  }
-  return NZ_OK;
+  return tally_result(h, h->agents.tally.get(), MatchSide{}, h->p.rec_action, "internal: the action record of %lld matches has a gap",
+                      out_host, actions_dev, (hipStream_t)stream);
 }
 
 extern "C" nz_status nz_scs_agent_match_decisions(nz_scs_search* h, int32_t side, int32_t* actions_dev, int32_t* n_legal_dev,
@@ -3635,7 +3633,6 @@ extern "C" nz_status nz_scs_search_reset_to(nz_scs_search* h, const nz_scs_openi
   if (!h) return NZ_ERR_ARG;
   if (!o || o->max_plies == 0) return nz_scs_search_reset(h, stream);
   if (!openings_ok(h, o)) return NZ_ERR_ARG;
-  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
   S_HIP(h, hipSetDevice(h->device));
   const hipStream_t s = (hipStream_t)stream;
   const int G = h->n_games, P = o->max_plies;
@@ -3666,16 +3663,13 @@ extern "C" nz_status nz_scs_openings_draw(nz_scs_search* h, const uint32_t* seed
                                           int32_t* n_plies_out, void* stream) {
   if (!h || !seeds_host || !actions_out || !n_plies_out) return sfail(h, NZ_ERR_ARG, "null argument");
   if (plies < 1 || plies > h->p.max_moves) return sfail(h, NZ_ERR_ARG, "openings of %d plies: 1 .. %d", plies, h->p.max_moves);
-  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
   S_HIP(h, hipSetDevice(h->device));
   const hipStream_t s = (hipStream_t)stream;
   const int G = h->n_games;
   if (h->n_game_rows > 0) {                      // every match on its own map, as the match calls set it
     if (h->n_game_rows < G) return sfail(h, NZ_ERR_ARG, "%d matches, %lld maps set", G, (long long)h->n_game_rows);
-    std::vector<int32_t> ident(G);
-    for (int g = 0; g < G; ++g) ident[g] = g;
     S_HIP(h, hipStreamSynchronize(s));
-    S_HIP(h, hipMemcpy(h->rows.row.get(), ident.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nz_status st = slots_read_own_rows(h)) return st;
   }
   OpeningBufs& b = h->openings;
   if (!(b.seeds.ensure(G) && b.actions.ensure((size_t)G * plies) && b.n_plies.ensure(G) && b.err.ensure(G)))
@@ -3699,7 +3693,6 @@ extern "C" nz_status nz_scs_openings_expand(nz_scs_search* h, const int32_t* fro
   if (depth >= h->p.max_moves) return sfail(h, NZ_ERR_ARG, "prefixes of %d plies: 0 .. %d", depth, h->p.max_moves - 1);
   if (h->n_game_rows > 0)
     return sfail(h, NZ_ERR_STATE, "per-game maps are set: one frontier belongs to one map (draw openings per match instead)");
-  if (h->host_rules.planes > AGENT_MAX_PLANES) return sfail(h, NZ_ERR_STATE, "internal: %d action planes", h->host_rules.planes);
   const int A = h->p.num_actions;
   for (int f = 0; f < n; ++f)
     for (int ply = 0; ply < depth; ++ply) {

@@ -19,8 +19,6 @@
 namespace nz {
 namespace {
 
-static_assert(MT_N % 4 == 0, "keys are copied in 16-byte words");
-
 __global__ void ttt_match_reset_kernel(TttMatchArgs a, const uint32_t* __restrict__ start) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;          // over n * 9
   if (idx >= a.n * TTT_MAX_MOVES) return;
@@ -76,21 +74,7 @@ __global__ __launch_bounds__(64) void ttt_agent_move_kernel(TttMatchArgs a, int 
     }
     action = __shfl(at, 0, 64);
   } else {
-    const uint4* src = reinterpret_cast<const uint4*>(a.mt_keys[side] + (size_t)i * MT_N);
-    uint4* dst = reinterpret_cast<uint4*>(key);
-    for (int w = lane; w < MT_N / 4; w += 64) dst[w] = src[w];
-    __syncthreads();
-    const int pos0 = a.mt_pos[side][i];
-    Mt m{key, pos0, lane};
-    const int k = mt_randint(m, n_legal);
-    __syncthreads();
-    // at most MT_RANDINT_TRIES < 624 words are drawn: the position went down exactly when the state was twisted
-    if (m.pos < pos0) {
-      const uint4* s2 = reinterpret_cast<const uint4*>(key);
-      uint4* d2 = reinterpret_cast<uint4*>(a.mt_keys[side] + (size_t)i * MT_N);
-      for (int w = lane; w < MT_N / 4; w += 64) d2[w] = s2[w];
-    }
-    if (lane == 0) a.mt_pos[side][i] = m.pos;
+    const int k = mt_stream_randint(key, a.mt_keys[side], a.mt_pos[side], i, n_legal, lane);
     if (k < 0) {
       if (lane == 0) atomicOr(&a.err[i], TTT_AGENT_ERR_CAP);
       return;

@@ -49,6 +49,29 @@ def _same_game(c1, c2):
     return all(np.array_equal(np.asarray(getattr(c1, k)), np.asarray(getattr(c2, k))) for k in _MAP_FIELDS)
 
 
+def _map_seeds(cfg, seeds, n_matches):
+    """The seeds of the matches' maps: a per_game config needs one per match (returned as a list); any other config
+    draws no map and `seeds` passes through."""
+    if not cfg.per_game:
+        return seeds
+    if seeds is None:
+        raise ValueError("a per_game config draws one map per match: pass seeds")
+    seeds = list(seeds)
+    if len(seeds) != n_matches:
+        raise ValueError(f"{len(seeds)} seeds for {n_matches} matches")
+    return seeds
+
+
+def _round_result(engine, tally, actions):
+    """The dict ScsMatch.play returns: a result call's tally and action record [N, MAX_MOVES], and the status of the
+    engine that holds the games."""
+    st = engine.status()
+    out = {k: int(getattr(tally, k)) for k, _ in type(tally)._fields_}
+    out["actions"] = actions[:, :max(1, out["length_max"])].cpu().numpy()
+    out["lengths"], out["outcomes"], out["finished"] = st[:, 6].copy(), st[:, 5].copy(), st[:, 4] != 0
+    return out
+
+
 class ScsMatch:
     """n_matches matches between agent 1 (search_cfg_1) and agent 2 (search_cfg_2).  `config`: an ScsGameConfig (or a
     path), or a pair of them, one per agent, which must describe the same game.  `agents`: the two ScsSelfPlay engines
@@ -97,12 +120,8 @@ class ScsMatch:
         import torch
         from . import _lib
         a1, a2 = self.agents
+        seeds = _map_seeds(self.cfg, seeds, self.n_matches)
         if self.cfg.per_game:
-            if seeds is None:
-                raise ValueError("a per_game config draws one map per match: pass seeds")
-            seeds = list(seeds)
-            if len(seeds) != self.n_matches:
-                raise ValueError(f"{len(seeds)} seeds for {self.n_matches} matches")
             a1.set_games(seeds)
             a2.set_games(seeds)
         stream = c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -114,11 +133,7 @@ class ScsMatch:
         tally = _lib.ScsMatchTally()
         actions = torch.empty((self.n_matches, a1.MAX_MOVES), dtype=torch.int32, device=a1.device)
         a1._check(_lib.lib.nz_scs_match_result(a1._h, a2._h, byref(tally), c_void_p(actions.data_ptr()), stream))
-        st = a1.status()
-        out = {k: int(getattr(tally, k)) for k, _ in _lib.ScsMatchTally._fields_}
-        out["actions"] = actions[:, :max(1, out["length_max"])].cpu().numpy()
-        out["lengths"], out["outcomes"], out["finished"] = st[:, 6].copy(), st[:, 5].copy(), st[:, 4] != 0
-        return out
+        return _round_result(a1, tally, actions)
 
 
 def _agent_spec(spec):
@@ -196,13 +211,7 @@ class ScsAgentMatch:
                     raise ValueError(f"agent {i + 1}: {len(sides[i])} agent_seeds for {self.n_matches} matches")
                 from .scs import _seed_array
                 per_side[i] = _seed_array(sides[i])
-        if self.cfg.per_game:
-            if seeds is None:
-                raise ValueError("a per_game config draws one map per match: pass seeds")
-            seeds = list(seeds)
-            if len(seeds) != self.n_matches:
-                raise ValueError(f"{len(seeds)} seeds for {self.n_matches} matches")
-        return seeds, per_side
+        return _map_seeds(self.cfg, seeds, self.n_matches), per_side
 
     def play(self, net1, net2, seeds=None, agent_seeds=None, max_moves=None, start_actions=None, n_plies=None):
         """One round, as ScsMatch.play (`start_actions` / `n_plies`: match i from its opening; a random side's stream
@@ -232,11 +241,8 @@ class ScsAgentMatch:
         tally = _lib.ScsMatchTally()
         actions = torch.empty((self.n_matches, e.MAX_MOVES), dtype=torch.int32, device=e.device)
         e._check(_lib.lib.nz_scs_agent_match_result(e._h, byref(tally), c_void_p(actions.data_ptr()), stream))
-        st = e.status()
-        out = {k: int(getattr(tally, k)) for k, _ in _lib.ScsMatchTally._fields_}
-        T = max(1, out["length_max"])
-        out["actions"] = actions[:, :T].cpu().numpy()
-        out["lengths"], out["outcomes"], out["finished"] = st[:, 6].copy(), st[:, 5].copy(), st[:, 4] != 0
+        out = _round_result(e, tally, actions)
+        T = out["actions"].shape[1]
         out["agent_actions"], out["agent_n_legal"], out["agent_probs"] = [None, None], [None, None], [None, None]
         for i, kind in enumerate(self.kinds):
             if kind == "mcts":
@@ -385,8 +391,6 @@ class ScsTester:
             for k, v in agent_results(r["outcomes"], i == 1, r["finished"]).items():
                 total[k] += v
         return total
-
-    Test_using_agents = test_using_agents
 
 
 # ---- Tic-Tac-Toe -------------------------------------------------------------------------------------------------------
