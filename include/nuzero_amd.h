@@ -808,7 +808,8 @@ nz_status nz_scs_agent_record_read(nz_scs_search* h, int32_t side, int32_t slot,
  * a prefix's end), n_plies_out int32 [n_games].  Touches no game of the engine.  Synchronises.
  * nz_scs_openings_expand: one level of the enumeration of all openings.  frontier_host int32 [n_prefixes][depth]
  * (depth >= 0; depth 0: the start, frontier_host may be NULL): each prefix is replayed from the start.  counts_host
- * int32 [n_prefixes] receives the number of legal actions after each prefix (0: the game is over there).  With
+ * int32 [n_prefixes] receives the number of legal actions after each prefix (0: the game is over there, or it is a live
+ * position without a legal action -- a placement whose every arrival tile the enemy holds).  With
  * children_host non-NULL (keys_host too) the call also writes, at the exclusive scan of the counts, the child prefixes
  * children_host int32 [sum of counts][depth + 1] in ascending action order and keys_host uint64 [sum of counts][2],
  * the 128-bit digest of each child position's planes (the digest nz_scs_search_record_read reports for a leaf; equal

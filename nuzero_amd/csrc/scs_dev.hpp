@@ -221,14 +221,23 @@ struct Scs {
     remove(u, s.tile[u]);
     s.status[u] = SCS_DEAD;
   }
-  // first strict maximum of (k1, k2, movement allowance) in list order (:1253-1285)
+  // first strict maximum of (k1, k2, movement allowance) in list order (:1253-1285).  The tuple is compared as ONE
+  // integer (the statistics are int8: + 128 makes each a byte, most significant key first).  Written as nested
+  // comparisons, `a1 > b1 || (a1 == b1 && (a2 > b2 || ...))`, the one-lane kernels came out of the compiler keeping the
+  // first key only -- the select on the inner comparisons' result was dropped -- and no test had a second key decide
+  // until tests/test_gpu_scs_directed.py.
+  __device__ int strength(int u, bool attacker) const {
+    const int k1 = attacker ? r.u_attack[u] : r.u_defense[u], k2 = attacker ? r.u_defense[u] : r.u_attack[u];
+    return ((k1 + 128) << 16) | ((k2 + 128) << 8) | (r.u_mov[u] + 128);
+  }
   __device__ int strongest(const int8_t* list, int n, bool attacker) const {
-    int best = list[0];
-    for (int i = 0; i < n; ++i) {
-      const int u = list[i];
-      const int a1 = attacker ? r.u_attack[u] : r.u_defense[u], b1 = attacker ? r.u_attack[best] : r.u_defense[best];
-      const int a2 = attacker ? r.u_defense[u] : r.u_attack[u], b2 = attacker ? r.u_defense[best] : r.u_attack[best];
-      if (a1 > b1 || (a1 == b1 && (a2 > b2 || (a2 == b2 && r.u_mov[u] > r.u_mov[best])))) best = u;
+    int best = list[0], best_key = strength(best, attacker);
+    for (int i = 1; i < n; ++i) {
+      const int key = strength(list[i], attacker);
+      if (key > best_key) {
+        best = list[i];
+        best_key = key;
+      }
     }
     return best;
   }

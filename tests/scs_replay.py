@@ -80,8 +80,9 @@ ORACLE_NET_TOL = 1e-5
 
 def replay_game(args):
     """(config path, search config, seed, training, digests [n,8], probs [n,A], values [n], max_moves[, options]) ->
-    trace dict.  options (optional): "per_game" (bool), "oracle_net" ((weights, arch, depth) of a feed-forward board
-    net: FeedForwardRef).  The result also holds the run's path-depth measures and the live tree's peak node count.
+    trace dict.  options (optional): "per_game" (bool), "prefix" (actions stepped before the first search: the trace
+    then starts at decision len(prefix)), "oracle_net" ((weights, arch, depth) of a feed-forward board net:
+    FeedForwardRef).  The result also holds the run's path-depth measures and the live tree's peak node count.
     Top-level so it can run in a worker process (CPU only: nothing here touches the GPU)."""
     config_path, search, seed, training, digests, probs, values, max_moves = args[:8]
     options = args[8] if len(args) > 8 and args[8] else {}
@@ -91,6 +92,8 @@ def replay_game(args):
     # per-game maps: ONE stream, the game's map drawn first and its search going on with it
     cfg = ScsConfig(config_path, map_seed=rs) if options.get("per_game") else ScsConfig(config_path)
     game = ScsGame(cfg)
+    for a in options.get("prefix", ()):          # the search starts at the position an opening leads to (reset_to)
+        game.step_index(int(a))
     ref = None
     if options.get("oracle_net") is not None:
         from scipy.special import softmax
@@ -155,10 +158,11 @@ def replay_games(jobs, workers=None):
         return list(ex.map(replay_game, jobs))
 
 
-def assert_trace_equals_device(r, g, out, label=""):
-    """Every root statistic of game g of a device export `r` equals the oracle replay `out`, bit for bit."""
+def assert_trace_equals_device(r, g, out, label="", first=0):
+    """Every root statistic of game g of a device export `r` equals the oracle replay `out`, bit for bit.  `first`: the
+    decision number of the replay's first move (the plies of the "prefix" option the replay started behind)."""
     trace = out["trace"]
-    for m, mv in enumerate(trace):
+    for m, mv in enumerate(trace, first):
         k = len(mv["child_actions"])
         where = (label, g, m)
         assert r["actions"][g, m] == mv["action"], where
