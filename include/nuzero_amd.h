@@ -619,8 +619,13 @@ nz_status nz_scs_search_waves(const nz_scs_search* h, int64_t* waves);
 /* The persistent route of nz_scs_search_play / _play_moves / _play_round: one wavefront per game runs the whole
  * search of a move -- descent, rules, the network for its own leaf, expansion, backup (Explorer.run_mcts,
  * Search/Explorer.py:40-67, with one simulation in flight per tree, :49-61) -- in ONE launch per move, no game waiting
- * for another.  Available for ConvNet / ResNet board nets on boards of up to 32 cells whose layers are at most 64
- * channels wide, with or without the inference cache; other configurations keep the wave-by-wave route.
+ * for another.  Available, with or without the inference cache, for ConvNet / ResNet board nets
+ *   - on boards of up to 32 cells, with layers of at most 64 channels and head layers no wider than the padded trunk,
+ *   - whose input planes, padded to 16, fill whole 32-channel groups (17..32, 49..64, 81..96 or 113..128 planes: the
+ *     86 of stacking limit 2, not the 67 and 105 of stacking limits 1 and 3),
+ *   - one position of which fits a wavefront's 38 KB of LDS and four games' blocks a workgroup's 160 KB: with 86 planes
+ *     up to 30 cells at widths of up to 32, up to 18 cells at widths 33..64 (DESIGN.md section 7 has the table);
+ * other configurations keep the wave-by-wave route (the same games, slower).
  * enable: 1 require it (a play fails where it is not available), 0 never, -1 the default (use it where available).
  * *used (may be NULL): whether the last play ran on it. */
 nz_status nz_scs_search_persistent(nz_scs_search* h, int32_t enable, int32_t* used);

@@ -1901,6 +1901,11 @@ bool nz::boardnet_wave_program(nz_boardnet* h, nz::WaveNet* out, std::string* wh
   const size_t stage = (size_t)rows * h->inp;
   off += std::max(3 * act, (stage + 3) / 4 * 4);
   if (off * sizeof(float) > 38 * 1024) return no("the activations of one position do not fit a wavefront's share of LDS");
+  // The input pieces' space is the logits', the value plane's and a hidden buffer's from the first layer on, and
+  // split_planes_half writes a leaf's inp / 8 chunks only: with half a 32-channel group left over (67 or 105 planes:
+  // inp = 80, 112) the first layer's last K group reads the other half as the last pass left it -- float32 rows taken
+  // for bf16, not always finite (zero weights do not help then).  Seen on the device: NaN values, wrong probabilities.
+  if (h->inp % 32 != 0) return no("the input planes do not fill whole 32-channel groups");
   pg.lds_floats = (int32_t)off;
   pg.zrow_index = rows;
   pg.n_ops = n_ops;

@@ -7,10 +7,13 @@ import numpy as np
 
 
 def replay_keeping_planes(args):
-    """(config path, search config, seed, digests uint64 [n, 2], probs [n, A], values [n]) -> {"trace", "length",
-    "terminal_value", "evaluations_used", "planes" float32 [n, C, rows, cols]}: the planes in the order the device's
-    search consumed the evaluations, each checked against the recorded digest."""
-    path, search, seed, dig, probs, values = args
+    """(config path, search config, seed, digests uint64 [n, 2], probs [n, A], values [n][, max_moves]) -> {"trace",
+    "length", "terminal", "terminal_value", "evaluations_used", "evaluations_recorded", "planes" float32 [n, C, rows,
+    cols]}: the planes in the order the device's search consumed the evaluations, each checked against the recorded
+    digest.  max_moves (optional; None or 0: the whole game): the replay stops after that many decisions, as
+    play_native(..., max_moves) does; terminal_value is then None unless the game ended within them."""
+    path, search, seed, dig, probs, values = args[:6]
+    max_moves = args[6] if len(args) > 6 else None
     from oracle import search as osearch
     from oracle.scs import ScsConfig, ScsGame
     from scs_replay import image_mix_digest
@@ -31,7 +34,7 @@ def replay_keeping_planes(args):
 
     explorer = osearch.Explorer(search, True, rs)
     root, trace = osearch.Node(0), []
-    while not game.is_terminal():
+    while not game.is_terminal() and (not max_moves or len(trace) < max_moves):
         action, chosen, bias = explorer.run_mcts(game, ev, root)
         trace.append({"action": int(action), "root_visits": int(root.visit_count), "root_value_sum": float(root.value_sum),
                       "bias": float(bias), "child_actions": [c.action for c in root.children],
@@ -40,8 +43,10 @@ def replay_keeping_planes(args):
                       "child_value_sums": [float(c.value_sum) for c in root.children]})
         game.step_index(action)
         root = chosen
-    return {"trace": trace, "length": game.length, "terminal_value": game.terminal_value, "evaluations_used": cursor[0],
-            "planes": np.stack(planes)}
+    terminal = bool(game.is_terminal())
+    return {"trace": trace, "length": game.length, "terminal": terminal,
+            "terminal_value": game.terminal_value if terminal else None, "evaluations_used": cursor[0],
+            "evaluations_recorded": len(values), "planes": np.stack(planes)}
 
 
 def replay_games_keeping_planes(jobs, workers=None):

@@ -13,6 +13,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 @pytest.mark.parametrize("name,n_games", [("mirrored_5x5", 48), ("late_reinforcements_5x5", 48),
                                           ("two_types_6x5", 48), ("ten_by_ten", 12), ("wide_arrival_10x10", 8),
                                           ("reference_test_config", 12),
+                                          ("tiny_4x4", 24), ("tiny_3x6", 24), ("stack1_4x4", 24), ("stack3_4x4", 24),
                                           ("randomized_5x5@7", 24), ("randomized_10x10@2", 8)])
 def test_scs_device_rules_equal_oracle(name, n_games):
     """(name@seed: a "Randomized" configuration of the reference with the map it draws after np.random.seed(seed) --
