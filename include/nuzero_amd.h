@@ -448,6 +448,16 @@ nz_status nz_scs_status(nz_scs* h, int32_t* status_dev, void* stream);
  *   repeat: select(images [G][C][R][Cc], leaf_game [G], &n) ; if n == 0 break ;
  *           evaluate images[0..n) ; expand(probs [n][A], value [n])
  *   end_move(uniforms [G][3])
+ * The kernels OR their checks into one device word; the calls that synchronise (select, end_move, apply, the play
+ * and match loops) return NZ_ERR_OVERFLOW with the word and its meanings in the message while any bit is set, until the
+ * next reset: 1 arena full, 2 visit table / path too short, 4 a move ended before its search (simulations left or a leaf
+ * pending), 8 forced action not legal, 16 more legal actions than the bound computed at create, 32 game longer than that
+ * bound, 64 RESERVED (the match check reports in the same word that its two engines no longer hold the same game),
+ * 128 the position has no legal action although the game is not over: a searched root (no simulation left, no leaf
+ * pending) without a child.  The reference raises there (IndexError in max_action); the move's simulations have run (each
+ * evaluated the root), no action is played for that game, the other games of the call complete their move, and the
+ * message names the first such game and its decision number.  Inside the tree such a node is evaluated at every visit,
+ * gets no children and its value is backed up, as the reference does.
  * nodes_per_game sizes each game's tree arena: two halves; at every re-root the new root's subtree is copied
  * into the other half (the rest of the tree is dropped), so a half must hold the kept subtree plus one move's
  * expansions (32 bytes per node; a full half is reported as NZ_ERR_OVERFLOW).  nodes_per_game <= 0: the default,
@@ -465,6 +475,10 @@ nz_status nz_scs_search_select(nz_scs_search* h, float* images_dev, int32_t* lea
                                int32_t* n_leaves_host, void* stream);
 nz_status nz_scs_search_expand(nz_scs_search* h, const float* probs_dev, const float* value_dev, void* stream);
 nz_status nz_scs_search_end_move(nz_scs_search* h, const double* uniforms_dev, void* stream);
+/* Test hook: the legal masks stored with the pending leaves, masks_dev uint32[G][*words_host] (action a: bit a & 31 of
+ * word a >> 5; masks_dev NULL: the row length alone).  A row is meaningful between select and expand, for the games of
+ * leaf_game; an all-zero row is a live position without a legal action (its expansion makes no child). */
+nz_status nz_scs_search_leaf_masks(nz_scs_search* h, uint32_t* masks_dev, int32_t* words_host, void* stream);
 /* status_dev int32[G][7] as nz_scs_status */
 nz_status nz_scs_search_status(nz_scs_search* h, int32_t* status_dev, void* stream);
 /* Per move m < M of game g (dev pointers, any may be NULL; M = max_moves, C = max_children of

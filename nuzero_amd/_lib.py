@@ -159,6 +159,7 @@ SIGNATURES = {
     "nz_scs_search_reset": (c_int32, [c_void_p, c_void_p]),
     "nz_scs_search_root_children": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nz_scs_search_begin_move": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "nz_scs_search_leaf_masks": (c_int32, [c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     "nz_scs_search_select": (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     "nz_scs_search_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nz_scs_search_end_move": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -105,7 +105,7 @@ struct SearchParams {
   int32_t* hit_count;      // [1] hits of this wave
   float* eval_probs;       // [3 G][A] evaluations: the network's [0, G), cache hits [G, 2 G) / [2 G, 3 G) by wave parity
   float* eval_value;       // [3 G]
-  int32_t* error_flag;
+  int32_t* error_flag;     // [3] the flag word (FLAG_TEXT); game and decision of the first root found without a legal action (-1, -1: none)
   int64_t* counters;       // [16] simulations, expansions; [8] cache hits, [9] misses, [10] entries in use; [2..7] shader ticks per phase of the NZ_SCS_STAMPS diagnostic build
   // records [G][max_moves]...
   int32_t* rec_action;
@@ -309,6 +309,7 @@ __global__ void search_reset_kernel(SearchParams p) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g == 0) {
     *p.leaf_count = 0; *p.active_count = 0; *p.error_flag = 0;
+    p.error_flag[1] = -1; p.error_flag[2] = -1;
     for (int i = 0; i < 16; ++i)
       if (i < 8 || i > 10) p.counters[i] = 0;      // [8..10] belong to the inference cache (nz_scs_search_cache)
   }
@@ -1721,7 +1722,11 @@ __global__ void end_move_kernel(SearchParams p, const double* __restrict__ unifo
   const SNode root = nodes[p.root[g]];
   const int k = root.n_children, move = real.length;
   if (k == 0 || p.sims_left[g] != 0 || p.pending[g] >= 0 || move >= p.max_moves) {
-    atomicOr(p.error_flag, move >= p.max_moves ? 32 : 4);
+    // a searched root without a child: a live position without a legal action ("Dead ends").  The move's
+    // simulations all evaluated the root; the reference raises in max_action here.  The first game to say so is named.
+    const bool dead_end = k == 0 && p.sims_left[g] == 0 && p.pending[g] < 0 && move < p.max_moves;
+    atomicOr(p.error_flag, move >= p.max_moves ? 32 : dead_end ? 128 : 4);
+    if (dead_end && atomicCAS(&p.error_flag[1], -1, g) == -1) p.error_flag[2] = move;
     return;
   }
   const size_t gm = (size_t)g * p.max_moves + move;
@@ -1877,7 +1882,7 @@ struct CreateBufs {               // nz_scs_search_create, for the handle's life
 #define MADE(f, n) (f.ensure(n) && (p.f = f.get()))
     return whole(this, rules.ensure(1) && leaf_count.ensure(6) && MADE(real, G) && MADE(scratch, G) && MADE(nodes, G * (size_t)p.cap) &&
                            MADE(half, G) && MADE(node_count, G) && MADE(root, G) && MADE(sims_left, G) && MADE(pending, G) &&
-                           MADE(path, G * (size_t)p.max_path) && MADE(path_len, G) && MADE(leaf_mask, G * MASK_WORDS) && MADE(error_flag, 1) &&
+                           MADE(path, G * (size_t)p.max_path) && MADE(path_len, G) && MADE(leaf_mask, G * MASK_WORDS) && MADE(error_flag, 3) &&
                            MADE(counters, 16) && MADE(bias_tab, tab) && MADE(sqrt_tab, tab) && MADE(rec_action, GM) && MADE(rec_tree_size, GM) &&
                            MADE(rec_children, GM) && MADE(rec_bias, GM) && MADE(rec_root_value_sum, GM) && MADE(rec_child_action, GMC) &&
                            MADE(rec_child_visit, GMC) && MADE(rec_child_prior, GMC) && MADE(rec_child_value_sum, GMC));
@@ -2098,8 +2103,20 @@ nz_status sfail(nz_scs_search* h, nz_status code, const char* fmt, ...) {
     hipError_t e__ = (call);                                                                      \
     if (e__ != hipSuccess) return sfail((h), NZ_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
   } while (0)
+// (bit 64 is the match check's: match_live_kernel reports "the engines no longer hold the same game" in the same word)
 constexpr const char* FLAG_TEXT = "1 arena full, 2 visit table/path too short, 4 move ended before its search, 8 forced action is not legal, "
-                                  "16 more legal actions than the bound computed at create, 32 game longer than that bound";
+                                  "16 more legal actions than the bound computed at create, 32 game longer than that bound, "
+                                  "128 the position has no legal action";
+// what a check appends to its message when flag 128 is set: the first game that reached such a position and its decision number
+std::string dead_end_text(nz_scs_search* h, int32_t flag, hipStream_t s) {
+  if (!(flag & 128)) return "";
+  int32_t at[2] = {-1, -1};
+  if (hipMemcpyAsync(at, h->p.error_flag + 1, sizeof(at), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return "";
+  char buf[128];
+  snprintf(buf, sizeof(buf), "; game %d, decision %d: the position has no legal action and the game is not over", at[0], at[1]);
+  return buf;
+}
 // the (leaf, active, cache hit) counter pointers at rest: the first triple, zeroed by the host (a wave-by-wave play leaves the last wave's)
 void rest_counters(nz_scs_search* h) {
   int32_t* const counters = h->made.leaf_count.get();
@@ -2110,7 +2127,7 @@ nz_status check_flag(nz_scs_search* h, hipStream_t s) {
   int32_t f = 0;
   S_HIP(h, hipMemcpyAsync(&f, h->p.error_flag, sizeof(f), hipMemcpyDeviceToHost, s));
   S_HIP(h, hipStreamSynchronize(s));
-  if (f) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s)", f, FLAG_TEXT);
+  if (f) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s%s)", f, FLAG_TEXT, dead_end_text(h, f, s).c_str());
   return NZ_OK;
 }
 // What nz_scs_search_reset_to refuses before any launch (nuzero_amd.scs_positions.check_openings is its twin); false: the
@@ -2283,6 +2300,19 @@ nz_status nz_scs_search_root_children(nz_scs_search* h, int32_t* out_dev, void* 
   S_HIP(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(root_children_kernel, dim3((h->n_games + 127) / 128), dim3(128), 0, (hipStream_t)stream, h->p, out_dev);
   S_HIP(h, hipGetLastError());
+  return NZ_OK;
+}
+
+// Test hook: the legal masks the searches stored with their pending leaves, one row of `*words_host` 32-bit words per game
+// (action a is bit a & 31 of word a >> 5; all zero: a live position without a legal action).  masks_dev may be NULL (the
+// row length alone).  A row is meaningful between nz_scs_search_select and nz_scs_search_expand for the games of leaf_game.
+nz_status nz_scs_search_leaf_masks(nz_scs_search* h, uint32_t* masks_dev, int32_t* words_host, void* stream) {
+  if (!h) return NZ_ERR_ARG;
+  if (words_host) *words_host = MASK_WORDS;
+  if (!masks_dev) return NZ_OK;
+  S_HIP(h, hipSetDevice(h->device));
+  S_HIP(h, hipMemcpyAsync(masks_dev, h->p.leaf_mask, (size_t)h->n_games * MASK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
   return NZ_OK;
 }
 
@@ -3373,7 +3403,8 @@ extern "C" nz_status nz_scs_match_play_from(nz_scs_search* a1, nz_boardnet* net1
     const int32_t f1 = m.pinned[1], f2 = m.pinned[2];
     if (f1 & 64) return sfail(a1, NZ_ERR_STATE, "internal: the two engines no longer hold the same games");
     if (f1 || f2)
-      return sfail(a1, NZ_ERR_OVERFLOW, "device check failed (agent 1 flag %d, agent 2 flag %d: %s)", f1, f2, FLAG_TEXT);
+      return sfail(a1, NZ_ERR_OVERFLOW, "device check failed (agent 1 flag %d, agent 2 flag %d: %s%s)", f1, f2, FLAG_TEXT,
+                   (f1 & 128 ? dead_end_text(a1, f1, s1) : dead_end_text(a2, f2, s1)).c_str());
     *live = m.pinned[0];
     return NZ_OK;
   };
@@ -3524,7 +3555,8 @@ extern "C" nz_status nz_scs_agent_match_play_from(nz_scs_search* h, const nz_scs
     S_HIP(h, agent_live_launch(h->p.real, G, h->p.error_flag, b.err.get(), b.state.get(), s));
     S_HIP(h, hipMemcpyAsync(b.pinned.get(), b.state.get(), 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     S_HIP(h, hipStreamSynchronize(s));
-    if (b.pinned[1]) return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s)", b.pinned[1], FLAG_TEXT);
+    if (b.pinned[1])
+      return sfail(h, NZ_ERR_OVERFLOW, "device check failed (flag %d: %s%s)", b.pinned[1], FLAG_TEXT, dead_end_text(h, b.pinned[1], s).c_str());
     if (b.pinned[2])
       return sfail(h, NZ_ERR_OVERFLOW, "scripted agent check failed (flags %d: 1 randint rejection cap, 2 no legal action, "
                    "4 game longer than the bound computed at create)", b.pinned[2]);

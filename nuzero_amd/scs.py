@@ -524,6 +524,16 @@ class ScsSelfPlay:
         self._check(lib.nz_scs_search_apply(self._h, c_void_p(a.data_ptr()) if a is not None else None,
                                             c_void_p(u.data_ptr()) if u is not None else None, self._stream()))
 
+    def leaf_masks(self):
+        """Test hook (nz_scs_search_leaf_masks): the legal masks stored with the pending leaves as bool [G, num_actions];
+        meaningful inside the evaluator of search(), for the games of `_leaf_game`."""
+        words = c_int32(0)
+        self._check(lib.nz_scs_search_leaf_masks(self._h, None, byref(words), self._stream()))
+        m = torch.empty((self.n_games, int(words.value)), dtype=torch.int32, device=self.device)
+        self._check(lib.nz_scs_search_leaf_masks(self._h, c_void_p(m.data_ptr()), byref(words), self._stream()))
+        bits = np.unpackbits(m.cpu().numpy().view(np.uint8), axis=1, bitorder="little")
+        return bits[:, :self.cfg.num_actions].astype(bool)
+
     def last_actions(self):
         out = torch.empty((self.n_games,), dtype=torch.int32, device=self.device)
         self._check(lib.nz_scs_search_last_actions(self._h, c_void_p(out.data_ptr()), self._stream()))

@@ -244,8 +244,7 @@ def test_searches_from_positions_deep_in_directed_play_equal_the_oracle():
     replays the move from them -- each consumed leaf's image in order, then the root statistics, bit for bit.
     Library route, wave by wave (images staged in the network's input rows): the same decision with the same root
     statistics.  The persistent route has no form for this shape (105 input planes on 30 cells do not fit a
-    wavefront's share of LDS) and must say so before anything is launched.
-    No search here starts at or next to a dead end: directed_6x5 arrives on whole board sides."""
+    wavefront's share of LDS) and must say so before anything is launched."""
     from nuzero_amd._lib import NzError
     from nuzero_amd.scs import ScsGameConfig, ScsSelfPlay
     from nuzero_amd.tester import ScsMatch
